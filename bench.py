@@ -12,9 +12,12 @@ tensors are all-gathered over RCCL on a side stream while the local decode runs.
 same loop on BASELINE config C5's per-GPU share (SNAC 44.1 kHz + LocalMHA, 8 x 5 s clips per GPU, the four code
 levels of a clip gathered in one collective).
 
-The JSON line carries
-  * `ms_per_step` / `value` from the wall clock around EXACTLY --steps steps (profiler off; barrier + synchronise both sides; max over
-    ranks), `ms_per_step_median` from HIP events recorded between the steps, `encode_only` / `decode_only` (SURVEY 8d);
+A plain run sets up, warms up, times the steps and prints the JSON line with the headline figures: `ms_per_step` / `value` from the
+wall clock around EXACTLY --steps steps (profiler off; barrier + synchronise both sides; max over ranks) and `ms_per_step_median` from
+HIP events recorded between the steps.  `--dump-outputs DIR` writes what the last timed step computed (codes, zQ, latents, PCM; float32
+or float64 .npy files) to DIR, for output-by-output comparisons of two builds on the same seeded inputs.  Everything else below runs
+only with `--full`; the line of a `--full` run also carries
+  * `encode_only` / `decode_only` (SURVEY 8d);
   * `roofline` for the dominant kernel class (the dilated k=7 residual-unit convolutions, fp32 matrix-core implicit
     GEMM: bound "mfma", peak = 157.3 TFLOP/s dense fp32 MFMA on MI355X) measured with HIP events on the launch stream in a
     second pass of the same --steps steps (the per-launch event pairs stay out of the timed region);
@@ -25,7 +28,8 @@ The JSON line carries
     one warm-up + 3 timed passes over 8 clips, median;
   * `extra_configs` (N=1 only): BASELINE configs C3 (Encodec 48 kHz stereo, 16 x 2 s), C5's per-GPU share and C1
     (SNAC 24 kHz, 1 x 1 s) on the same GPU: ms, x real-time, compact per-class HIP-event table, dominant kernel class with its
-    roofline fraction and a GPU == oracle check on one clip; their step times also as flat top-level keys (c3_... / c5_share_... / c1_...).
+    roofline fraction and a GPU == oracle check on one clip; their step times also as flat top-level keys (c3_... / c5_share_... / c1_...);
+  * with N > 1 (and `--local-group`): the check of every gathered slot against a 1-GPU encode of the same clips.
   The line is kept small (about 4 KB); the full per-class tables are written to gpurun_out/bench_detail.json (NC_BENCH_DETAIL=<path>).
   `roofline.traffic` comes from profiles/traffic.json only when the loaded library's SHA-256 equals the one recorded there
   (else null + "traffic_stale": true).
@@ -330,6 +334,26 @@ def median(v):
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the last timed step handed back, one `out_dir/<name>.npy` each -- integer codes as float64 (exact),
+    everything else as float32.  Above 64 MB in all, every array keeps the same leading fraction of its clips (a fixed sample: the
+    first clips of the batch)."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, DUMP_LIMIT_BYTES / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if keep < 1.0:
+            a = a[:max(1, int(a.shape[0] * keep))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def run_local_group(args):
     """`--local-group`: ONE process drives --gpus devices through nc_group_create_local (ncclCommInitAll + grouped in-place all-gathers on
     per-device side streams): the layout of a single C# host (Examples/Program.cs:228-322 batches in one process).  Every device holds
@@ -403,8 +427,10 @@ def run_local_group(args):
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     for m in models:
         m.check_errors()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict({"codes_gathered": call[0]}, **{f"audio_device{d}": a for d, a in enumerate(audio)}))
     ok = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         # every device's copy of the gathered tensor equals every other's, and slot d equals a plain encode of block d on device d
         ok = all(torch.equal(call[0].cpu(), call[d].cpu()) for d in range(1, n))
         for d, m in enumerate(models):
@@ -412,14 +438,16 @@ def run_local_group(args):
                 want = torch.cat([c.reshape(B, -1) for c in m.encode(blocks[d])], dim=1) if snac_mode else m.encode(blocks[d])[1]
                 torch.cuda.synchronize(d)
             ok = ok and bool(torch.equal(call[d][d * B:(d + 1) * B].reshape(B, -1), want.reshape(B, -1)))
-    models[0].profile_enable(True)
-    models[0].profile_reset()
-    for _ in range(args.steps):
-        step()
-    sync()
-    prof = models[0].profile_read()
-    models[0].profile_enable(False)
-    classes = class_table(prof, args.steps, None)
+    classes = None
+    if args.full:
+        models[0].profile_enable(True)
+        models[0].profile_reset()
+        for _ in range(args.steps):
+            step()
+        sync()
+        prof = models[0].profile_read()
+        models[0].profile_enable(False)
+        classes = class_table(prof, args.steps, None)
     g.dispose()
     for m in models:
         m.dispose()
@@ -431,9 +459,11 @@ def run_local_group(args):
            "data": "synthetic",
            "config": {"workload": ("SNAC 44.1kHz + LocalMHA" if snac_mode else "DAC 44.1kHz 8kbps") + " encode+decode, batch=%d x %.0f s clips per GPU" % (B, seconds),
                       "clips_per_gpu": B, "clip_seconds": seconds, "global_batch": n * B, "launch": "one host process, nc_group_create_local",
-                      "collective": "grouped RCCL all_gather of the codes, in place, one side stream per device" + (", %d-bit packed" % args.pack_bits if args.pack_bits else ""),
-                      "gathered_equals_1gpu_every_slot_every_device": ok},
-           "roofline": dict(dominant(classes) or {}, all_classes=classes, note="device 0's launches"), "cpu_baseline": None}
+                      "collective": "grouped RCCL all_gather of the codes, in place, one side stream per device" + (", %d-bit packed" % args.pack_bits if args.pack_bits else "")},
+           }
+    if args.full:
+        out["config"]["gathered_equals_1gpu_every_slot_every_device"] = ok
+        out.update(roofline=dict(dominant(classes) or {}, all_classes=classes, note="device 0's launches"), cpu_baseline=None)
     assert ok is not False, "gathered codes differ between devices or from the plain encode"
     print(json.dumps(out), flush=True)
     return 0
@@ -458,6 +488,9 @@ def main():
     ap.add_argument("--check", action="store_true", help="(default now) kept for compatibility")
     ap.add_argument("--local-group", action="store_true", help="ONE process drives --gpus devices through nc_group_create_local (single-host layout)")
     ap.add_argument("--launch-timeout", type=int, default=3300, help="self-launched ranks are stopped after this many seconds")
+    ap.add_argument("--full", action="store_true", help="also the measurements and checks beyond the headline: profiler pass + roofline, "
+                    "encode-only / decode-only, extra configs, CPU baselines, GPU == oracle and gathered-slot checks, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.local_group:
@@ -522,7 +555,7 @@ def main():
             audio = model.decode(codes, noise)
             if use_dist:
                 torch.cuda.current_stream().wait_stream(side)
-            return codes, None, audio
+            return codes, None, audio, None
     else:
         cfg = DACConfig.dac_44khz()
         sd = dac_synthetic_state_dict(cfg, seed=42)
@@ -548,7 +581,7 @@ def main():
             audio = model.decode(z)
             if use_dist:
                 torch.cuda.current_stream().wait_stream(side)
-            return codes, z, audio
+            return codes, z, audio, lat
 
     def sync():
         if use_dist:
@@ -564,7 +597,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        codes, z, audio = step()
+        codes, z, audio, lat = step()
         marks[i + 1].record()
     sync()
     dt = time.perf_counter() - t0
@@ -573,34 +606,41 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        outs = {f"codes{i}": c for i, c in enumerate(codes)} if snac_mode else {"codes": codes, "z": z, "latents": lat}
+        outs["audio"] = audio
+        if use_dist:
+            outs["codes_gathered"] = gathered
+        dump_outputs(args.dump_outputs, outs)
 
-    # ---- second pass (untimed): the per-class table, HIP events around every launch on the launch stream (roofline.achieved)
-    model.profile_enable(True)
-    model.profile_reset()
-    for _ in range(args.steps):
-        step()
-    sync()
-    prof = model.profile_read()
-    model.profile_enable(False)
+    if args.full:
+        # ---- second pass (untimed): the per-class table, HIP events around every launch on the launch stream (roofline.achieved)
+        model.profile_enable(True)
+        model.profile_reset()
+        for _ in range(args.steps):
+            step()
+        sync()
+        prof = model.profile_read()
+        model.profile_enable(False)
 
-    # ---- encode-only / decode-only (Examples/Program.cs:252-291 calls them separately), same inputs, rank-local
-    def half(fn):
-        fn(); torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-        ev[0].record()
-        for i in range(args.steps):
-            fn()
-            ev[i + 1].record()
-        torch.cuda.synchronize()
-        ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
-        med = ms[len(ms) // 2] if len(ms) % 2 else 0.5 * (ms[len(ms) // 2 - 1] + ms[len(ms) // 2])
-        return {"ms_median": round(med, 3), "ms_mean": round(sum(ms) / len(ms), 3), "x_realtime_median": round(B * seconds / (med * 1e-3), 1)}
-    if snac_mode:
-        enc_only = half(lambda: model.encode(pcm))
-        dec_only = half(lambda: model.decode(codes, noise))
-    else:
-        enc_only = half(lambda: model.encode(pcm))
-        dec_only = half(lambda: model.decode(z))
+        # ---- encode-only / decode-only (Examples/Program.cs:252-291 calls them separately), same inputs, rank-local
+        def half(fn):
+            fn(); torch.cuda.synchronize()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+            ev[0].record()
+            for i in range(args.steps):
+                fn()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
+            med = ms[len(ms) // 2] if len(ms) % 2 else 0.5 * (ms[len(ms) // 2 - 1] + ms[len(ms) // 2])
+            return {"ms_median": round(med, 3), "ms_mean": round(sum(ms) / len(ms), 3), "x_realtime_median": round(B * seconds / (med * 1e-3), 1)}
+        if snac_mode:
+            enc_only = half(lambda: model.encode(pcm))
+            dec_only = half(lambda: model.decode(codes, noise))
+        else:
+            enc_only = half(lambda: model.encode(pcm))
+            dec_only = half(lambda: model.decode(z))
 
     audio_seconds = world * B * seconds * args.steps
     value = audio_seconds / dt
@@ -609,6 +649,27 @@ def main():
     med_ms = sms[len(sms) // 2] if len(sms) % 2 else 0.5 * (sms[len(sms) // 2 - 1] + sms[len(sms) // 2])   # this rank's per-step GPU times
 
     if rank == 0:
+        if snac_mode:
+            metric = "audio-seconds/sec encode+decode (x real-time), SNAC-44.1kHz B=8 x 5 s per GPU"
+            workload = "SNAC 44.1kHz + LocalMHA encode+decode, batch=%d x %.0f s clips per GPU (BASELINE configs[4] share)" % (B, seconds)
+            coll = "RCCL all_gather of int64 codes [B,%d] (4 levels side by side) per rank" % sum(widths)
+            if args.pack_bits:
+                coll += ", %d-bit packed payload" % args.pack_bits
+        else:
+            metric = "audio-seconds/sec encode+decode (x real-time), DAC-44.1kHz B=32"
+            workload = "DAC 44.1kHz 8kbps encode+decode, batch=%d x %.0f s clips per GPU (BASELINE configs[1])" % (B, seconds)
+            coll = "RCCL all_gather of int64 codes [B,9,87] per rank" + (", %d-bit packed payload" % args.pack_bits if args.pack_bits else "")
+        out = {
+            "metric": metric,
+            "value": round(value, 2), "unit": "audio-seconds/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "ms_per_step_median": round(med_ms, 3), "value_at_median_step": round(world * B * seconds / (med_ms * 1e-3), 2),
+            "ms_per_step_min_max": [round(min(step_ms), 3), round(max(step_ms), 3)],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload, "clips_per_gpu": B, "clip_seconds": seconds, "global_batch": world * B,
+                       "collective": coll if use_dist else "none"},
+        }
+    if rank == 0 and args.full:
         classes = class_table(prof, args.steps, load_traffic("snac44k" if snac_mode else "dac44k") if (B == (8 if snac_mode else 32)) else None)
         total_kernel_ms = sum(v["ms"] for v in prof.values())
         total_flops = sum(v["flops"] for v in prof.values())
@@ -695,28 +756,7 @@ def main():
                     cpu["aten_proxy"] = aten_proxy(cfg, sd, pcm_h[:max(1, min(args.proxy_clips, B))], seconds, args.proxy_iters)
                 except Exception as e:   # the proxy is informational: never lose the bench line to it
                     cpu["aten_proxy"] = {"error": repr(e)}
-        if snac_mode:
-            metric = "audio-seconds/sec encode+decode (x real-time), SNAC-44.1kHz B=8 x 5 s per GPU"
-            workload = "SNAC 44.1kHz + LocalMHA encode+decode, batch=%d x %.0f s clips per GPU (BASELINE configs[4] share)" % (B, seconds)
-            coll = "RCCL all_gather of int64 codes [B,%d] (4 levels side by side) per rank" % sum(widths)
-            if args.pack_bits:
-                coll += ", %d-bit packed payload" % args.pack_bits
-        else:
-            metric = "audio-seconds/sec encode+decode (x real-time), DAC-44.1kHz B=32"
-            workload = "DAC 44.1kHz 8kbps encode+decode, batch=%d x %.0f s clips per GPU (BASELINE configs[1])" % (B, seconds)
-            coll = "RCCL all_gather of int64 codes [B,9,87] per rank" + (", %d-bit packed payload" % args.pack_bits if args.pack_bits else "")
-        out = {
-            "metric": metric,
-            "value": round(value, 2), "unit": "audio-seconds/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "ms_per_step_median": round(med_ms, 3), "value_at_median_step": round(world * B * seconds / (med_ms * 1e-3), 2),
-            "ms_per_step_min_max": [round(min(step_ms), 3), round(max(step_ms), 3)],
-            "encode_only": enc_only, "decode_only": dec_only,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "clips_per_gpu": B, "clip_seconds": seconds, "global_batch": world * B,
-                       "collective": coll if use_dist else "none"},
-            "roofline": roofline, "cpu_baseline": cpu, "extra_configs": extras,
-        }
+        out.update({"encode_only": enc_only, "decode_only": dec_only, "roofline": roofline, "cpu_baseline": cpu, "extra_configs": extras})
         # The ONE line must be readable in a log tail: the full per-class tables go to a detail file, the line keeps a
         # compact form of them; the other BASELINE configs' step times are flat top-level keys as well.
         detail = json.loads(json.dumps(out))
@@ -747,7 +787,7 @@ def main():
         except OSError:
             pass
     gathered_ok = None
-    if use_dist and not args.no_check:
+    if use_dist and args.full and not args.no_check:
         # the gathered codes of the N-GPU run must equal the 1-GPU run on the same inputs -- EVERY slot, on every rank:
         # each rank re-encodes every shard's clips (same seeds) on its own GPU, outside the timed region, and compares slot by slot
         ok = True

@@ -164,7 +164,7 @@ def test_bench_distributed_path_one_rank(config, steps):
         port = s.getsockname()[1]
     e = dict(os.environ, NC_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
              HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-extra",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra",
            "--config", config] + (["--pack-bits", "12"] if config == "snac44k" else [])   # (the SNAC run also moves its codes bit-packed)
     r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -196,7 +196,7 @@ def _one_json_line(r):
 
 
 def test_bench_self_launch_one_rank():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
     r = subprocess.run(cmd, env=_clean_env(NC_BENCH_SELF_LAUNCH="1"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     out = _one_json_line(r)
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["value"] > 0
@@ -216,7 +216,7 @@ def test_bench_self_launch_reports_a_failing_rank():
 def test_bench_local_group_one_device(config, extra):
     """--local-group: ONE process drives the devices through nc_group_create_local + the device-resident grouped all-gather
     (nc_group_*_encode_allgather_local_dev), the layout of a single C# host (Examples/Program.cs:228-322); one device here."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--local-group", "--steps", "2", "--warmup", "1", "--config", config] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--local-group", "--steps", "2", "--warmup", "1", "--full", "--config", config] + extra
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     import json
@@ -226,8 +226,53 @@ def test_bench_local_group_one_device(config, extra):
 
 @pytest.mark.skipif(_n_gpus() < 2, reason="needs two GPUs")
 def test_bench_self_launch_and_local_group_two_gpus():
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
     out = _one_json_line(subprocess.run(base, env=_clean_env(), capture_output=True, text=True, timeout=1200, cwd=ROOT))
     assert out["n_gpus"] == 2 and out["config"]["gathered_equals_1gpu_every_slot_every_rank"] is True
     r = subprocess.run(base + ["--local-group"], env=_clean_env(), capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: exactly K timed steps, the headline keys only (everything else is
+    `--full`), and the last timed step's codes / zQ / latents / PCM as float .npy files that equal the oracle's codes on a clip."""
+    import json
+    import numpy as np
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    out = _one_json_line(subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT))
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "audio-seconds/sec" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 32 * 1.0 / (out["ms_per_step"] * 1e-3)) <= 0.01 * out["value"]
+    for moved in ("roofline", "cpu_baseline", "extra_configs", "encode_only", "decode_only"):
+        assert moved not in out
+    arrays = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert set(arrays) == {"codes", "z", "latents", "audio"}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert arrays["codes"].shape == (32, 9, 87) and arrays["z"].shape == (32, 1024, 87) and arrays["audio"].shape[:2] == (32, 1)
+    assert np.all(np.isfinite(arrays["audio"])) and np.all(np.isfinite(arrays["z"]))
+    codes = arrays["codes"]
+    assert np.array_equal(codes, np.round(codes)) and codes.min() >= 0 and codes.max() < 1024
+    # clip 0 against the C oracle on the bench's own seeded weights and PCM (host only: this process never touches the GPU)
+    from neuralcodecs_amd import DACConfig
+    from neuralcodecs_amd.weights import dac_synthetic_state_dict, save_blob, synthetic_pcm
+    from oracle import c_oracle
+    cfg = DACConfig.dac_44khz()
+    ref = c_oracle.RefDAC(cfg, save_blob(dac_synthetic_state_dict(cfg, seed=42)))
+    rz, rcodes, _, _ = ref.encode(synthetic_pcm(32, 1, 44100, cfg.sample_rate, seed=1234)[:1])
+    assert np.array_equal(codes[:1], rcodes)
+    assert np.abs(arrays["audio"][:1] - ref.decode(rz)).max() <= 1e-4
+
+
+def test_bench_local_group_plain_run_prints_the_headline_only():
+    """A plain --local-group run leaves out what only --full measures or checks, as the plain one-process run does."""
+    import json
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--local-group", "--steps", "2", "--warmup", "1"]
+    r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])     # (RCCL's banner shares stdout in this layout)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    for moved in ("roofline", "cpu_baseline"):
+        assert moved not in out
+    assert "gathered_equals_1gpu_every_slot_every_device" not in out["config"]

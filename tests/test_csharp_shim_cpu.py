@@ -4,8 +4,9 @@ Engine side: NcMi355x.cs is GENERATED from include/nc_mi355x.h (one [DllImport] 
 count, struct layouts equal to the ctypes mirrors the parity tests drive the library with), and every NcMi355x.nc_* call of the
 hand-written model classes names a header export with that many arguments.
 
-Reference side (build container only: these tests SKIP where /root/reference is absent, e.g. on the GPU box): the model classes
-DACNative / SNACNative / EncodecNative and the Create*NativeAsync factories are compared with the reference's own sources --
+Reference side: the model classes DACNative / SNACNative / EncodecNative and the Create*NativeAsync factories are compared with the
+reference's own sources when NC_REFERENCE_SRC names a checkout of them (the repository does not carry them); every test also runs, with
+or without it, the checks that need only the binding's own files (constructor, interfaces, factory shapes, usings, the bandwidth rule) --
   * every `config.X` / `_config.X` they read is a public property of the reference's Config/{DAC,SNAC,Encodec}/*Config.cs with the
     type the code assumes, and nullable ones are only used in nullable-safe forms;
   * every public method and property of Models/{DAC,SNAC,Encodec}.cs (SURVEY 8b's preserved surface) exists with the same return
@@ -19,6 +20,7 @@ import glob
 import os
 import re
 import sys
+import warnings
 
 import pytest
 
@@ -29,10 +31,21 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import csharp_parse as P  # noqa: E402
 import gen_csharp_shim as gen  # noqa: E402
 
-REF = "/root/reference"
+REF = os.environ.get("NC_REFERENCE_SRC", "")      # root of a NeuralCodecs checkout: enables the comparisons with the reference's sources
 REF_T = os.path.join(REF, "NeuralCodecs.Torch")
 REF_C = os.path.join(REF, "NeuralCodecs.Core")
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF_T), reason="the reference's sources exist in the build container only")
+HAVE_REF = bool(REF)                                # (a wrong path then fails the comparisons instead of switching them off)
+
+
+@pytest.fixture(autouse=True)
+def _say_when_the_reference_side_is_not_compared(request):
+    """The repository carries no part of the reference's sources, so its half of these comparisons needs NC_REFERENCE_SRC.  A run
+    without it says so in pytest's warnings summary, test by test, rather than passing as if the comparison had been made."""
+    if not HAVE_REF and "reference" in request.node.name:
+        warnings.warn(f"{request.node.name}: only the binding-side checks ran; set NC_REFERENCE_SRC to a NeuralCodecs checkout to "
+                      "compare against the reference's sources", UserWarning)
+    yield
+
 
 MODELS = {  # native class -> (its file, reference class, reference file, reference config class, config file)
     "DACNative": ("DAC.Native.cs", "DAC", "Models/DAC.cs", "DACConfig", "Config/DAC/DACConfig.cs"),
@@ -141,18 +154,18 @@ CONFIG_TYPES = {
 NULLABLE_SAFE = re.compile(r"\s*(\?\?|\.HasValue|\.Value\b|\s+is\b|;|=(?!=)|\}|,\s*$)")   # what may follow a nullable property read
 
 
-@needs_reference
 @pytest.mark.parametrize("native", sorted(MODELS))
 def test_config_properties_exist_in_the_reference_with_the_assumed_types(native):
     fname, _, _, cfg_cls, cfg_file = MODELS[native]
-    ref_props = P.members(_read(os.path.join(REF_T, cfg_file)), cfg_cls)["props"]
+    ref_props = P.members(_read(os.path.join(REF_T, cfg_file)), cfg_cls)["props"] if HAVE_REF else None
     text = P.strip_comments(_native(fname))
     used = set(re.findall(r"\b_?config\.(\w+)", text))
     assert used, "the class never reads its config?"
     for prop in sorted(used):
-        assert prop in ref_props, f"{fname}: config.{prop} -- {cfg_cls} has no such public property ({cfg_file})"
         assert prop in CONFIG_TYPES[cfg_cls], f"{fname}: config.{prop} is read but its assumed type is not declared in CONFIG_TYPES"
-        assert ref_props[prop] == CONFIG_TYPES[cfg_cls][prop], f"{cfg_cls}.{prop} is {ref_props[prop]} in the reference, the binding assumes {CONFIG_TYPES[cfg_cls][prop]}"
+        if ref_props is not None:
+            assert prop in ref_props, f"{fname}: config.{prop} -- {cfg_cls} has no such public property ({cfg_file})"
+            assert ref_props[prop] == CONFIG_TYPES[cfg_cls][prop], f"{cfg_cls}.{prop} is {ref_props[prop]} in the reference, the binding assumes {CONFIG_TYPES[cfg_cls][prop]}"
     assert set(CONFIG_TYPES[cfg_cls]) == used, f"CONFIG_TYPES[{cfg_cls}] lists properties the class no longer reads: {set(CONFIG_TYPES[cfg_cls]) - used}"
     for prop, ty in CONFIG_TYPES[cfg_cls].items():
         if not ty.endswith("?"):
@@ -162,33 +175,33 @@ def test_config_properties_exist_in_the_reference_with_the_assumed_types(native)
             assert NULLABLE_SAFE.match(tail), f"{fname}: nullable {cfg_cls}.{prop} ({ty}) used as a plain value: ...{text[m.start():m.end() + 24]!r}"
 
 
-@needs_reference
 @pytest.mark.parametrize("native", sorted(MODELS))
 def test_every_public_member_of_the_reference_model_is_mirrored(native):
     fname, ref_cls, ref_file, cfg_cls, _ = MODELS[native]
-    ref = P.members(_read(os.path.join(REF_T, ref_file)), ref_cls)
     mine = P.members(_native(fname), native)
     have = {P.signature(r, n, p): body for r, n, p, body in mine["methods"]}
-    assert len(ref["methods"]) >= 6
-    for r, n, p, _ in ref["methods"]:
-        if n in NOT_MIRRORED[ref_cls]["methods"]:
-            continue
-        sig = P.signature(r, n, p)
-        assert sig in have, f"{native} lacks the reference member `{sig}` ({ref_file})"
-        assert have[sig], f"{native}.{n} has no body"
-    for name, ty in ref["props"].items():
-        if name in NOT_MIRRORED[ref_cls]["props"]:
-            continue
-        assert mine["props"].get(name) == ty, f"{native} lacks the reference property `{ty} {name}` ({ref_file})"
+    if HAVE_REF:
+        ref = P.members(_read(os.path.join(REF_T, ref_file)), ref_cls)
+        assert len(ref["methods"]) >= 6
+        for r, n, p, _ in ref["methods"]:
+            if n in NOT_MIRRORED[ref_cls]["methods"]:
+                continue
+            sig = P.signature(r, n, p)
+            assert sig in have, f"{native} lacks the reference member `{sig}` ({ref_file})"
+            assert have[sig], f"{native}.{n} has no body"
+        for name, ty in ref["props"].items():
+            if name in NOT_MIRRORED[ref_cls]["props"]:
+                continue
+            assert mine["props"].get(name) == ty, f"{native} lacks the reference property `{ty} {name}` ({ref_file})"
     assert [[(t, n) for t, n, _ in c] for c in mine["ctors"]] == [[(cfg_cls, "config")]], f"{native}: constructor must take ({cfg_cls} config) like {ref_file}"
     # INeuralCodec (Core/INeuralCodec.cs:8-20): Config, LoadWeights + IDisposable
-    iprops, imethods = P.interface_members(_read(os.path.join(REF_C, "INeuralCodec.cs")), "INeuralCodec")
-    assert iprops == {"Config": "IModelConfig"} and [P.signature(*m) for m in imethods] == ["void LoadWeights(string)"]
+    if HAVE_REF:
+        iprops, imethods = P.interface_members(_read(os.path.join(REF_C, "INeuralCodec.cs")), "INeuralCodec")
+        assert iprops == {"Config": "IModelConfig"} and [P.signature(*m) for m in imethods] == ["void LoadWeights(string)"]
     assert re.search(r"class " + native + r"\s*:\s*INeuralCodec\b", _native(fname))
     assert mine["props"].get("Config") == "IModelConfig" and "void LoadWeights(string)" in have and "void Dispose()" in have
 
 
-@needs_reference
 def test_surveyed_surface_is_present():
     """SURVEY 8b's list, spelled out (so that a change of NOT_MIRRORED cannot silently drop one of them)."""
     want = {
@@ -210,17 +223,21 @@ def test_surveyed_surface_is_present():
         assert props.get(name) == ty                                          # Models/Encodec.cs:145-201
 
 
-@needs_reference
 def test_factories_have_the_reference_parameter_lists():
-    ref = {n: (r, p) for r, n, p, _ in P.members(_read(os.path.join(REF_T, "NeuralCodecs.cs")), "NeuralCodecs")["methods"]}
     mine = {n: (r, p, b) for r, n, p, b in P.members(_native("NeuralCodecs.Native.cs"), "NeuralCodecs")["methods"]}
-    assert re.search(r"public static partial class NeuralCodecs\b", _read(os.path.join(REF_T, "NeuralCodecs.cs")))      # so that ours can join it
     assert re.search(r"public static partial class NeuralCodecs\b", _native("NeuralCodecs.Native.cs"))
     assert re.search(r"^namespace NeuralCodecs\.Torch;", _native("NeuralCodecs.Native.cs"), flags=re.M)
     for kind in ("SNAC", "DAC", "Encodec"):
+        nr, _, body = mine[f"Create{kind}NativeAsync"]
+        assert nr == f"Task<{kind}Native>" and body
+    if not HAVE_REF:
+        return
+    ref = {n: (r, p) for r, n, p, _ in P.members(_read(os.path.join(REF_T, "NeuralCodecs.cs")), "NeuralCodecs")["methods"]}
+    assert re.search(r"public static partial class NeuralCodecs\b", _read(os.path.join(REF_T, "NeuralCodecs.cs")))      # so that ours can join it
+    for kind in ("SNAC", "DAC", "Encodec"):
         r, p = ref[f"Create{kind}Async"]
-        nr, np_, body = mine[f"Create{kind}NativeAsync"]
-        assert r == f"Task<{kind}>" and nr == f"Task<{kind}Native>" and body
+        np_ = mine[f"Create{kind}NativeAsync"][1]
+        assert r == f"Task<{kind}>"
         assert p == np_, f"Create{kind}NativeAsync{np_} differs from the reference's Create{kind}Async{p}"          # types, names and defaults
 
 
@@ -232,22 +249,22 @@ def _reference_namespaces():
     return ns
 
 
-@needs_reference
 def test_usings_exceptions_and_records_resolve_against_the_reference():
-    namespaces = _reference_namespaces()
-    exc = {}
-    for path in glob.glob(os.path.join(REF_C, "Exceptions", "*.cs")):
-        cls = os.path.splitext(os.path.basename(path))[0]
-        exc[cls] = P.members(_read(path), cls)["ctors"]
-    assert {"LoadException", "CodecException", "NeuralCodecException"} <= set(exc)
-    frame = P.strip_comments(_read(os.path.join(REF_T, "Modules/Encodec/EncodedFrame.cs")))
-    fm = re.search(r"public record EncodedFrame\((.*?)\);", frame)
-    frame_params = P.parse_params(fm.group(1))
-    assert [(t, n) for t, n, _ in frame_params] == [("Tensor", "Codes"), ("Tensor?", "Scale")]
+    namespaces, exc = None, {}
+    if HAVE_REF:
+        namespaces = _reference_namespaces()
+        for path in glob.glob(os.path.join(REF_C, "Exceptions", "*.cs")):
+            cls = os.path.splitext(os.path.basename(path))[0]
+            exc[cls] = P.members(_read(path), cls)["ctors"]
+        assert {"LoadException", "CodecException", "NeuralCodecException"} <= set(exc)
+        frame = P.strip_comments(_read(os.path.join(REF_T, "Modules/Encodec/EncodedFrame.cs")))
+        fm = re.search(r"public record EncodedFrame\((.*?)\);", frame)
+        frame_params = P.parse_params(fm.group(1))
+        assert [(t, n) for t, n, _ in frame_params] == [("Tensor", "Codes"), ("Tensor?", "Scale")]
     for fname in list(gen.MODEL_FILES) + ["NcMi355x.cs"]:
         text = P.strip_comments(_native(fname))
         for m in re.finditer(r"^using (?:static )?(NeuralCodecs[\w.]*);", text, flags=re.M):
-            if m.group(1) == "NeuralCodecs.Torch.Native":
+            if m.group(1) == "NeuralCodecs.Torch.Native" or namespaces is None:
                 continue                                                   # ours: declared by NcMi355x.cs
             assert m.group(1) in namespaces, f"{fname}: `using {m.group(1)}` -- the reference declares no such namespace"
         for m in re.finditer(r"\bnew (?:[\w.]+\.)?(\w+Exception)\s*\(", text):
@@ -264,6 +281,8 @@ def test_usings_exceptions_and_records_resolve_against_the_reference():
         for m in re.finditer(r"\bframe\.(\w+)", text):
             assert m.group(1) in ("Codes", "Scale")
     assert "namespace NeuralCodecs.Torch.Native;" in _native("NcMi355x.cs")
+    if not HAVE_REF:
+        return
     # ModelLoadOptions.Device / DeviceConfiguration.{Type,Index} / DeviceType.CUDA as the binding uses them
     opts = P.members(_read(os.path.join(REF_C, "Loading/ModelLoadOptions.cs")), "ModelLoadOptions")["props"]
     dev = P.members(_read(os.path.join(REF_C, "Configuration/DeviceConfiguration.cs")), "DeviceConfiguration")["props"]
@@ -271,22 +290,22 @@ def test_usings_exceptions_and_records_resolve_against_the_reference():
     assert re.search(r"\bCUDA\b", _read(os.path.join(REF_C, "Configuration/DeviceType.cs")))
 
 
-@needs_reference
 def test_encodec_constructor_keeps_the_reference_bandwidth_rule():
     """Models/Encodec.cs:48-56,84: the bandwidth comes from config.Bandwidth, validated against TargetBandwidths with an
     ArgumentException; Overlap defaults to 0 (the generated class started from TargetBandwidths.Max())."""
     squash = lambda s: re.sub(r"\s+", "", s)
-    ref = squash(P.strip_comments(_read(os.path.join(REF_T, "Models/Encodec.cs"))))
+    ref = squash(P.strip_comments(_read(os.path.join(REF_T, "Models/Encodec.cs")))) if HAVE_REF else None
     mine_src = P.strip_comments(_native("Encodec.Native.cs"))
     ctor = mine_src[mine_src.index("public EncodecNative(EncodecConfig config)"):]
     ctor = squash(ctor[:P._balanced(ctor, ctor.index("{"), "{", "}")])
     rule = "if(config.Bandwidthisnull||!((IList<float>)config.TargetBandwidths).Contains(config.Bandwidth.Value)){thrownewArgumentException("
-    assert rule in ref and rule in ctor
-    assert "_bandwidth=config.Bandwidth;" in ref and "_bandwidth=config.Bandwidth;" in ctor
-    assert "_overlap=config.Overlap??0;" in ref and "_overlap=config.Overlap??0;" in ctor
+    assert rule in ctor and "_bandwidth=config.Bandwidth;" in ctor and "_overlap=config.Overlap??0;" in ctor
+    if ref is not None:
+        assert rule in ref and "_bandwidth=config.Bandwidth;" in ref and "_overlap=config.Overlap??0;" in ref
     assert "bandwidth=config.Bandwidth.Value" in ctor and "bandwidth=config.TargetBandwidths.Max()" not in ctor
     assert ctor.index("thrownewArgumentException(") < ctor.index("nc_encodec_create")                      # validated before anything is created
     # SetTargetBandwidth (Encodec.cs:409-419): membership check, then the switch; the config follows
     stb = squash(mine_src[mine_src.index("public void SetTargetBandwidth(float bandwidth)"):mine_src.index("EncodeHost(")])
     assert "if(!_targetBandwidths.Contains(bandwidth)){thrownewArgumentException(" in stb and "_config.Bandwidth=bandwidth;" in stb
-    assert "if(!_targetBandwidths.Contains(bandwidth)){thrownewArgumentException(" in ref and "_config.Bandwidth=bandwidth;" in ref
+    if ref is not None:
+        assert "if(!_targetBandwidths.Contains(bandwidth)){thrownewArgumentException(" in ref and "_config.Bandwidth=bandwidth;" in ref

@@ -7,7 +7,7 @@ for rep in 1 2 ${REPS}; do
 for f in build_abl/lib_*.so; do
   v=$(basename $f .so)
   cp $f neuralcodecs_amd/libnc_mi355x.so
-  echo "== $v"; timeout 300 python bench.py --no-cpu-baseline --no-extra 2>/dev/null | sumline
+  echo "== $v"; timeout 300 python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | sumline
   if [ -n "$ENC" ]; then timeout 300 python tools/codecbench.py --only encodec48 --steps 10 --warmup 3 2>/dev/null | tail -1; fi
 done
 done

@@ -6,7 +6,7 @@ REPS=${REPS:-2}
 for rep in $(seq 1 $REPS); do
 for f in build_abl/lib_*.so; do
   v=$(basename $f .so)
-  NC_MI355X_LIB=$PWD/$f python bench.py --no-cpu-baseline --no-extra --no-check --steps 10 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v dac', d['ms_per_step'], {k: round(v['ms_per_step'],2) for k, v in d['roofline']['all_classes'].items() if k in ('conv_k7','conv_k1','conv_up','conv_down')})"
+  NC_MI355X_LIB=$PWD/$f python bench.py --full --no-cpu-baseline --no-extra --no-check --steps 10 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v dac', d['ms_per_step'], {k: round(v['ms_per_step'],2) for k, v in d['roofline']['all_classes'].items() if k in ('conv_k7','conv_k1','conv_up','conv_down')})"
   NC_MI355X_LIB=$PWD/$f python tools/codecbench.py --classes --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06_final; mkdir -p $O
 true
-timeout 900 python bench.py > $O/r06_bench_full.json 2> $O/r06_bench_full.err; echo bench rc=$?
+timeout 900 python bench.py --full > $O/r06_bench_full.json 2> $O/r06_bench_full.err; echo bench rc=$?
 cp gpurun_out/bench_detail.json $O/r06_bench_detail.json
 python -c "
 import json

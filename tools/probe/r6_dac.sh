@@ -9,6 +9,6 @@ d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
 print(sys.argv[2], d['ms_per_step'], d['roofline']['frac'], {k:v[0] for k,v in d['roofline']['all_classes'].items()}, {k:v for k,v in d.items() if k.startswith('c')and k.endswith('ms_per_step')}, len(json.dumps(d)))
 " $1 $2; }
 for rep in 1 2; do
-python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench_pitch_$rep.json 2>$OUT/bench_pitch.err; show $OUT/bench_pitch_$rep.json pitch
-NC_DAC_NO_PITCH=1 python bench.py --no-cpu-baseline --no-extra --steps 20 --warmup 5 > $OUT/bench_nopitch_$rep.json 2>$OUT/bench_nopitch.err; show $OUT/bench_nopitch_$rep.json nopitch
+python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench_pitch_$rep.json 2>$OUT/bench_pitch.err; show $OUT/bench_pitch_$rep.json pitch
+NC_DAC_NO_PITCH=1 python bench.py --full --no-cpu-baseline --no-extra --steps 20 --warmup 5 > $OUT/bench_nopitch_$rep.json 2>$OUT/bench_nopitch.err; show $OUT/bench_nopitch_$rep.json nopitch
 done

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 TAG=${1:-r6d}; OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 timeout 1200 python -m pytest tests/test_dac_gpu.py tests/test_ops_gpu.py tests/test_encodec_gpu.py tests/test_baseline_sizes_gpu.py::test_c2_dac44k_batch32_vs_oracle_and_batch_invariance tests/test_nonfinite_gpu.py tests/test_containers_gpu.py -m gpu -q -x > $OUT/pytest.log 2>&1; tail -3 $OUT/pytest.log
-python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>$OUT/bench.err | python -c "
+python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>$OUT/bench.err | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print(d['ms_per_step'], d['roofline']['frac'], {k:v for k,v in d.items() if k.startswith('c') and k.endswith('ms_per_step')})"
