@@ -54,11 +54,7 @@ void d2h(void* h, const void* d, size_t n, hipStream_t s) { NC_HIP(hipMemcpyAsyn
 extern "C" {
 
 const char* nc_last_error(void) { return get_last_error(); }
-#ifdef NC_EXPERIMENTS
-const char* nc_version(void) { return "nc_mi355x 0.1 (gfx950) +experiments"; }   // make EXPERIMENTS=1: measured-and-rejected kernels and their switches
-#else
 const char* nc_version(void) { return "nc_mi355x 0.1 (gfx950)"; }
-#endif
 
 const char* nc_debug_switches(void) { return env_switch_table(); }
 

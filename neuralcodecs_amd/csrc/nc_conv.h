@@ -106,7 +106,7 @@ __host__ __device__ constexpr int a_tile_pos(int TM, int i, int r) {
 
 struct TileCfg {
     int TM, TN, K, CB;
-    int NW = 4;                       // waves per workgroup (8: wide variants)
+    int NW = 4;                       // waves per workgroup (3: narrow variants)
     int BM() const { return 32 * TM; }
     int BN() const { return 32 * NW * TN; }
     int KB() const { return CB * K; }

@@ -40,28 +40,8 @@ int conv_kernel_nx_k16();
 #define NC_K_CASES(X) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(10) X(16)
 
 conv_kernel_fn conv_kernel_table_fused_k7(int, int);
-// Measured-and-rejected k=7 variants (light / wide / wave-specialised / distributed staging): built only with
-// `make EXPERIMENTS=1` (-DNC_EXPERIMENTS); the default library carries neither their code objects nor their switches.
-#ifdef NC_EXPERIMENTS
-conv_kernel_fn conv_kernel_table_light_k7(int, int);
-conv_kernel_fn conv_kernel_table_wide_k7(int, int);
-conv_kernel_fn conv_kernel_table_spec_k7(int, int);
-conv_kernel_fn conv_kernel_table_dist_k7(int, int);
-static int experiment_mode(const char* name) { return (int)env_int(name, 0); }
-#else
-static conv_kernel_fn conv_kernel_table_light_k7(int, int) { return nullptr; }
-static conv_kernel_fn conv_kernel_table_wide_k7(int, int) { return nullptr; }
-static conv_kernel_fn conv_kernel_table_spec_k7(int, int) { return nullptr; }
-static conv_kernel_fn conv_kernel_table_dist_k7(int, int) { return nullptr; }
-static int experiment_mode(const char*) { return 0; }
-#endif
 conv_kernel_fn conv_kernel_table_xv_k7(int);
 conv_kernel_fn conv_kernel_table_xv_fused_k7(int);
-#ifdef NC_EXPERIMENTS
-conv_kernel_fn conv_kernel_table_duo_k7(int);   // (the DUO form of the XV-only k = 7 instances, NC_DUO=1: bit-exact, 6 % slower on the k = 7 class)
-#else
-static conv_kernel_fn conv_kernel_table_duo_k7(int) { return nullptr; }
-#endif
 conv_kernel_fn conv_kernel_table_xv_sub_k2(int);
 conv_kernel_fn conv_kernel_table_xv_subg_k2(int);
 conv_kernel_fn conv_kernel_table_sub_k2(int, int);
@@ -104,11 +84,6 @@ static conv_kernel_fn in2_kernel(int Ktaps, bool sub, int TM, int TN) {
     return nullptr;
 }
 conv_kernel_fn conv1x1_kernel_table(int, int);
-#ifdef NC_EXPERIMENTS
-conv_kernel_fn conv1x1_stream_kernel_table(int, int);   // (round 2's streaming pointwise variant: overtaken in round 4, EXPERIMENTS=1 builds only)
-#else
-static conv_kernel_fn conv1x1_stream_kernel_table(int, int) { return nullptr; }
-#endif
 bool launch_conv_thin(const float* x, int64_t x_bstride, int64_t x_cstride, int Cin, int x_len, const float* w_dense, const float* bias, float* y,
                       int64_t y_bstride, int64_t y_cstride, int B, int Cout, int K, int pad, int dil, int64_t Tout, bool tanh_out, hipStream_t s);
 bool launch_conv_stem(const float* x, int64_t x_bstride, int x_len, const float* w_dense, const float* bias, const float* alpha_out, float* y,
@@ -481,35 +456,12 @@ static bool launch_conv1x1(const ConvLayer& L, const ConvIO& io, int B, hipStrea
     a.n_t_tiles = (int32_t)((T + 255) / 256);
     a.n_cb = (L.Cin + 15) / 16;
     a.co_group = pick_co_group(a.n_co_tiles, 4.0 * B * L.Cin * (double)T, 4.0 * L.Cin * (double)L.Cout, (double)B * a.n_t_tiles);
-    int64_t grid = (int64_t)a.n_co_tiles * B * a.n_t_tiles;
-    size_t lds = 0;
-    {   // streaming variant: narrow long rows, whole weight tile of a row tile resident in LDS (see conv1x1_stream_kernel)
-        // (not the default since round 4: with the in-place B ring and buffer-load addressing the tile-per-workgroup kernel is 1-6 % faster on
-        // these layers in steady state, DAC conv_k1 class 3.92 -> 3.79 ms; round 5: the streaming variant is compiled by `make EXPERIMENTS=1`
-        // only, where NC_PW_STREAM=1 selects it -- tools/probe/envmatrix.sh builds that library and runs the parity suites under it)
-#ifdef NC_EXPERIMENTS
-        static const bool no_stream = !env_flag("NC_PW_STREAM");
-#else
-        constexpr bool no_stream = true;
-#endif
-        const size_t need = sizeof(float) * ((size_t)L.Cin * BM + 3 * (size_t)BM);
-        conv_kernel_fn sfn = (!no_stream && !in_mode && mode <= 4 && L.Cin % 32 == 0 && L.Cin <= 192 && L.Cout % BM == 0 && need <= 76 * 1024 &&
-                              grid >= 2048)
-                                 ? conv1x1_stream_kernel_table(tc.cfg.TM, mode)
-                                 : nullptr;
-        if (sfn) {
-            fn = sfn;
-            lds = need;
-            ensure_dynamic_lds((const void*)fn, 80 * 1024);
-            const int64_t per = std::max<int64_t>(1, 512 / a.n_co_tiles);            // two workgroups per CU, a whole number per row tile
-            grid = (int64_t)a.n_co_tiles * std::min<int64_t>(per, (int64_t)B * a.n_t_tiles);
-        }
-    }
+    const int64_t grid = (int64_t)a.n_co_tiles * B * a.n_t_tiles;
     if (prof && prof->on) {
         const double bytes = 4.0 * ((double)B * L.Cin * T + (double)B * L.Cout * T * (io.res ? 2 : 1) + (double)L.Cin * L.Cout);
         prof->begin(stream, L.kclass, L.flops(B, T), bytes);
     }
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), 0, stream, a);
     NC_HIP(hipGetLastError());
     if (prof && prof->on) prof->end(stream);
     return true;
@@ -740,17 +692,7 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
             }
         }
     }
-    // light variant (reduction block of 4 channels, 3 workgroups per CU): same packed weights when Cin is a multiple of 8
     int nx = nx_for_k(c.K);
-    bool light = false;
-    {
-        static const int light_mode = experiment_mode("NC_LIGHT");
-        if (light_mode == 1 && !narrow && !flat && !io.fuse_k1 && c.K == 7 && c.CB == 8 && L.Cin % 8 == 0 && c.TN == 2 && (c.TM == 2 || c.TM == 3)) {
-            light = true;
-            c.CB = 4;
-            nx = 5;
-        }
-    }
     const bool fused_wide = io.fuse_k1 && c.TM > 4;   // C = 192 / 256 residual unit: whole-channel tile, 128 columns, 4-channel blocks
     if (fused_wide) { c.TN = 1; c.CB = 4; nx = 5; }
     bool slim = false;
@@ -761,35 +703,12 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         // 215 -> 145 us (32->16 k3, 48000 steps x 32 clips), 152 -> 118 us (64->32), 80 -> 51 us (2->32 k7).  Measured neutral or
         // slower for the strided k=4 / k=8 layers and the sub-pixel up-convolutions, which keep the standard blocks.
         static const bool no_slim = env_flag("NC_NO_SLIM");
-        if (!no_slim && !flat && !light && !narrow && !io.fuse_k1 && !io.x2 && !L.sub_stride && !L.transposed && c.TM <= 2 && n_cols_all >= 1024) {
+        if (!no_slim && !flat && !narrow && !io.fuse_k1 && !io.x2 && !L.sub_stride && !L.transposed && c.TM <= 2 && n_cols_all >= 1024) {
             int cb2 = 0, nx2 = 0;
             if (c.K == 3 && c.CB == 16) { slim_fn = conv_kernel_table_slim_k3(c.TM, c.TN); cb2 = 8; nx2 = 10; }
             else if (c.K == 7 && c.CB == 8 && L.Cin <= 4 && L.stride == 1 && L.dil == 1) { slim_fn = conv_kernel_table_slim_k7(c.TM, c.TN); cb2 = 4; nx2 = 5; }
             if (slim_fn) { slim = true; c.CB = cb2; nx = nx2; }
         }
-    }
-    bool wide = false;
-    {
-        static const int wide_mode = experiment_mode("NC_WIDE");
-        if (wide_mode == 1 && !light && !narrow && !flat && !io.fuse_k1 && c.K == 7 && c.TN == 2 && c.TM >= 2 && n_cols_all >= 2048) {
-            wide = true;
-            c.NW = 8;
-            nx = 9;
-        }
-    }
-    // wave-specialised variant (4 consumer + 2 producer waves): k=7, 64/96-row tiles, long rows
-    int n_prod = 0;
-    {
-        static const int spec_mode = experiment_mode("NC_SPEC");
-        if (spec_mode == 1 && !light && !narrow && !flat && !wide && !io.fuse_k1 && c.K == 7 && c.TN == 2 && (c.TM == 2 || c.TM == 3)) {
-            n_prod = 2;
-            nx = 20;
-        }
-    }
-    bool dist = false;
-    {
-        static const int dist_mode = experiment_mode("NC_DIST");
-        if (dist_mode == 1 && !n_prod && !light && !narrow && !flat && !wide && !io.fuse_k1 && c.K == 7 && c.TN == 2 && c.TM >= 2) dist = true;
     }
     // Distributed staging for the grids that leave a workgroup alone on its CU (the deep strided / sub-pixel layers of Encodec at
     // 150 frames: 20 GFLOP per launch): nobody feeds the matrix pipe during the staging runs of the segmented pipeline -- measured
@@ -800,13 +719,13 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         static const int64_t max_grid = env_int("NC_DIST_MAX_GRID", 768);
         const int64_t n_co = (L.rows() + c.BM() - 1) / c.BM();
         const int64_t n_tt = flat ? ((int64_t)B * flat_pitch + c.BN() - 1) / c.BN() : (int64_t)B * ((n_cols_all + c.BN() - 1) / c.BN());
-        if (!off && !dist && !n_prod && !light && !narrow && !wide && !slim && !in_mode && !io.x2 && !io.fuse_k1 && io.epi == 0 && L.n_phase == 1 &&
+        if (!off && !narrow && !slim && !in_mode && !io.x2 && !io.fuse_k1 && io.epi == 0 && L.n_phase == 1 &&
             n_co * n_tt <= max_grid) {
             if (L.sub_shift && c.K == 2) dist_small_fn = conv_kernel_table_dist_sub_k2(c.TM, c.TN);
             else if (!L.sub_stride && !L.transposed && c.K == 16) dist_small_fn = conv_kernel_table_dist_k16(c.TM, c.TN);
         }
     }
-    const int NW = n_prod ? n_prod : c.NW;   // waves that stage the input window
+    const int NW = c.NW;
     const int BM = c.BM(), BN = c.BN(), CB = c.CB, KB = c.KB();
     ConvArgs a{};
     a.x = io.x; a.x_bstride = io.x_bstride; a.x_cstride = io.x_cstride; a.Cin = L.Cin; a.x_len = io.x_len;
@@ -847,7 +766,6 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
     const int ad = a.dil < 0 ? -a.dil : a.dil;
     a.xneg = a.dil < 0 ? (L.Ktaps - 1) * ad : 0;
     int xv_extra = 0;
-    bool duo_launch = false;          // ... in its two-tiles-per-workgroup form (nc_conv_kernel.hip.h "DUO")
     conv_kernel_fn xv_fn = nullptr;   // XV-only instance of this launch (nc_conv_kernel.hip.h "XVK"), when its staging form applies
     {   // XV (round 5): vectorised window staging of the two-tap sub-pixel instances (the kernel's XV note) -- plain input, rows and window
         // start on 16-byte boundaries (xneg is raised by up to 3 slots for that: the window still fits its 320-slot pitch), whole float4s
@@ -861,23 +779,15 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         static const int64_t xv_k7_min = env_int("NC_XV_K7_MIN_COLS", 0);
         const bool xv_k7 = !no_xv_k7 && n_cols_all >= xv_k7_min;
         const bool two_tap = L.sub_stride && L.n_phase == 1 && c.K == 2 && c.CB == 16 && !io.alpha_in && !io.fuse_k1;
-#ifdef NC_EXPERIMENTS
-        static const bool duo_env = env_flag("NC_DUO");
-#else
-        constexpr bool duo_env = false;
-#endif
-        const bool duo7 = duo_env && !io.fuse_k1 && (c.TM == 2 || c.TM == 3);
-        const bool k7 = (xv_k7 || duo7) && !L.transposed && !L.sub_stride && c.K == 7 && c.CB == 8 && L.stride == 1 && !fused_wide;   // (the fused units included)
+        const bool k7 = xv_k7 && !L.transposed && !L.sub_stride && c.K == 7 && c.CB == 8 && L.stride == 1 && !fused_wide;   // (the fused units included)
         const int vw = two_tap ? 4 : 2;   // floats per staged word
-        if (!no_xv && !no_xr && (two_tap || k7) && c.TN == 2 && c.NW == 4 && c.TM >= 2 && c.TM <= 4 && !narrow && !flat && !dist_small_fn && !n_prod &&
-            !light && !wide && !dist && !slim && !in_mode && !io.x2 && !io.gn_part && sx == 1 && L.Cin % c.CB == 0 && io.x_len % vw == 0 &&
+        if (!no_xv && !no_xr && (two_tap || k7) && c.TN == 2 && c.NW == 4 && c.TM >= 2 && c.TM <= 4 && !narrow && !flat && !dist_small_fn &&
+            !slim && !in_mode && !io.x2 && !io.gn_part && sx == 1 && L.Cin % c.CB == 0 && io.x_len % vw == 0 &&
             io.x_cstride % 16 == 0 && io.x_bstride % 16 == 0 && (reinterpret_cast<uintptr_t>(io.x) & 63) == 0) {   // (rows on 64-byte boundaries: see above)
             xv_extra = (vw - (a.pad + a.xneg) % vw) % vw;
             if ((BN - 1) * sx + (L.Ktaps - 1) * ad + 1 + xv_extra <= 320) {
                 xv_fn = two_tap ? (L.sub_shift ? conv_kernel_table_xv_sub_k2(c.TM) : conv_kernel_table_xv_subg_k2(c.TM))
-                                : duo7 ? conv_kernel_table_duo_k7(c.TM)
-                                       : (io.fuse_k1 ? conv_kernel_table_xv_fused_k7(c.TM) : conv_kernel_table_xv_k7(c.TM));
-                duo_launch = xv_fn && !two_tap && duo7;
+                                : (io.fuse_k1 ? conv_kernel_table_xv_fused_k7(c.TM) : conv_kernel_table_xv_k7(c.TM));
             }
             if (xv_fn) { a.xneg += xv_extra; a.epi |= EPI_XVEC; }
             else xv_extra = 0;
@@ -930,12 +840,6 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         fn = xv_fn;
     } else if (dist_small_fn) {
         fn = dist_small_fn;
-    } else if (dist) {
-        fn = conv_kernel_table_dist_k7(c.TM, c.TN);
-        if (!fn) fail(NC_EUNSUPPORTED, "no distributed-staging conv kernel for TM=%d TN=%d", c.TM, c.TN);
-    } else if (n_prod) {
-        fn = conv_kernel_table_spec_k7(c.TM, c.TN);
-        if (!fn) fail(NC_EUNSUPPORTED, "no specialised conv kernel for TM=%d TN=%d", c.TM, c.TN);
     } else if (io.x2) {
         fn = in2_kernel(c.K, L.sub_shift != 0, c.TM, c.TN);
         if (!fn) fail(NC_EUNSUPPORTED, "no two-input conv kernel for K=%d TM=%d TN=%d", c.K, c.TM, c.TN);
@@ -947,20 +851,10 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         if (!fn) fail(NC_EUNSUPPORTED, "no sub-pixel conv kernel for K=%d TM=%d TN=%d", c.K, c.TM, c.TN);
     } else if (narrow) {
         fn = narrow_kernel(c.K, c.TM);
-    } else if (wide) {
-        fn = conv_kernel_table_wide_k7(c.TM, c.TN);
-        if (!fn) fail(NC_EUNSUPPORTED, "no wide conv kernel for TM=%d TN=%d", c.TM, c.TN);
     } else if (slim) {
         fn = slim_fn;
-    } else if (light) {
-        fn = conv_kernel_table_light_k7(c.TM, c.TN);
-        if (!fn) fail(NC_EUNSUPPORTED, "no light conv kernel for TM=%d TN=%d", c.TM, c.TN);
     } else {
         fn = lookup_kernel(c);
-    }
-    {   // experiment: NC_LDS_MIN=<bytes> raises the LDS request (fewer co-resident workgroups per CU)
-        static const size_t lds_min = (size_t)env_int("NC_LDS_MIN", 0);
-        lds = std::max(lds, std::min<size_t>(lds_min, 160 * 1024));
     }
     if (lds > 160 * 1024) fail(NC_EUNSUPPORTED, "conv tile needs %zu B of LDS", lds);
     ensure_dynamic_lds((const void*)fn, 160 * 1024);
@@ -991,12 +885,7 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         }
     }
 #endif
-    if (duo_launch) {   // two tiles per workgroup: 8 wavefronts, each sub-workgroup its own LDS half
-        const size_t lds_sub = sizeof(float) * (((size_t)a.ep_off + 6 * (size_t)BM + 3) & ~(size_t)3);
-        if (2 * lds_sub > 160 * 1024) fail(NC_EUNSUPPORTED, "DUO conv tile needs %zu B of LDS", 2 * lds_sub);
-        hipLaunchKernelGGL(fn, dim3((unsigned)((grid + 1) / 2)), dim3(512), 2 * lds_sub, stream, a);
-    } else
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64 * (c.NW + n_prod)), lds, stream, a);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64 * c.NW), lds, stream, a);
     NC_HIP(hipGetLastError());
     if (prof && prof->on) prof->end(stream);
 #ifdef NC_CONV_TRACE
@@ -1005,7 +894,7 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         NC_HIP(hipStreamSynchronize(stream));
         NC_HIP(hipMemcpy(hb.data(), trace_buf.p, hb.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(trace_file, "wb")) {
-            const int hdr[8] = {16, c.NW + n_prod, 8, 8, c.TM, c.TN, c.K, (a.epi & EPI_XVEC) ? 1 : 0};
+            const int hdr[8] = {16, c.NW, 8, 8, c.TM, c.TN, c.K, (a.epi & EPI_XVEC) ? 1 : 0};
             std::fwrite(hdr, sizeof(int), 8, f);
             std::fwrite(hb.data(), 8, hb.size(), f);
             std::fclose(f);
@@ -1018,7 +907,7 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
         // kernel name (dispatch order) to attribute HBM traffic / matrix-core busy cycles to exactly the launches a class counts.
         static FILE* lf = [] { const char* p = env_str("NC_LAUNCH_LOG"); return p ? std::fopen(p, "w") : (FILE*)nullptr; }();
         if (lf) {
-            std::fprintf(lf, "conv_mfma %d %lld %d %d %d %lld %d\n", L.kclass, (long long)grid * 64 * (c.NW + n_prod), L.Cin, L.Cout, L.K,
+            std::fprintf(lf, "conv_mfma %d %lld %d %d %d %lld %d\n", L.kclass, (long long)grid * 64 * c.NW, L.Cin, L.Cout, L.K,
                          (long long)io.Tin, io.fuse_k1 ? 1 : 0);
             std::fflush(lf);
         }

@@ -18,31 +18,6 @@
 #define NC_TRACE_CB0 8
 #define NC_TRACE_NCB 8
 #endif
-// ---- compile-time knobs of the template.  The SHIPPED build fixes every one of them to its shipped value: the A/B experiments of DESIGN 8
-// (rounds 4-5; results under profiles/r05_ab_*.txt) can only be compiled with -DNC_EXPERIMENTS (`make EXPERIMENTS=1` + tools/probe/mk_abl.sh),
-// and a -D override without it is an error -- one of them, NC_XV_SNAKE_ON=0, is a timing probe that computes WRONG results on purpose.
-#if !defined(NC_EXPERIMENTS) && (defined(NC_STAGE_PRIO) || defined(NC_LEGACY_ROWS) || defined(NC_XV_SNAKE_ILV) || defined(NC_XV_SNAKE_ON) || \
-                                 defined(NC_XV_FD) || defined(NC_XV_STORE_SEG))
-#error "NC_STAGE_PRIO / NC_LEGACY_ROWS / NC_XV_SNAKE_ILV / NC_XV_SNAKE_ON / NC_XV_FD / NC_XV_STORE_SEG are experiment knobs: build with -DNC_EXPERIMENTS"
-#endif
-#ifndef NC_STAGE_PRIO
-#define NC_STAGE_PRIO 0     // s_setprio of the staging runs of the segmented pipeline (0 = leave the priority alone; measured: no gain)
-#endif
-#ifndef NC_LEGACY_ROWS      // staging Snake of the legacy instances: 2 = sign-free chains side by side (shipped), 1 = side by side with the parity select, 0 = pair by pair
-#define NC_LEGACY_ROWS 2
-#endif
-#ifndef NC_XV_SNAKE_ILV     // 1 = the Snake chains of a staging run step by step side by side (shipped); 0: word by word, the round-5 first form
-#define NC_XV_SNAKE_ILV 1
-#endif
-#ifndef NC_XV_SNAKE_ON      // 1 (shipped); 0 = timing probe only (WRONG results): what the staging Snake costs in total
-#define NC_XV_SNAKE_ON 1
-#endif
-#ifndef NC_XV_FD
-#define NC_XV_FD 1          // XV-only instances: fragment prefetch depth (2 measured: no gain)
-#endif
-#ifndef NC_XV_STORE_SEG
-#define NC_XV_STORE_SEG 3   // XV staging: the block's one staging run sits at the head of this matrix-core segment (0 .. 3; 4 = behind the last):
-#endif                      // segment 3 measured best (profiles/r05_ab_xv_store_segment.txt)
 
 namespace nc {
 
@@ -66,7 +41,7 @@ struct nc_rt_flag {
 typedef __attribute__((address_space(1))) const void* nc_gptr;
 typedef __attribute__((address_space(3))) void* nc_lptr;
 
-// Block = NW waves (4, or 8 for the wide variants).  Wave w owns all BM = 32*TM output channels of the tile and the
+// Block = NW waves (4, or 3 for the narrow variants).  Wave w owns all BM = 32*TM output channels of the tile and the
 // 32*TN columns [w*32*TN, (w+1)*32*TN).  The reduction runs over blocks of CB input channels
 // (KB = CB*K flattened kk = ci*K + k, ascending: the canonical chain order).  Per block the
 // workgroup holds in LDS, double-buffered,
@@ -79,10 +54,6 @@ typedef __attribute__((address_space(3))) void* nc_lptr;
 // segment g+1 -- so a load has a whole segment of MFMA time to land, only 1/(NSEG-1) of the staging
 // registers are live at once, and the VALU work sits between matrix-core segments.
 //   MFMA step kp: lane l supplies A[row = l&31][kk = 2*kp + (l>>5)] and B[kk][col = l&31].
-// NP > 0: wave-specialised variant.  NW consumer waves do nothing but fragment reads and matrix-core steps; NP producer waves
-// stage the next reduction block (global reads, Snake, LDS writes).  In the classic variant every wave alternates between the two
-// roles, and its vector-ALU staging run issues slowly while the co-resident wave saturates the matrix pipe -- time during which
-// its own matrix-core steps cannot issue.  With the roles split, the consumers always have matrix-core work ready.
 // DIST: distributed staging.  A wave issues in order, and a matrix-core instruction holds its wave until the pipe accepts it; the
 // few instructions that sit BETWEEN two matrix-core instructions issue in the shadow of the first (64 cycles), but a cluster of
 // staging instructions between two matrix-core streaks keeps the wave away from the pipe for its whole length.  So the reads of the
@@ -105,20 +76,10 @@ typedef __attribute__((address_space(3))) void* nc_lptr;
 // with everything else compiled OUT: no Encodec input mode, no flattened column axis, no item-form staging state, no generic-pitch loop,
 // no GroupNorm epilogue.  This is the "scalar-register diet" of VERDICT r4: the legacy instances keep every run-time mode and pay for it
 // in spilled scalar registers whose reloads are vector instructions.
-template <int TM, int TN, int K, int CB, int NX, bool FUSE = false, int OCC = 2, int NW = 4, int NP = 0, bool DIST = false, int SUB = 0,
-          bool IN2 = false, bool XVK = false, bool DUO = false>
-__global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void conv_mfma_kernel(const ConvArgs p) {
-    // DUO (round 5): TWO tiles per workgroup.  A workgroup of 8 wavefronts is two "sub-workgroups" of 4 (one wavefront of each per SIMD),
-    // each with its own tile, its own half of the LDS and the XV-only loop -- but the second runs HALF A REDUCTION BLOCK behind the first,
-    // held there by the workgroup barrier, which both now pass twice per block (at the block's end and in its middle: one sub-workgroup's
-    // end is the other's middle).  Per half block one of them runs its staging run + two matrix-core segments, the other two segments:
-    // a staging run always has a partner inside a matrix-core segment on its SIMD.  With two independent workgroups per CU that
-    // anti-phase is left to chance (the phase trace: the pipe idles where both waves of a SIMD are outside their segments at once).
-    static_assert(!DUO || (XVK && !FUSE), "DUO belongs to the XV-only plain instances");
-    constexpr bool SPEC = NP > 0;
-    constexpr int NT = 64 * (NW + NP);             // threads per workgroup
-    constexpr int SW = SPEC ? NP : NW;             // waves that stage
-    constexpr int SNT = 64 * SW;
+template <int TM, int TN, int K, int CB, int NX, bool FUSE = false, int OCC = 2, int NW = 4, bool DIST = false, int SUB = 0,
+          bool IN2 = false, bool XVK = false>
+__global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs p) {
+    constexpr int NT = 64 * NW;                    // threads per workgroup
     constexpr int BM = 32 * TM;
     constexpr int BNW = 32 * TN;
     constexpr int BN = NW * BNW;
@@ -126,22 +87,21 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     constexpr int KP = KB / 2;
     constexpr int A_FLOATS = KB * BM;
     constexpr int A_VEC = A_FLOATS / 4;            // float4 words in the weight tile
-    constexpr int NA = (A_VEC + SNT - 1) / SNT;    // float4 copies per staging thread
+    constexpr int NA = (A_VEC + NT - 1) / NT;      // float4 copies per thread
     constexpr bool A_DMA = false;
-    constexpr int NSEG = SPEC ? 3 : DIST ? 2 : (KP >= 16 ? 4 : 2);   // (specialised: the producers stage a block in two groups)
+    constexpr int NSEG = DIST ? 2 : (KP >= 16 ? 4 : 2);
     constexpr int NG = NSEG - 1;
     constexpr int GA = (NA + NG - 1) / NG;         // per-group register footprint
     constexpr int GX = (NX + NG - 1) / NG;
     constexpr int GXX = IN2 ? 2 * GX : GX;         // staging registers per group: the second operand's samples sit behind the first's
-    static_assert(!IN2 || (!FUSE && !SPEC && !DIST), "the two-input staging mode belongs to the plain template");
+    static_assert(!IN2 || (!FUSE && !DIST), "the two-input staging mode belongs to the plain template");
     static_assert(KB % 2 == 0, "reduction block must hold an even number of kk");
     static_assert(A_FLOATS % 4 == 0, "A tile must be 16-byte granular");
 
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
-    const int sub = DUO ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;      // sub-workgroup (DUO), wave-uniform
-    float* const smem = DUO ? smem_all + sub * ((p.ep_off + 6 * BM + 3) & ~3) : smem_all;    // its half of the LDS
+    float* const smem = smem_all;
 
-    const int tid = DUO ? (int)(threadIdx.x & 255) : (int)threadIdx.x;
+    const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31;
@@ -162,9 +122,11 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
 #else
 #define NC_STAMP(cb, slot) do {} while (0)
 #endif
-    const bool producer = SPEC && wave >= NW;
-    const int swave = SPEC ? wave - NW : wave;     // index among the staging waves (consumers of the specialised variant: unused)
-    const int stid = SPEC ? tid - 64 * NW : tid;
+    // This wave and thread among the staging waves (every wave stages).  smem, swave and stid are plain copies kept as locals of their
+    // own: the staging lambdas capture them by reference, and with smem_all / wave / tid in their place the compiler schedules the
+    // kernels differently (same values, another instruction order).
+    const int swave = wave;
+    const int stid = tid;
 
     // ---- XCD-aware block -> tile map: block id b runs on XCD b%8 (observed; speed only).  Give each
     // XCD a contiguous range of the (phase, co_tile, clip, t_tile) order so the blocks resident on
@@ -175,13 +137,6 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     {
         const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
         lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    bool duo_dead = false;   // DUO: the second sub-workgroup of the last workgroup of an odd tile count repeats the last tile without storing
-    if constexpr (DUO) {
-        const int n_tiles = p.n_phase * p.n_co_tiles * p.B * p.n_t_tiles;
-        lin = 2 * lin + sub;
-        duo_dead = lin >= n_tiles;
-        lin = min(lin, n_tiles - 1);
     }
     // (integer division runs on the vector ALU: hand the wave-uniform results back to scalar registers)
     // Polyphase (transposed) launches: the stride phases of one output tile are adjacent in the order, so they run together on
@@ -257,7 +212,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     if constexpr (!XVK)
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-        const int item = swave + SW * i;
+        const int item = swave + NW * i;
         xc[i] = (item * chunk_magic) >> 20;
         const int jw = (item - xc[i] * nchunk) * 64 + lane;          // window slot of this lane
         const int sg = seg_of(col0 * s + jw, flat_px);               // its segment (0 without p.flat)
@@ -290,7 +245,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     // K = 7 (every launch whose rows start on 64-byte boundaries -- NC_XV_K7_MIN_COLS=<n> raises a column floor; NC_NO_XV_K7=1 keeps the legacy instances): the same for the dilated residual-unit convolutions with 8-byte words -- [8][320] floats = 5
     // float2 per thread, so the Snake work per thread stays exactly the item form's 10 elements, as packed pairs of one channel.
     constexpr bool XVCAND = XVK;
-    static_assert(!XVK || (TN == 2 && NW == 4 && !IN2 && !SPEC && !DIST && ((K == 2 && SUB != 0 && !FUSE) || (K == 7 && SUB == 0))),
+    static_assert(!XVK || (TN == 2 && NW == 4 && !IN2 && !DIST && ((K == 2 && SUB != 0 && !FUSE) || (K == 7 && SUB == 0))),
                   "XV-only instances: two-tap sub-pixel or k = 7, 256-column tiles");
     constexpr int XVW = K == 2 ? 4 : 2;                          // floats per staged word
     constexpr int XVROW = 320;                                   // (== XROWC of the 256-column tiles, defined with the fragment reads below)
@@ -325,15 +280,15 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             for (int n = 0; n < NV; ++n) rxv[n] = *reinterpret_cast<const xv_t*>(base + xvo[n]);
             const f32x4* src = wbase + (size_t)cbn * A_VEC;
 #pragma unroll
-            for (int n = 0; n < NA; ++n) rav[n] = (src + SNT * n)[(A_VEC % SNT == 0) ? (unsigned)stid : min((unsigned)stid, (unsigned)(A_VEC - 1 - SNT * n))];
+            for (int n = 0; n < NA; ++n) rav[n] = (src + NT * n)[(A_VEC % NT == 0) ? (unsigned)stid : min((unsigned)stid, (unsigned)(A_VEC - 1 - NT * n))];
         }
     };
     auto xv_store = [&](int cbn, float* Ad, float* Xd, auto allok_tag, auto snake_tag) __attribute__((always_inline)) {
         if constexpr (XVCAND) {
 #pragma unroll
             for (int n = 0; n < NA; ++n)
-                if ((A_VEC % SNT == 0) || stid + SNT * n < A_VEC) reinterpret_cast<f32x4*>(Ad)[stid + SNT * n] = rav[n];
-            if constexpr (K == 7 && NC_XV_SNAKE_ON && NC_XV_SNAKE_ILV && decltype(snake_tag)::value) {
+                if ((A_VEC % NT == 0) || stid + NT * n < A_VEC) reinterpret_cast<f32x4*>(Ad)[stid + NT * n] = rav[n];
+            if constexpr (K == 7 && decltype(snake_tag)::value) {
                 // Snake of the consumed tensor (snake(0) == 0: the zero padding survives it), the sine up to its sign ((-s)^2 == s^2 exactly:
                 // bit-identical, 8 of the ~25 instructions of a pair fewer; nc_math.h), and the NV words' chains STEP BY STEP side by side:
                 // read -> chain -> store word by word made every packed instruction wait on the one before it (an `s_nop` between each
@@ -353,17 +308,12 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
                     if ((XVN % NT == 0) || tid + NT * n < XVN) reinterpret_cast<xv_t*>(Xd)[tid + NT * n] = xv_t{xv[n][0], xv[n][1]};
             } else {
 #pragma unroll
-            for (int n = 0; n < NV; ++n) {
-                xv_t v = rxv[n];
-                if constexpr (!decltype(allok_tag)::value)
-                    if (!((xvok >> n) & 1u)) v = xv_t(0.0f);
-                if constexpr (K == 7 && NC_XV_SNAKE_ON && decltype(snake_tag)::value) {
-                    const float2 al = Al[cbn * CB + xvc[n]];
-                    const nc_f2 sm = nc_snakef2_m(nc_f2{v[0], v[1]}, nc_f2{al.x, al.x}, nc_f2{al.y, al.y});
-                    v[0] = sm[0]; v[1] = sm[1];
+                for (int n = 0; n < NV; ++n) {
+                    xv_t v = rxv[n];
+                    if constexpr (!decltype(allok_tag)::value)
+                        if (!((xvok >> n) & 1u)) v = xv_t(0.0f);
+                    if ((XVN % NT == 0) || tid + NT * n < XVN) reinterpret_cast<xv_t*>(Xd)[tid + NT * n] = v;
                 }
-                if ((XVN % NT == 0) || tid + NT * n < XVN) reinterpret_cast<xv_t*>(Xd)[tid + NT * n] = v;
-            }
             }
         }
     };
@@ -388,7 +338,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             if constexpr (i < NX) {
                 // (the item's channel is recomputed -- two scalar instructions -- instead of being held: NX pinned scalars pushed the
                 //  two-tap instances, NX = 20, into scalar-register spills whose reloads are vector instructions inside the loop)
-                const int ci = min(cbn * CB + (((swave + SW * i) * chunk_magic) >> 20), Cin - 1);           // wave-uniform
+                const int ci = min(cbn * CB + (((swave + NW * i) * chunk_magic) >> 20), Cin - 1);           // wave-uniform
                 const float* row = xb + (size_t)((unsigned)ci * x_cstride);   // uniform base + 32-bit lane offset
                 rx[u] = row[xg[i]];
                 if constexpr (IN2) rx[GX + u] = (xb2 + (size_t)((unsigned)ci * x_cstride))[xg[i]];
@@ -398,8 +348,8 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             constexpr int u = decltype(ut)::value, n = g * GA + u;
             if constexpr (n < NA) {
                 // uniform pointer (scalar arithmetic) + the thread index: no per-read vector address arithmetic
-                const f32x4* srcn = src + SNT * n;
-                ra[u] = srcn[(A_VEC % SNT == 0) ? (unsigned)stid : min((unsigned)stid, (unsigned)(A_VEC - 1 - SNT * n))];
+                const f32x4* srcn = src + NT * n;
+                ra[u] = srcn[(A_VEC % NT == 0) ? (unsigned)stid : min((unsigned)stid, (unsigned)(A_VEC - 1 - NT * n))];
             }
         });
     };
@@ -413,9 +363,9 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         nc_static_for<GA>([&](auto ut) __attribute__((always_inline)) {
             constexpr int u = decltype(ut)::value, n = g * GA + u;
             if constexpr (n < NA) {
-                const int idx = stid + SNT * n;
+                const int idx = stid + NT * n;
                 if constexpr (!A_DMA)
-                    if ((A_VEC % SNT == 0) || idx < A_VEC) reinterpret_cast<f32x4*>(Ad)[idx] = ra[u];
+                    if ((A_VEC % NT == 0) || idx < A_VEC) reinterpret_cast<f32x4*>(Ad)[idx] = ra[u];
             }
         });
         float2 al[GX] = {};
@@ -424,7 +374,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             nc_static_for<GX>([&](auto ut) __attribute__((always_inline)) {
                 constexpr int u = decltype(ut)::value, i = g * GX + u;
                 if constexpr (i < NX) {
-                    const int item = swave + SW * i;
+                    const int item = swave + NW * i;
                     al[u] = Al[cbn * CB + ((item * chunk_magic) >> 20)];
                     if constexpr (IN2) al2[u] = Al2[cbn * CB + ((item * chunk_magic) >> 20)];
                 }
@@ -435,7 +385,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         nc_static_for<GX>([&](auto ut) __attribute__((always_inline)) {
             constexpr int u = decltype(ut)::value, i = g * GX + u;
             if constexpr (i < NX) {
-                const int item = swave + SW * i;
+                const int item = swave + NW * i;
                 const int c = (item * chunk_magic) >> 20;
                 const int ci = cbn * CB + c;
                 const int j = (item - c * nchunk) * 64 + lane;
@@ -462,14 +412,14 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         });
         if constexpr (SNAKE) {   // Snake of the consumed tensor, two window values per packed instruction (nc_math.h; items past NX: unused)
             // groups of >= 2 pairs: the sine up to its sign and the pairs' chains step by step side by side (nc_math.h; round 5: in the k = 7
-            // instances 57 -> 37 `s_nop` and 40 vector instructions fewer per loop, conv_k7 -0.17 ms, bit-identical; NC_LEGACY_ROWS=0
-            // at compile time keeps the pair-by-pair form with the parity select)
-            if constexpr (GX >= 4 && NC_LEGACY_ROWS != 0) {
+            // instances 57 -> 37 `s_nop` and 40 vector instructions fewer per loop, conv_k7 -0.17 ms, bit-identical); smaller groups pair
+            // by pair with the parity select
+            if constexpr (GX >= 4) {
                 constexpr int NPR = GX / 2;
                 nc_f2 xs[NPR], as[NPR], is[NPR];
 #pragma unroll
                 for (int q = 0; q < NPR; ++q) { xs[q] = nc_f2{v[2 * q], v[2 * q + 1]}; as[q] = nc_f2{al[2 * q].x, al[2 * q + 1].x}; is[q] = nc_f2{al[2 * q].y, al[2 * q + 1].y}; }
-                nc_snakef2_m_rows<NPR, NC_LEGACY_ROWS == 1>(xs, as, is);
+                nc_snakef2_m_rows<NPR>(xs, as, is);
 #pragma unroll
                 for (int q = 0; q < NPR; ++q) { v[2 * q] = xs[q][0]; v[2 * q + 1] = xs[q][1]; }
             } else
@@ -490,7 +440,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         store_group_from(cbn, Ad, Xd, gtag, snake_tag, ra, rx);
     };
     auto store_group_any = [&](int cbn, float* Ad, float* Xd, auto gtag) __attribute__((always_inline)) {
-        if constexpr (!FUSE && !SPEC && !DIST) {
+        if constexpr (!FUSE && !DIST) {
             if (in_mode) { store_group(cbn, Ad, Xd, gtag, std::integral_constant<int, 2>{}); return; }
         }
         // (instances with >= 16 window items per lane only: on the k = 7 instances, NX = 10, whose masks fit the scalar file, the extra
@@ -520,7 +470,6 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         float rx0[XVK ? 1 : NG][GXX];
         if constexpr (XVK) xv_issue(0);
         else
-        if (!SPEC || producer)
             nc_static_for<NG>([&](auto g) __attribute__((always_inline)) { issue_group_to(0, g, ra0[decltype(g)::value], rx0[decltype(g)::value]); });
         // Snake alphas of all input channels -> (alpha, 1/alpha), 4 reads per thread in flight per pass
         if (alpha_in != nullptr) {
@@ -559,10 +508,9 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             if (K == 7 && alpha_in != nullptr) xv_store(0, As0, Xs0, std::false_type{}, std::true_type{});
             else xv_store(0, As0, Xs0, std::false_type{}, std::false_type{});
         } else
-        if (!SPEC || producer)
             nc_static_for<NG>([&](auto g) __attribute__((always_inline)) {
                 constexpr int gi = decltype(g)::value;
-                if constexpr (!FUSE && !SPEC && !DIST) {
+                if constexpr (!FUSE && !DIST) {
                     if (in_mode) { store_group_from(0, As0, Xs0, g, std::integral_constant<int, 2>{}, ra0[gi], rx0[gi]); return; }
                 }
                 if (alpha_in != nullptr)
@@ -589,7 +537,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         xt[k] = x_lane + (hi ? d : 0);
     }
 
-    constexpr int FD = XVK ? NC_XV_FD : 1;   // fragment reads run FD matrix-core steps ahead (FD + 1 register sets)
+    constexpr int FD = 1;   // fragment reads run FD matrix-core steps ahead (FD + 1 register sets)
     float fa[FD + 1][TM], fb[FD + 1][TN];
     // Ac = current weight buffer + hi*BM (the kk row of this lane half at step 0); xsc = scalar float index of the current window
     // Constant row pitch (XR, round 4): the k = 7 instances with 256-column tiles always stage 5 chunks of 64 slots per channel (a
@@ -601,7 +549,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     // The launcher's xrow is checked at run time; any other pitch (a strided k = 7 layer) takes the generic form below.
     // The two-tap instances (sub-pixel up-convolutions: a window of 256 + 1 (+ halos) slots) have the same pitch for the same reason.
     // 128-column tiles (TN = 1: the wide fused units): 128 + 6 d <= 182 slots, 3 chunks, pitch 192.
-    constexpr bool XRCAND = ((K == 7 && SUB == 0) || K == 2) && (TN == 2 || TN == 1) && NW == 4 && !IN2 && !SPEC && !DIST;
+    constexpr bool XRCAND = ((K == 7 && SUB == 0) || K == 2) && (TN == 2 || TN == 1) && NW == 4 && !IN2 && !DIST;
     constexpr int XROWC = TN == 2 ? 320 : 192;
     // (The same for the strided down-convolutions -- pitch, phase-row pitch and tap offsets all follow from (K, tile width), two lane
     //  pointers per column block -- and for the K = 1 instances was built and measured on one box: strided SLOWER, conv_down 2.82 ->
@@ -629,35 +577,6 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     };
     auto load_frag = [&](const float* Ac, int xsc, auto kp_tag) __attribute__((always_inline)) { load_frag_x(Ac, xsc, kp_tag, std::integral_constant<int, 0>{}); };
 
-    if constexpr (SPEC) {
-        static_assert(!SPEC || !FUSE, "the fused tail has workgroup barriers: not combined with producer waves");
-        if (producer) {
-            // Producer waves: their own loop (no accumulators live), one barrier per reduction block like the consumers.  Each
-            // block is staged in NG groups, a group's reads all in flight before its Snake + LDS writes.
-            // The reads of group q+1 are issued before group q is transformed and written (two register sets), and the producer
-            // waves run at raised issue priority: their short vector instructions are not starved by the consumers' matrix stream.
-            __builtin_amdgcn_s_setprio(3);
-            f32x4 pa[2][GA];
-            float px[2][GXX];
-            if (n_cb > 1) issue_group_to(1, std::integral_constant<int, 0>{}, pa[0], px[0]);
-            for (int cb = 0; cb < n_cb; ++cb) {
-                const int cur = cb & 1;
-                float* const An = As0 + (cur ^ 1) * A_FLOATS;
-                float* const Xn = Xs0 + (cur ^ 1) * xbuf;
-                if (cb + 1 < n_cb)
-                    nc_static_for<NG>([&](auto g) __attribute__((always_inline)) {
-                        constexpr int gi = decltype(g)::value;
-                        // next group in flight: group gi+1 of this block, or group 0 of the block after
-                        if constexpr (gi + 1 < NG) issue_group_to(cb + 1, std::integral_constant<int, gi + 1>{}, pa[(gi + 1) & 1], px[(gi + 1) & 1]);
-                        else if (cb + 2 < n_cb) issue_group_to(cb + 2, std::integral_constant<int, 0>{}, pa[(gi + 1) & 1], px[(gi + 1) & 1]);
-                        if (alpha_in != nullptr) store_group_from(cb + 1, An, Xn, g, std::true_type{}, pa[gi & 1], px[gi & 1]);
-                        else store_group_from(cb + 1, An, Xn, g, std::false_type{}, pa[gi & 1], px[gi & 1]);
-                    });
-                __syncthreads();
-            }
-            return;
-        }
-    }
     if constexpr (DIST) {
         static_assert(!DIST || NG == 1, "distributed staging holds the whole next block in one register group");
         // one staging unit: weight vector `un` (un < NA) or window item un - NA of block cbn
@@ -666,11 +585,11 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             constexpr bool SNAKE = decltype(snake_tag)::value;
             if constexpr (un < NA) {
                 // (threads past the tile's end hold a copy of its last vector and rewrite it: branch-free)
-                const int idx = (A_VEC % SNT == 0) ? stid + SNT * un : min(stid + SNT * un, A_VEC - 1);
+                const int idx = (A_VEC % NT == 0) ? stid + NT * un : min(stid + NT * un, A_VEC - 1);
                 reinterpret_cast<f32x4*>(Ad)[idx] = ra[un];
             } else {
                 constexpr int i = un - NA;
-                const int item = swave + SW * i;
+                const int item = swave + NW * i;
                 const int c = xc[i];
                 const int j = (item - c * nchunk) * 64 + lane;
                 const bool ok = (cbn * CB + c < Cin) & (((okm >> i) & 1u) != 0);
@@ -733,9 +652,6 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     if constexpr (XVCAND && XR == 1) {
         if (use_xv && n_cb > 1) xv_issue(1);      // (block 0 came through the prologue; see the rotating schedule below)
     }
-    if constexpr (DUO) {
-        if (sub == 1) __syncthreads();            // the second sub-workgroup starts half a block late ...
-    }
     for (int cb = 0; cb < n_cb; ++cb) {
         const int cur = cb & 1;
         const float* Ac = As0 + cur * A_FLOATS + hi * BM + nc_a_lane_off<TM>(l31);
@@ -753,44 +669,23 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             }
         }
 
-        if constexpr (SPEC) {
-            nc_static_for<FD>([&](auto d) __attribute__((always_inline)) {
-                if constexpr (decltype(d)::value < KP) load_frag(Ac, Xc, d);
-            });
-            nc_static_for<KP>([&](auto d) __attribute__((always_inline)) {
-                constexpr int kp = decltype(d)::value;
-                if constexpr (kp + FD < KP) load_frag(Ac, Xc, std::integral_constant<int, kp + FD>{});
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kp % (FD + 1)][i], fb[kp % (FD + 1)][j], acc[i][j], 0, 0, 0);
-            });
-        } else
         nc_static_for<NSEG>([&](auto seg_tag) __attribute__((always_inline)) {
             constexpr int seg = decltype(seg_tag)::value;
             if constexpr (seg == 0) NC_STAMP(cb, 0);
             else if constexpr (seg <= 3) NC_STAMP(cb, 2 * seg - 1);
-#if NC_STAGE_PRIO
-            if (more) __builtin_amdgcn_s_setprio(NC_STAGE_PRIO);   // (experiment: the staging run at raised issue priority)
-#endif
-            if constexpr (DUO && seg == NSEG / 2) __syncthreads();   // the partner's block boundary
             if (more) {
                 if constexpr (XVCAND && XR == 1) {   // (the XV-only instances)
-                    // rotating schedule: ONE register set.  At the head of segment NC_XV_STORE_SEG the words of block cb + 1 (in flight
-                    // since the same point of the block before: a whole block of latency cover) go to the idle LDS buffers, and the
-                    // reads of block cb + 2 are issued straight behind them (that block's buffers are the ones being read now, but its
-                    // words stay in registers until this block's closing barrier has passed).
-                    if constexpr (seg == (DUO ? 0 : NC_XV_STORE_SEG)) xv_stage(cb, An, Xn);   // (DUO: the run opens the block, beside the partner's segments 2-3)
+                    // rotating schedule: ONE register set.  At the head of segment 3 the words of block cb + 1 (in flight since the same
+                    // point of the block before: a whole block of latency cover) go to the idle LDS buffers, and the reads of block cb + 2
+                    // are issued straight behind them (that block's buffers are the ones being read now, but its words stay in registers
+                    // until this block's closing barrier has passed).  Segment 3 measured best (profiles/r05_ab_xv_store_segment.txt).
+                    static_assert(NSEG == 4, "the XV staging run sits at the head of segment 3");
+                    if constexpr (seg == 3) xv_stage(cb, An, Xn);
                 } else {
                     if constexpr (seg >= 1) store_group_any(cb + 1, An, Xn, std::integral_constant<int, (seg >= 1 ? seg - 1 : 0)>{});
                     if constexpr (seg < NG) issue_group(cb + 1, seg_tag);
                 }
             }
-#if NC_STAGE_PRIO
-            if (more) __builtin_amdgcn_s_setprio(0);
-#endif
             if constexpr (seg >= 1 && seg <= 3) NC_STAMP(cb, 2 * seg);
             // ---- matrix-core steps of this segment, ascending kk; fragments of step kp+1 are read before
             //      the MFMAs of step kp are issued (register double buffer fa/fb)
@@ -802,9 +697,6 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             nc_static_for<kp_hi - kp_lo>([&](auto d) __attribute__((always_inline)) {
                 constexpr int kp = kp_lo + decltype(d)::value;
                 if constexpr (kp + FD < KP) load_frag_x(Ac, Xc, std::integral_constant<int, kp + FD>{}, xr_tag);
-#if defined(NC_XV_NOSB)
-                if constexpr (!XVK)
-#endif
                 __builtin_amdgcn_sched_barrier(0);   // keep the fragment reads of step kp+1 ahead of the MFMAs of step kp
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -813,14 +705,8 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kp % (FD + 1)][i], fb[kp % (FD + 1)][j], acc[i][j], 0, 0, 0);
             });
         });
-        if constexpr (XVCAND && XR == 1 && NC_XV_STORE_SEG >= NSEG && !DUO) {   // (experiment: the words written behind the block's last matrix-core step)
-            if (more && use_xv) xv_stage(cb, An, Xn);
-        }
         NC_STAMP(cb, 7);
         __syncthreads();
-    }
-    if constexpr (DUO) {
-        if (sub == 0) __syncthreads();            // ... and the first passes the barrier once more at the end: equal counts
     }
     };
     if constexpr (XVK) {
@@ -861,7 +747,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
     for (int j = 0; j < TN; ++j) {
         const int col = col0 + wave * BNW + j * 32 + l31 - sgc[j] * flat_pc;   // column within its clip b + sgc[j]
         const int t = col * p.y_tstride + p.y_toff + phase;
-        const bool clip_ok = (col < p.n_cols) & (b + sgc[j] < p.Bc) & !duo_dead;
+        const bool clip_ok = (col < p.n_cols) & (b + sgc[j] < p.Bc);
         const unsigned clip_off = (unsigned)min(sgc[j], p.Bc - 1 - b) * (unsigned)p.y_bstride;   // (clamped: masked reads stay inside the tensor)
         if constexpr (SUB != 0) {   // t = sample of sub-row r = 0; row R adds (R + 4*hi) & smask.  Time bounds are checked per row.
             okc[j] = clip_ok;
@@ -960,7 +846,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
             for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) vq[rr][j] = v[j][4 * rq + rr];
-            if constexpr (XVK && NC_XV_SNAKE_ILV) {   // (XV-only instances: sign-free sine, the 2 x TN chains step by step side by side)
+            if constexpr (XVK) {   // (XV-only instances: sign-free sine, the 2 x TN chains step by step side by side)
                 if (snake) {
                     nc_f2 xs[2 * TN], as[2 * TN], is[2 * TN];
 #pragma unroll
@@ -1056,7 +942,7 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         });
     };
 
-    if constexpr (!FUSE && !SPEC && !XVK) {
+    if constexpr (!FUSE && !XVK) {
         // GroupNorm(1,C) block sums of the output (Encodec's NormConv1d, NormConv1d.cs:155): every 32x32 accumulator tile is reduced in
         // registers in the canonical order of nc_gn.h and leaves ONE (S1, S2) pair -- the tensor is not read back for its statistics.
         if (p.gn_part != nullptr) {
@@ -1152,8 +1038,8 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
         //      D registers holding rows (2m, 2m+1) of one lane half into the B operands of k-steps m and m+2.
         static_assert(!FUSE || K == 7, "the fused tail belongs to the k=7 residual-unit convolution");
         // 1) h = snake(h_pre + b7, a2), in place
-        if constexpr (XVK && NC_XV_SNAKE_ILV) {   // (XV-only instances: sign-free sine, eight chains step by step side by side -- pair by
-                                                  //  pair the compiler serialises them with an `s_nop` between every two instructions)
+        if constexpr (XVK) {   // (XV-only instances: sign-free sine, eight chains step by step side by side -- pair by
+                               //  pair the compiler serialises them with an `s_nop` between every two instructions)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1319,10 +1205,10 @@ __global__ __launch_bounds__((DUO ? 2 : 1) * 64 * (NW + NP), DUO ? 1 : OCC) void
 
 typedef void (*conv_kernel_fn)(const ConvArgs);
 
-template <int TM, int TN, int K, int CB, int NX, bool FUSE = false, int OCC = 2, int NW = 4, int NP = 0, bool DIST = false, int SUB = 0,
-          bool IN2 = false, bool XVK = false, bool DUO = false>
+template <int TM, int TN, int K, int CB, int NX, bool FUSE = false, int OCC = 2, int NW = 4, bool DIST = false, int SUB = 0,
+          bool IN2 = false, bool XVK = false>
 inline conv_kernel_fn get_conv_kernel() {
-    return &conv_mfma_kernel<TM, TN, K, CB, NX, FUSE, OCC, NW, NP, DIST, SUB, IN2, XVK, DUO>;
+    return &conv_mfma_kernel<TM, TN, K, CB, NX, FUSE, OCC, NW, DIST, SUB, IN2, XVK>;
 }
 
 }  // namespace nc
@@ -1353,10 +1239,10 @@ inline conv_kernel_fn get_conv_kernel() {
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_##NAME(int TM, int TN) {                                              \
         switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, true>(); \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, true>(); \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, true>(); \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, true>(); \
+            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
+            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
+            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
+            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1367,14 +1253,14 @@ inline conv_kernel_fn get_conv_kernel() {
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_sub_k##KVAL(int TM, int TN) {                                         \
         switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, true>();      \
+            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
+            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1384,10 +1270,10 @@ inline conv_kernel_fn get_conv_kernel() {
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_sub_narrow_k##KVAL(int TM) {                                          \
         switch (TM) {                                                                                      \
-            case 1: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 3, 0, false, true>();       \
-            case 2: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 3, 0, false, true>();       \
-            case 3: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 3, 0, false, true>();       \
-            case 4: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 3, 0, false, true>();       \
+            case 1: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
+            case 2: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
+            case 3: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
+            case 4: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1422,20 +1308,6 @@ inline conv_kernel_fn get_conv_kernel() {
     }                                                                                                      \
     }
 
-// Light variants: a shorter reduction block (smaller LDS tiles, fewer staging registers) compiled for 3 waves per SIMD, for
-// launches whose block count fits the chip in one round only at 3 workgroups per CU.  Same packed weight image as the
-// standard variant when its CB is a multiple of this one's (kk = ci*K + k is contiguous across reduction blocks).
-#define NC_INSTANTIATE_CONV_LIGHT(KVAL, CBVAL, NXVAL)                                                      \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_light_k##KVAL(int TM, int TN) {                                       \
-        switch (TM * 10 + TN) {                                                                            \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 3>();                         \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 3>();                         \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
 // Slim variants: half-size reduction block (half the LDS per workgroup) compiled for 4 waves per SIMD, for the narrow long-T layers
 // (Cout <= 64) whose workgroups are bound by their memory round trips: more workgroups per CU overlap them.  Same packed weight image.
 #define NC_INSTANTIATE_CONV_SLIM(KVAL, CBVAL, NXVAL) NC_INSTANTIATE_CONV_SLIM_N(slim, KVAL, CBVAL, NXVAL)
@@ -1447,20 +1319,6 @@ inline conv_kernel_fn get_conv_kernel() {
             case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 4>();                         \
             case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 4>();                         \
             case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 4>();                         \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Wide variants: 8 waves share one weight tile (BN = 512 columns), halving the weight traffic and staging per MFMA for the
-// long-clip layers; one workgroup per CU.
-#define NC_INSTANTIATE_CONV_WIDE(KVAL, CBVAL, NXVAL)                                                       \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_wide_k##KVAL(int TM, int TN) {                                        \
-        switch (TM * 10 + TN) {                                                                            \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 8>();                      \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 8>();                      \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 8>();                      \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1481,42 +1339,17 @@ inline conv_kernel_fn get_conv_kernel() {
     }                                                                                                      \
     }
 
-// Wave-specialised variants: 4 consumer + 2 producer waves (384 threads), 3 waves per SIMD with two workgroups per CU.
-#define NC_INSTANTIATE_CONV_SPEC(KVAL, CBVAL, NXVAL)                                                       \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_spec_k##KVAL(int TM, int TN) {                                        \
-        switch (TM * 10 + TN) {                                                                            \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 3, 4, 2>();                   \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 3, 4, 2>();                   \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Distributed-staging variants (see DIST above).
-#define NC_INSTANTIATE_CONV_DIST(KVAL, CBVAL, NXVAL)                                                       \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_dist_k##KVAL(int TM, int TN) {                                        \
-        switch (TM * 10 + TN) {                                                                            \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true>();             \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true>();             \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true>();             \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
 // Distributed staging for the one-workgroup-per-CU grids of the deep strided / sub-pixel layers (Encodec at 150 frames): with no
 // co-resident partner to feed the matrix pipe during a workgroup's staging runs, the runs are dealt into the matrix-core shadows.
 #define NC_INSTANTIATE_CONV_DIST_SMALL(NAME, KVAL, CBVAL, NXVAL, SUBV)                                     \
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_##NAME(int TM, int TN) {                                              \
         switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true, SUBV>();       \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true, SUBV>();       \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true, SUBV>();       \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true, SUBV>();       \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, true, SUBV>();       \
+            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
+            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
+            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
+            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
+            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1527,14 +1360,14 @@ inline conv_kernel_fn get_conv_kernel() {
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_subg_k##KVAL(int TM, int TN) {                                        \
         switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, 2>();         \
+            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
+            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
@@ -1545,21 +1378,9 @@ inline conv_kernel_fn get_conv_kernel() {
     namespace nc {                                                                                         \
     conv_kernel_fn conv_kernel_table_##NAME(int TM) {                                                      \
         switch (TM) {                                                                                      \
-            case 2: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, 0, false, SUBV, false, true>(); \
-            case 3: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, 0, false, SUBV, false, true>(); \
-            case 4: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, 0, false, SUBV, false, true>(); \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// DUO instances (see DUO above): two tiles per workgroup of 8 wavefronts, the second half a block behind the first.
-#define NC_INSTANTIATE_CONV_DUO(NAME, KVAL, CBVAL, NXVAL, SUBV)                                            \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_##NAME(int TM) {                                                      \
-        switch (TM) {                                                                                      \
-            case 2: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, false, true, true>(); \
-            case 3: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, 0, false, SUBV, false, true, true>(); \
+            case 2: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
+            case 3: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
+            case 4: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
         }                                                                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \

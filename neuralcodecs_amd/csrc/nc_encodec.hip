@@ -15,7 +15,6 @@
 #include "nc_gn.h"
 #include "nc_math.h"
 #include "nc_model.h"
-#include "nc_lstm.h"
 
 namespace nc {
 
@@ -631,13 +630,13 @@ __global__ __launch_bounds__(256) void euclid_vq_kernel(float* __restrict__ resi
 constexpr int EM_F = 32, EM_MAXD = 128;
 typedef float em_f32x16 __attribute__((ext_vector_type(16)));
 typedef float em_f32x4 __attribute__((ext_vector_type(4)));
-// NWV wavefronts share a stage's codebook scan (N / NWV codes each: 8 waves halve the scan of a workgroup that sits alone on its CU)
-template <int DD, int NWV = 4>
-__global__ __launch_bounds__(64 * NWV) void euclid_rvq_mfma_kernel(const float* __restrict__ residual, const float* const* __restrict__ cbT_ptrs,
+template <int DD>
+__global__ __launch_bounds__(256) void euclid_rvq_mfma_kernel(const float* __restrict__ residual, const float* const* __restrict__ cbT_ptrs,
                                                               const float* const* __restrict__ cb_ptrs, const float* const* __restrict__ c2_ptrs,
                                                               int n_q, int N, int B, int64_t T, int64_t* __restrict__ codes,
                                                               int64_t codes_bstride) {
     constexpr int D = DD;
+    constexpr int NWV = 4;   // wavefronts that share a stage's codebook scan, N / NWV codes each
     __shared__ float es[EM_MAXD][EM_F + 1];   // residual block [d][frame]: lane (frame, k half) of a B fragment reads es[2kp + half][frame]; rows padded by one
                                               // word -- the residual update walks d across the lanes (unpadded: every lane of a wave on ONE bank)
     __shared__ float e2s[EM_F];
@@ -972,17 +971,6 @@ void EncodecModel::load_lstm(const Blob& b, const std::string& key, Lstm& l, int
         }
         upload(y.bhh, static_cast<const float*>(bhh.data), (size_t)4 * C);
         upload(y.bih, static_cast<const float*>(bih.data), (size_t)4 * C);
-#ifdef NC_EXPERIMENTS
-        if (lstm2_supported(C)) {   // fragment images of nc_lstm.hip: W_hh of every layer (per-layer split kernel), W_ih of the upper one (fused kernel)
-            std::vector<float> img((size_t)4 * C * C);
-            lstm2_pack_image(static_cast<const float*>(whh.data), C, img.data());
-            upload(y.w2hh, img.data(), img.size());
-            if (i == 1 && cfg.lstm_layers == 2) {
-                lstm2_pack_image(static_cast<const float*>(wih.data), C, img.data());
-                upload(y.w2ih, img.data(), img.size());
-            }
-        }
-#endif
     }
 }
 
@@ -1517,76 +1505,6 @@ float* EncodecModel::run_lstm(Lstm& l, const float* x, int N, int64_t T, bool el
         io.y = gi; io.y_bstride = (int64_t)4 * C * T; io.y_cstride = T;
         launch_conv(y.ih, io, N, s, &prof);
     };
-#ifdef NC_EXPERIMENTS   // measured-and-rejected: `make EXPERIMENTS=1` compiles nc_lstm.hip and these two branches
-    // Fused two-layer launch (nc_lstm.hip, NC_LSTM_FUSED=1): every step of both layers in ONE persistent launch per pair of column tiles
-    // -- no drain in the exchange (values validated against a sentinel), chain wavefronts that never store, no tensors between the
-    // layers, no chunked projection GEMMs.  Bit-exact, but MEASURED SLOWER than the per-layer kernels below on two tiles (C3 9.5-9.8
-    // against 9.05 ms; 16 clips at 24 kHz 5.4-5.9 against 5.67 ms): with C / 4 = 128 workgroups in every exchange a step is 9.8-12 us
-    // (in-kernel trace, tools/probe/lstm2_trace.py: publish -> flags seen 2.6-3.4 us, operand loads 1.4-2.2 us, and the workgroups
-    // drift 3.5-5 us apart inside a step) against 5.7-6.2 us for an exchange among 32.  Kept as a switch, not the default: DESIGN 8.
-    static const bool fused_env = env_flag("NC_LSTM_FUSED");
-    const bool per_layer_env = !fused_env;
-    const int n_tiles2 = (N + 15) / 16;
-    const size_t ex_floats = lstm2_exchange_floats(C, T, std::min(n_tiles2, 2));
-    if (!stepwise && !per_layer_env && nl == 2 && lstm2_supported(C) && l.layers[1]->w2ih.p && cu_count >= C / 4 &&
-        lds_per_cu >= lstm2_lds_bytes(C, std::min(n_tiles2, 2)) && ex_floats * 4 < ((size_t)1 << 31) && (int64_t)4 * C * T * N < ((int64_t)1 << 31)) {
-        LstmSection section(*this, stream);
-        {   // NC_LSTM_FAKE_TIMEOUT=1 (tests): the first persistent launch of the process is reported as timed out
-            static bool fake = env_flag("NC_LSTM_FAKE_TIMEOUT");
-            if (fake) { fake = false; *reinterpret_cast<volatile unsigned*>(lstm_tmo_host) = 1; }
-        }
-        // layer 0's input projections of ALL steps as one pointwise GEMM over the [C][T][N] view of x: gi0 [4C][T][N]
-        float* xT = alloc((size_t)N * C * T);
-        float* gi0 = alloc((size_t)N * 4 * C * T);
-        float* out = alloc((size_t)N * C * T);
-        {
-            const int64_t n = (int64_t)N * C * T;
-            hipLaunchKernelGGL(nct_to_ctn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, xT, N, C, T);
-            NC_HIP(hipGetLastError());
-            ConvIO io{};
-            io.x = xT; io.x_bstride = 0; io.x_cstride = T * N; io.x_len = (int32_t)(T * N); io.Tin = T * N;
-            io.y = gi0; io.y_bstride = 0; io.y_cstride = T * N;
-            launch_conv(l.layers[0]->ih, io, 1, stream, &prof);
-        }
-        for (int tl = 0; tl < n_tiles2; tl += 2) {
-            const int nt = std::min(2, n_tiles2 - tl);
-            const size_t exf = lstm2_exchange_floats(C, T, nt);
-            float* S = alloc(exf);
-            unsigned* flags = reinterpret_cast<unsigned*>(alloc((size_t)nt * 2 * (C / 4)));
-            NC_HIP(hipMemsetAsync(S, 0xFF, exf * 4, stream));                       // LSTM2_SENTINEL in every word
-            NC_HIP(hipMemsetAsync(flags, 0, (size_t)nt * 2 * (C / 4) * 4, stream));
-            Lstm2Args a{};
-            a.gi0 = gi0; a.whh0 = l.layers[0]->w2hh.as<float>(); a.wih1 = l.layers[1]->w2ih.as<float>(); a.whh1 = l.layers[1]->w2hh.as<float>();
-            a.bhh0 = l.layers[0]->bhh.as<float>(); a.bih1 = l.layers[1]->bih.as<float>(); a.bhh1 = l.layers[1]->bhh.as<float>();
-            a.skip = x; a.out = out; a.elu_out = elu_out ? 1 : 0; a.S = S; a.flags = flags; a.tmo = lstm_tmo_dev;
-            a.N = N; a.C = C; a.T = T; a.tile0 = tl; a.tiles = nt;
-            const double nn = (double)std::min(N - tl * 16, nt * 16) * (double)T;
-            if (prof.on) prof.begin(stream, NC_KC_LSTM, 2.0 * 3 * 4 * C * C * nn, 4.0 * 8 * C * nn);   // W_hh0, W_ih1, W_hh1 contractions
-            static const char* trace_path = env_str("NC_LSTM2_TRACE");   // diagnostic: stamps of 8 steps of the first full-size launch
-            static bool traced = false;
-            const size_t trace_words = (size_t)(C / 4) * nt * 8 * LSTM2_TRACE_STEPS * 4 + 4;   // + the clock probe
-            if (trace_path && !traced && T >= LSTM2_TRACE_T0 + LSTM2_TRACE_STEPS) {
-                a.trace = reinterpret_cast<unsigned long long*>(alloc(trace_words * 2));
-                NC_HIP(hipMemsetAsync(a.trace, 0, trace_words * 8, stream));
-            }
-            lstm2_launch(a, stream);
-            if (prof.on) prof.end(stream);
-            if (a.trace) {
-                traced = true;
-                std::vector<unsigned long long> hbuf(trace_words);
-                NC_HIP(hipStreamSynchronize(stream));
-                NC_HIP(hipMemcpy(hbuf.data(), a.trace, trace_words * 8, hipMemcpyDeviceToHost));
-                if (FILE* f = std::fopen(trace_path, "wb")) {
-                    const int hdr[4] = {C / 4, nt, 8, LSTM2_TRACE_STEPS};
-                    std::fwrite(hdr, sizeof(int), 4, f);
-                    std::fwrite(hbuf.data(), 8, trace_words, f);
-                    std::fclose(f);
-                }
-            }
-        }
-        return out;
-    }
-#endif  // NC_EXPERIMENTS
     if (!stepwise && C % 64 == 0 && (KS == 128 || KS == 16)) {
         LstmSection section(*this, stream);   // (see LstmTicket: sections of different handles on one device run one after the other)
         // Persistent layer kernel: a launch runs a range of steps for a group of column tiles (<= 64 co-resident workgroups, so the
@@ -1633,35 +1551,15 @@ float* EncodecModel::run_lstm(Lstm& l, const float* x, int N, int64_t T, bool el
             static bool fake = env_flag("NC_LSTM_FAKE_TIMEOUT");
             if (fake) { fake = false; *reinterpret_cast<volatile unsigned*>(lstm_tmo_host) = 1; }
         }
-        // Role-split kernel (nc_lstm.hip lstm1_kernel, round 4, NC_LSTM_SPLIT=1): the same launches and chunk schedule, but load-only chain
-        // waves, store-only gate waves and exchange regions that are never reused and validated by value -- no drain.  Bit-exact and
-        // MEASURED SLOWER than lstm_seq_kernel (C3 10.1-10.2 against 9.07-9.15 ms on the same box, 16 clips at 24 kHz 6.75-6.9 against 5.6),
-        // with the flags polled by a gate wave and by a (load-only) chain wave alike: without the drain the hint flags run ahead of
-        // the payload, so operand loads are retried, and the LDS post / wait hops between chain, gate and polling waves cost more than
-        // the two workgroup barriers they replace.  Not the default; DESIGN 8 round 4.
-#ifdef NC_EXPERIMENTS
-        static const bool want_split = env_flag("NC_LSTM_SPLIT");
-        const bool split = want_split && lstm2_supported(C) && l.layers[0]->w2hh.p && lds_per_cu >= lstm1_lds_bytes(C) &&
-                           (size_t)T * n_tiles * C * 16 * 4 < ((size_t)1 << 31);
-#else
-        constexpr bool split = false;
-#endif
         std::vector<float*> gi(nl), out(nl), hx(nl), cs(nl);
         std::vector<unsigned*> flags(nl);
         for (int li = 0; li < nl; ++li) {
             gi[li] = alloc((size_t)N * 4 * C * T);
             out[li] = alloc((size_t)N * C * T);
             cs[li] = alloc((size_t)n_tiles * C * 16);
-            if (split) {
-                hx[li] = alloc((size_t)T * n_tiles * C * 16);                          // one exchange region per step
-                NC_HIP(hipMemsetAsync(hx[li], 0xFF, (size_t)T * n_tiles * C * 16 * 4, stream));   // LSTM2_SENTINEL in every word
-                flags[li] = reinterpret_cast<unsigned*>(alloc((size_t)n_tiles * (C / 4)));
-                NC_HIP(hipMemsetAsync(flags[li], 0, (size_t)n_tiles * (C / 4) * 4, stream));
-            } else {
-                hx[li] = alloc((size_t)2 * n_tiles * C * 16);
-                flags[li] = reinterpret_cast<unsigned*>(alloc((size_t)n_tiles * nprod));   // per call + layer: groups may run concurrently
-                NC_HIP(hipMemsetAsync(flags[li], 0, (size_t)n_tiles * nprod * 4, stream));
-            }
+            hx[li] = alloc((size_t)2 * n_tiles * C * 16);
+            flags[li] = reinterpret_cast<unsigned*>(alloc((size_t)n_tiles * nprod));   // per call + layer: groups may run concurrently
+            NC_HIP(hipMemsetAsync(flags[li], 0, (size_t)n_tiles * nprod * 4, stream));
         }
         hipStream_t sA = stream, sB = stream;
         size_t ev_i = 0;
@@ -1682,21 +1580,7 @@ float* EncodecModel::run_lstm(Lstm& l, const float* x, int N, int64_t T, bool el
             const bool last = li + 1 == nl;
             const double n = (double)N * (double)(t1 - t0);
             if (prof.on) prof.begin(s, NC_KC_LSTM, 2.0 * 4 * C * C * n, 4.0 * 6 * C * n);
-#ifdef NC_EXPERIMENTS
-            for (int tl = 0; split && tl < n_tiles; tl += 4) {                         // (C / 16 workgroups per tile: up to four tiles per launch)
-                const int nt = std::min(4, n_tiles - tl);
-                LstmSplitArgs a{};
-                a.gi = gi[li]; a.w = y.w2hh.as<float>(); a.bhh = y.bhh.as<float>(); a.skip = last ? x : nullptr; a.out = out[li]; a.elu_out = (last && elu_out) ? 1 : 0;
-                if (piped) { a.gi_b = 1; a.gi_c = T * N; a.gi_t = N; }
-                else { a.gi_b = (int64_t)4 * C * T; a.gi_c = T; a.gi_t = 1; }
-                if (between(li)) { a.out_b = 1; a.out_c = T * N; a.out_t = N; }
-                else { a.out_b = (int64_t)C * T; a.out_c = T; a.out_t = 1; }
-                a.S = hx[li]; a.flags = flags[li]; a.tmo = sync; a.cstate = cs[li];
-                a.N = N; a.C = C; a.T = T; a.t0 = t0; a.t1 = t1; a.tile0 = tl; a.tiles_total = n_tiles;
-                lstm1_launch(a, nt, s);
-            }
-#endif
-            for (int tl = 0; !split && tl < n_tiles; tl += per_launch) {
+            for (int tl = 0; tl < n_tiles; tl += per_launch) {
                 const int nt = std::min(per_launch, n_tiles - tl);
                 LstmSeqArgs a{};
                 a.gi = gi[li]; a.whhp = y.whhp.as<float>(); a.bhh = y.bhh.as<float>(); a.skip = last ? x : nullptr; a.out = out[li]; a.elu_out = (last && elu_out) ? 1 : 0;
@@ -1854,17 +1738,6 @@ void EncodecModel::encode_batch(const float* x, int N, int64_t L, int64_t Tz, in
     const int Nc = cfg.codebook_size;
     if (!no_mfma_vq && Nc % 512 == 0 && Nc <= 1024 && D == 128) {
         // all stages in one launch, cross terms on the matrix cores (the residual block stays in LDS between the stages)
-        // (NC_RVQ_8WAVES=1: 8 wavefronts per workgroup, 128 codes each -- measured the same 236 us on C3's 150-workgroup grid as the
-        // 4-wave form: the stage is bound by its serial phases and the codebook stream, not by the matrix-core chain)
-#ifdef NC_EXPERIMENTS
-        static const bool rvq8 = env_flag("NC_RVQ_8WAVES");
-        const bool wide = rvq8 && Nc % 1024 == 0 && (total + EM_F - 1) / EM_F <= 256;
-        if (wide)
-            hipLaunchKernelGGL((euclid_rvq_mfma_kernel<128, 8>), dim3((unsigned)((total + EM_F - 1) / EM_F)), dim3(512), 0, stream, residual,
-                               book_ptrsT.as<const float*>(), book_ptrs.as<const float*>(), book_ptrs2.as<const float*>(), n_q, Nc, N, Tz, codes,
-                               (int64_t)n_q * Tz);
-        else
-#endif
         hipLaunchKernelGGL(euclid_rvq_mfma_kernel<128>, dim3((unsigned)((total + EM_F - 1) / EM_F)), dim3(256), 0, stream, residual,
                            book_ptrsT.as<const float*>(), book_ptrs.as<const float*>(), book_ptrs2.as<const float*>(), n_q, Nc, N, Tz, codes,
                            (int64_t)n_q * Tz);

@@ -30,7 +30,6 @@ const EnvRow kEnv[] = {
     {"NC_NO_TN_ROUNDS", 'b', "no round-count rule for the column-tile width"},
     {"NC_NO_XR", 'b', "generic B-fragment addressing in the conv template (no constant-pitch immediate offsets)"},
     {"NC_NO_XV", 'b', "legacy instances with item-wise window staging everywhere (no XV-only instances)"},
-    {"NC_DUO", 'b', "EXPERIMENTS=1 builds: k = 7 residual-unit convolutions as DUO instances (two tiles per 8-wavefront workgroup, the second half a block behind; measured slower)"},
     {"NC_XV_K7_MIN_COLS", 'i', "columns per clip from which the k = 7 convolutions take the XV-only instances (0: wherever the rows are 64-byte aligned)"},
     {"NC_NO_XV_K7", 'b', "legacy instances for the k = 7 residual-unit convolutions (no XV-only instances on the long rows)"},
     {"NC_NO_NARROW", 'b', "no 3-wave narrow variants"},
@@ -38,7 +37,6 @@ const EnvRow kEnv[] = {
     {"NC_NO_SUBPIXEL", 'b', "per-phase launches for power-of-two strided transposed convolutions"},
     {"NC_NO_SUBPIXEL_ANY", 'b', "per-phase launches for the other strides (3, 5)"},
     {"NC_NO_CONV1X1", 'b', "pointwise layers through the windowed template"},
-    {"NC_PW_STREAM", 'b', "EXPERIMENTS=1 builds: streaming pointwise variant for the narrow long rows (overtaken in round 4)"},
     {"NC_NO_SKINNY", 'b', "no skinny projection kernel (Cout <= 16)"},
     {"NC_NO_THIN", 'b', "PCM heads through the matrix-core template"},
     {"NC_THIN_NO_VEC", 'p', "scalar window loads in the thin-output kernel"},
@@ -48,7 +46,6 @@ const EnvRow kEnv[] = {
     {"NC_TINY_BLOCKS", 'i', "grid size below which the tiny-grid rule applies (256)"},
     {"NC_NO_DIST_SMALL", 'b', "segmented staging on small grids"},
     {"NC_DIST_MAX_GRID", 'i', "largest grid that takes distributed staging (768)"},
-    {"NC_LDS_MIN", 'i', "minimum dynamic LDS per workgroup (placement experiments)"},
     {"NC_NO_CONV_SMALL", 'b', "no short-row 16x16x4 kernel"},
     {"NC_SMALL_MAX_GRID", 'i', "largest short-row grid (2048)"},
     {"NC_SMALL_WIDE_BELOW", 'i', "template grid below which the 32-column short-row form is taken (512)"},
@@ -56,7 +53,6 @@ const EnvRow kEnv[] = {
     {"NC_SMALL_TN", 'i', "force the short-row column tiles (1 | 2 | 4)"},
     {"NC_SMALL_ROLLED", 'b', "rolled short-row loop"},
     {"NC_DAC_RVQ_STAGEWISE", 'p', "DAC quantizer stage by stage"},
-    {"NC_RVQ_8WAVES", 'b', "EXPERIMENTS=1 builds: 8-wavefront Euclidean RVQ workgroups (measured equal)"},
     {"NC_EUCLID_NO_MFMA", 'p', "vector Euclidean codebook search"},
     {"NC_ENCODEC_NO_FUSE", 'b', "padded / activated copies instead of the fused SConv1d input mode"},
     {"NC_ENCODEC_NO_OVERLAP", 'b', "segment groups one after the other"},
@@ -74,15 +70,12 @@ const EnvRow kEnv[] = {
     {"NC_RMS_TWO_PASS", 'b', "Encodec RMS scale as two launches (chunk sums, final) instead of the one-launch form"},
     {"NC_NO_RES_A", 'b', "residual blocks of the Encodec 48 kHz outer stages: shortcut and k = 3 branch as two launches instead of the fused first pass"},
     {"NC_SYNC_ACQUIRE", 'b', "agent-scope acquire fence behind the persistent LSTM's flag poll and in front of the in-launch GroupNorm finish"},
-    {"NC_LSTM_SPLIT", 'b', "EXPERIMENTS=1 builds: per-layer persistent LSTM with load-only / store-only wave roles and value-validated exchange regions (lstm1_kernel; measured slower)"},
     {"NC_LSTM_STEPWISE", 'b', "one LSTM launch per step"},
     {"NC_LSTM_CHUNKS", 'i', "layer-pipeline chunks of the per-layer persistent LSTM (6; 1 = layers in sequence)"},
     {"NC_LSTM_EVEN_CHUNKS", 'b', "equal LSTM chunks"},
     {"NC_LSTM_UB", 'i', "hidden-unit blocks per LSTM workgroup (2 | 4)"},
     {"NC_LSTM_NO_HTILE", 'b', "persistent LSTM: every wavefront fetches its own h operands, W_hh in LDS (the form before the LDS h tile)"},
     {"NC_LSTM_NO_ELU", 'b', "the consumer applies the ELU behind an SLSTM"},
-    {"NC_LSTM_FUSED", 'b', "EXPERIMENTS=1 builds: fused two-layer persistent LSTM (nc_lstm.hip; measured slower)"},
-    {"NC_LSTM2_TRACE", 's', "EXPERIMENTS=1 builds: file for the in-kernel stamps of the fused LSTM (tools/probe/lstm2_trace.py)"},
     {"NC_LSTM_FAKE_TIMEOUT", 'b', "tests: report the first persistent LSTM launch as timed out"},
     {"NC_SNAC_NO_FUSE", 'b', "SNAC residual units in two launches (depthwise, pointwise)"},
     {"NC_SNAC_FUSE_MIN_COLS", 'i', "columns (clips x steps) from which the one-launch SNAC residual unit is taken (65536)"},
@@ -95,10 +88,6 @@ const EnvRow kEnv[] = {
     {"NC_LAUNCH_LOG", 's', "launch log for the per-class PMC attribution"},
     {"NC_CONV_TRACE_FILE", 's', "-DNC_CONV_TRACE builds: file for the in-kernel phase trace of the convolution template (tools/probe/conv_trace.py)"},
     {"NC_CONV_TRACE_SEL", 's', "-DNC_CONV_TRACE builds: \"K,Cin,dilation\" of the launch to trace (default 7,384,1)"},
-    {"NC_LIGHT", 'i', "EXPERIMENTS=1 builds: light k = 7 variant"},
-    {"NC_WIDE", 'i', "EXPERIMENTS=1 builds: 8-wave k = 7 variant"},
-    {"NC_SPEC", 'i', "EXPERIMENTS=1 builds: producer / consumer k = 7 variant"},
-    {"NC_DIST", 'i', "EXPERIMENTS=1 builds: distributed-staging k = 7 variant"},
 };
 const EnvRow& env_row(const char* name, char kind) {
     for (const EnvRow& r : kEnv)

@@ -101,52 +101,22 @@ FALLBACK_ROWS = [
     {"NC_NO_FUSE": "1", "NC_ENCODEC_NO_FUSE": "1", "NC_DAC_RVQ_STAGEWISE": "1"},       # two-launch residual units, padded copies, stage-wise RVQ
     {"NC_NO_FLAT_GN": "1", "NC_LSTM_NO_ELU": "1", "NC_NO_DIST_SMALL": "1", "NC_LSTM_UB": "2", "NC_NO_SUBPIXEL_ANY": "1"},   # one-clip GroupNorm tiles, ELU in the consumer, segmented staging, 8-wave LSTM
     {"NC_SNAC_NO_FUSE": "1", "NC_ATTN_NO_MFMA": "1", "NC_LN_TILE": "0"},                # SNAC units in two launches, vector attention, per-column LayerNorm
-    {"NC_LSTM_FUSED": "1", "NC_RVQ_8WAVES": "1"},                                      # EXPERIMENTS=1 library: fused two-layer LSTM, 8-wave Euclidean RVQ
     {"NC_SYNC_ACQUIRE": "1"},                                                          # acquire fences in the LSTM exchange and the in-launch GroupNorm finish
-    {"NC_LSTM_SPLIT": "1"},                                                            # EXPERIMENTS=1 library: role-split per-layer persistent LSTM (nc_lstm.hip lstm1_kernel)
     {"NC_SNAC_FUSE_MIN_COLS": "0", "NC_LN_TILE": "16"},                                # one-launch SNAC residual units on the small fixtures too
     {"NC_NO_XR": "1"},                                                                 # generic fragment addressing in the conv template
-    {"NC_PW_STREAM": "1"},                                                             # EXPERIMENTS=1 library: streaming pointwise kernel
     {"NC_NO_XV": "1"},                                                                 # legacy instances for the two-tap up-convolutions (item-form staging)
     {"NC_NO_XV_K7": "1"},                                                              # legacy instances for the k = 7 convolutions on the long rows
-    {"NC_DUO": "1"},                                                                   # EXPERIMENTS=1 library: two tiles per 8-wavefront workgroup (k = 7)
     {"NC_NO_RES_A": "1", "NC_NO_DOWN2": "1", "NC_NO_DOWN4": "1", "NC_NO_DOWN5": "1", "NC_NO_UP2": "1", "NC_NO_UP4": "1", "NC_NO_UP_PITCH": "1", "NC_RMS_TWO_PASS": "1", "NC_LSTM_NO_HTILE": "1"},                                                              # round-5 launches: two-launch first pass of the residual blocks, windowed stride-2 down-conv, two-pass RMS scale
 ]
 
 
-# Switches of measured-and-rejected kernels: compiled by `make -C neuralcodecs_amd/csrc EXPERIMENTS=1` only (libnc_mi355x_exp.so, round 5:
-# the shipped library carries shipped paths only).  Rows that name one run against that library when it has been built, and skip otherwise.
-EXPERIMENT_SWITCHES = {"NC_LSTM_FUSED", "NC_LSTM_SPLIT", "NC_PW_STREAM", "NC_RVQ_8WAVES", "NC_LIGHT", "NC_WIDE", "NC_SPEC", "NC_DIST", "NC_DUO"}
-EXP_LIB = os.path.join(ROOT, "neuralcodecs_amd", "libnc_mi355x_exp.so")
-
-
-def _env_for(row):
-    e = dict(os.environ, **row)
-    if EXPERIMENT_SWITCHES & set(row):
-        if not os.path.exists(EXP_LIB):
-            pytest.skip("needs the EXPERIMENTS=1 library (make -C neuralcodecs_amd/csrc EXPERIMENTS=1)")
-        e["NC_MI355X_LIB"] = EXP_LIB
-    return e
-
-
 @pytest.mark.parametrize("row", FALLBACK_ROWS, ids=lambda r: "+".join(sorted(r)))
 def test_parity_under_fallback_switches(row):
-    e = _env_for(row)
+    e = dict(os.environ, **row)
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
            os.path.join(ROOT, "tests", "test_encodec_gpu.py") + "::test_encodec_small_vs_golden_and_oracle",
            os.path.join(ROOT, "tests", "test_encodec_gpu.py") + "::test_encodec48k_config_c3_shape",
            os.path.join(ROOT, "tests", "test_dac_gpu.py") + "::test_small_bit_exact_vs_c_oracle",
-           os.path.join(ROOT, "tests", "test_snac_gpu.py")]
-    r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-1500:])
-
-
-def test_streaming_pointwise_variant_under_its_switch():
-    """conv1x1_stream_kernel is no longer the default for the narrow long rows (round 4: the tile-per-workgroup kernel overtook it);
-    NC_PW_STREAM=1 selects it, and it stays held to the oracle: its own bit-exactness cases and the SNAC suite (whose 44 kHz units it served)."""
-    e = _env_for({"NC_PW_STREAM": "1"})
-    cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-           os.path.join(ROOT, "tests", "test_ops_gpu.py") + "::test_pointwise_streaming_variant_bit_exact",
            os.path.join(ROOT, "tests", "test_snac_gpu.py")]
     r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-1500:])

@@ -4,12 +4,7 @@
 # The hand-picked rows below combine switches that do not mask each other; `envmatrix.sh --each` instead ENUMERATES the engine's one
 # switch table (nc_debug_switches(), csrc/nc_util.hip) and runs the suites once per boolean switch, so a new switch is covered the
 # day it is added to the table.
-# Round 5: the switches of measured-and-rejected kernels (docs starting "EXPERIMENTS=1 builds") exist in libnc_mi355x_exp.so only
-# (`make -C neuralcodecs_amd/csrc EXPERIMENTS=1`, built HERE when missing -- the one matrix row that builds it); rows naming one run with
-# NC_MI355X_LIB pointing at that library.
 cd $GRAFT_REPO_ROOT
-EXP=$PWD/neuralcodecs_amd/libnc_mi355x_exp.so
-expl() { [ -f $EXP ] || make -C neuralcodecs_amd/csrc EXPERIMENTS=1 -j16 -s >/dev/null 2>&1; run NC_MI355X_LIB=$EXP "$@"; }
 run() { echo "== $*"; env "$@" timeout 900 python -m pytest tests/test_ops_gpu.py tests/test_dac_gpu.py tests/test_encodec_gpu.py tests/test_snac_gpu.py -m gpu -x -q 2>&1 | grep -E "passed|failed|rror" | head -3; }
 if [ "$1" = "--each" ]; then
   for sw in $(python - <<'PY'
@@ -17,9 +12,9 @@ from neuralcodecs_amd import _lib
 for line in _lib.lib().nc_debug_switches().decode().splitlines():
     name, kind, _ = line.split("\t")
     if kind in "bp" and name not in ("NC_LSTM_FAKE_TIMEOUT",):
-        print(("X:" if _.startswith("EXPERIMENTS=1") else "") + name)
+        print(name)
 PY
-); do case $sw in X:*) expl ${sw#X:}=1;; *) run $sw=1;; esac; done
+); do run $sw=1; done
   exit 0
 fi
 run NC_DEFAULT=1
@@ -48,8 +43,3 @@ run NC_NO_RES_A=1 NC_NO_DOWN2=1 NC_NO_DOWN4=1 NC_NO_DOWN5=1 NC_NO_UP2=1 NC_NO_UP
 run NC_NO_UP_PITCH=1 NC_RMS_TWO_PASS=1 NC_LSTM_CHUNKS=3
 run NC_LSTM_NO_HTILE=1
 run NC_DAC_PITCH=1
-# round 5: the experiments library (measured-and-rejected kernels)
-expl NC_LSTM_FUSED=1 NC_RVQ_8WAVES=1
-expl NC_LSTM_SPLIT=1
-expl NC_PW_STREAM=1
-expl NC_DUO=1
