@@ -436,6 +436,28 @@ NC_API nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32
                                   int32_t n_q, int32_t N, int32_t form, int64_t* codes, float* residual_out);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */
 NC_API nc_status nc_op_fold_weight_norm(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
+/* The HBM-bound SNAC kernels, one at a time (host pointers in and out, like nc_op_conv1d).
+ * Depthwise convolution (ResidualUnit.cs:32, groups == C) on x [B,C,T], w [C][K], K <= 7: y [B,C,T] holds the first T outputs
+ * y[b,c,t] = snake_out?(sum_k w[c,k] * snake_in?(x[b,c,t + k*dil - pad]) + bias[c]) over the zero-extended row; with "same" padding
+ * (2*pad == dil*(K-1)) that is the whole convolution.  bias / alpha_in / alpha_out [C] are nullable. */
+NC_API nc_status nc_op_dwconv1d(int device_index, int32_t B, int32_t C, int64_t T, int32_t K, int32_t pad, int32_t dil, const float* x,
+                                const float* w, const float* bias, const float* alpha_in, const float* alpha_out, float* y);
+/* LayerNorm over the channels of x [B,C,T] (LocalMHA.cs:85, eps 1e-5) -> y [B,C,T] */
+NC_API nc_status nc_op_layer_norm(int device_index, int32_t B, int32_t C, int64_t T, const float* x, const float* gamma,
+                                  const float* beta, float* y);
+/* Windowed rotary attention (LocalMHA.cs:84-113) on qkv [B,3C,T] (channel = part*C + head*64 + d) -> y [B,C,T]; W <= 32, T % W == 0,
+ * C % 64 == 0, else NC_EUNSUPPORTED.  inv_freq [32] is the checkpoint's rel_pos buffer (required); the cos / sin tables are built from it
+ * by the function the SNAC model uses. */
+NC_API nc_status nc_op_local_attn(int device_index, int32_t B, int32_t C, int64_t T, int32_t W, const float* qkv, const float* inv_freq,
+                                  float* y);
+/* avg_pool1d(s) (VectorQuantizer.cs:88) on x [rows,T] -> y [rows,T/s] */
+NC_API nc_status nc_op_avg_pool(int device_index, int64_t rows, int64_t T, int32_t s, const float* x, float* y);
+/* One depthwise SNAC ResidualUnit (ResidualUnit.cs:25-60): y = snake_next?(x + W1 . snake_a2(dw7_dil(snake_a1(x)) + b7) + b1) on x [B,C,T],
+ * w7 [C][7], w1 [C][C]; b7 / b1 / alpha_next nullable.  fused != 0 runs the one-launch kernel whatever NC_SNAC_FUSE_MIN_COLS says and
+ * returns NC_EUNSUPPORTED where that kernel does not serve the shape (it never falls back); fused == 0 runs the two-launch path. */
+NC_API nc_status nc_op_snac_unit(int device_index, int32_t B, int32_t C, int64_t T, int32_t dil, const float* x, const float* w7,
+                                 const float* b7, const float* a1, const float* a2, const float* w1, const float* b1,
+                                 const float* alpha_next, int32_t fused, float* y);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,11 @@ SYMBOLS = [
     ("nc_op_vq_argmin", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P]),
     ("nc_op_euclid_rvq", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("nc_op_fold_weight_norm", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    ("nc_op_dwconv1d", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("nc_op_layer_norm", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P]),
+    ("nc_op_local_attn", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("nc_op_avg_pool", C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    ("nc_op_snac_unit", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
 ]
 
 

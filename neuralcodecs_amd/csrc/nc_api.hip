@@ -803,4 +803,125 @@ nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, i
     });
 }
 
+// ---- op hooks over the HBM-bound SNAC kernels (nc_elem.hip, nc_snac_unit.hip) ----
+static float* op_upload(DevBuf& d, const float* h, size_t n) {
+    d.reserve(n * 4);
+    NC_HIP(hipMemcpy(d.p, h, n * 4, hipMemcpyHostToDevice));
+    return d.as<float>();
+}
+
+nc_status nc_op_dwconv1d(int device_index, int32_t B, int32_t C, int64_t T, int32_t K, int32_t pad, int32_t dil, const float* x,
+                         const float* w, const float* bias, const float* alpha_in, const float* alpha_out, float* y) {
+    return guard([&] {
+        if (!x || !w || !y) fail(NC_EINVAL, "null argument");
+        if (B <= 0 || C <= 0 || T <= 0 || T > ((int64_t)1 << 30) || K <= 0 || pad < 0 || dil <= 0) fail(NC_EINVAL, "bad depthwise shape");
+        op_set_device(device_index);
+        DwConvLayer L;
+        L.build(w, bias, C, K, pad, dil);
+        DevBuf dx, dy, dai, dao;
+        const size_t n = (size_t)B * C * T;
+        op_upload(dx, x, n);
+        dy.reserve(n * 4);
+        NC_HIP(hipMemset(dy.p, 0, n * 4));
+        const float* ai = alpha_in ? op_upload(dai, alpha_in, C) : nullptr;
+        const float* ao = alpha_out ? op_upload(dao, alpha_out, C) : nullptr;
+        launch_dwconv(L, dx.as<float>(), ai, ao, dy.as<float>(), B, T, nullptr, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_layer_norm(int device_index, int32_t B, int32_t C, int64_t T, const float* x, const float* gamma, const float* beta, float* y) {
+    return guard([&] {
+        if (!x || !gamma || !beta || !y) fail(NC_EINVAL, "null argument");
+        if (B <= 0 || C <= 0 || T <= 0) fail(NC_EINVAL, "bad LayerNorm shape");
+        op_set_device(device_index);
+        DevBuf dx, dy, dg, db;
+        const size_t n = (size_t)B * C * T;
+        op_upload(dx, x, n); op_upload(dg, gamma, C); op_upload(db, beta, C);
+        dy.reserve(n * 4);
+        NC_HIP(hipMemset(dy.p, 0, n * 4));
+        launch_layernorm_ct(dx.as<float>(), dg.as<float>(), db.as<float>(), dy.as<float>(), B, C, T, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_local_attn(int device_index, int32_t B, int32_t C, int64_t T, int32_t W, const float* qkv, const float* inv_freq, float* y) {
+    return guard([&] {
+        if (!qkv || !inv_freq || !y) fail(NC_EINVAL, "null argument");
+        if (B <= 0 || C <= 0 || T <= 0) fail(NC_EINVAL, "bad attention shape");
+        if (W <= 0 || W > 32 || T % W != 0 || C % 64 != 0) fail(NC_EUNSUPPORTED, "local attention: window %d / dim %d / %lld steps not supported", W, C, (long long)T);
+        op_set_device(device_index);
+        std::vector<float> cs, sn;
+        rotary_tables(inv_freq, W, cs, sn);
+        DevBuf dq, dy, dc, ds;
+        const size_t n = (size_t)B * C * T;
+        op_upload(dq, qkv, 3 * n); op_upload(dc, cs.data(), cs.size()); op_upload(ds, sn.data(), sn.size());
+        dy.reserve(n * 4);
+        NC_HIP(hipMemset(dy.p, 0, n * 4));
+        launch_local_attn(dq.as<float>(), dc.as<float>(), ds.as<float>(), dy.as<float>(), B, C, T, W, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_avg_pool(int device_index, int64_t rows, int64_t T, int32_t s, const float* x, float* y) {
+    return guard([&] {
+        if (!x || !y) fail(NC_EINVAL, "null argument");
+        if (rows <= 0 || T <= 0 || s <= 0 || T / s <= 0) fail(NC_EINVAL, "bad pooling shape");
+        op_set_device(device_index);
+        DevBuf dx, dy;
+        const size_t ny = (size_t)rows * (size_t)(T / s);
+        op_upload(dx, x, (size_t)rows * T);
+        dy.reserve(ny * 4);
+        NC_HIP(hipMemset(dy.p, 0, ny * 4));
+        launch_avg_pool(dx.as<float>(), dy.as<float>(), rows, T, s, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_snac_unit(int device_index, int32_t B, int32_t C, int64_t T, int32_t dil, const float* x, const float* w7, const float* b7,
+                          const float* a1, const float* a2, const float* w1, const float* b1, const float* alpha_next, int32_t fused,
+                          float* y) {
+    return guard([&] {
+        if (!x || !w7 || !a1 || !a2 || !w1 || !y) fail(NC_EINVAL, "null argument");
+        if (B <= 0 || C <= 0 || T <= 0 || T > ((int64_t)1 << 30) || dil <= 0) fail(NC_EINVAL, "bad arguments");
+        op_set_device(device_index);
+        DevBuf dx, dh, dy, d1, d2, dn;
+        const size_t n = (size_t)B * C * T;
+        op_upload(dx, x, n);
+        dy.reserve(n * 4);
+        NC_HIP(hipMemset(dy.p, 0, n * 4));
+        const float* an = alpha_next ? op_upload(dn, alpha_next, C) : nullptr;
+        if (fused) {
+            if (!SnacFusedUnit::supported(C, 7, dil)) fail(NC_EUNSUPPORTED, "no one-launch SNAC unit for %d channels at dilation %d", C, dil);
+            SnacFusedUnit fu;
+            fu.build(C, dil, w7, b7, a1, a2, w1, b1);
+            if (!fu.usable(dx.as<float>(), dy.as<float>(), T, B, /*any_cols=*/true))   // the caller chose this form: no column threshold
+                fail(NC_EUNSUPPORTED, "the one-launch SNAC unit does not serve this call: %lld steps (it wants a multiple of 4, >= 256, C * T < 2^30), or NC_SNAC_NO_FUSE is set", (long long)T);
+            hipDeviceProp_t prop;
+            NC_HIP(hipGetDeviceProperties(&prop, device_index));
+            fu.launch(dx.as<float>(), an, dy.as<float>(), B, T, prop.multiProcessorCount, nullptr, nullptr);
+        } else {
+            DwConvLayer dw;
+            dw.build(w7, b7, C, 7, 3 * dil, dil);
+            ConvLayer c1;
+            struct Release { ConvLayer& l; ~Release() { l.release_all(); } } release_c1{c1};   // also when a launch below throws
+            c1.build(w1, b1, C, C, 1, 1, 0, 1, 0, false);
+            dh.reserve(n * 4);
+            launch_dwconv(dw, dx.as<float>(), op_upload(d1, a1, C), op_upload(d2, a2, C), dh.as<float>(), B, T, nullptr, nullptr);
+            ConvIO io{};
+            io.x = dh.as<float>(); io.x_bstride = (int64_t)C * T; io.x_cstride = T; io.x_len = (int32_t)T; io.Tin = T;
+            io.res = dx.as<float>(); io.alpha_out = an;
+            io.y = dy.as<float>(); io.y_bstride = (int64_t)C * T; io.y_cstride = T;
+            launch_conv(c1, io, B, nullptr, nullptr);
+            NC_HIP(hipDeviceSynchronize());
+        }
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 }  // extern "C"

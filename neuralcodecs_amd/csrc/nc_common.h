@@ -48,6 +48,9 @@ bool env_present(const char* name);               // kind 'p': set at all
 long env_int(const char* name, long dflt);        // kind 'i'
 const char* env_str(const char* name);            // kind 's': nullptr when unset
 const char* env_switch_table();                   // "NAME\tkind\twhat it does\n" per switch
+// NC_LAUNCH_LOG=<path>: the one log file of the process (nullptr when unset).  One line per launch, flushed: "conv_mfma ..." from the
+// convolution template (tools/pmc_classes.py), "elem <kernel name>" from the launchers that choose among kernel forms (the op tests).
+FILE* launch_log();
 
 // Opt a kernel into > 64 KB of dynamic LDS on the CURRENT device.  The attribute is per (device, function): the cache is keyed on
 // both and guarded, so models on different GPUs (and host threads calling in concurrently) each get their opt-in.

@@ -18,7 +18,7 @@ struct SnacFusedUnit {
     DevBuf w1, tab, b1;
     static bool supported(int C, int K, int dil);
     void build(int C, int dil, const float* w7, const float* b7, const float* a1, const float* a2, const float* w1_dense, const float* b1);
-    bool usable(const float* x, const float* y, int64_t T, int B) const;
+    bool usable(const float* x, const float* y, int64_t T, int B, bool any_cols = false) const;   // any_cols: skip NC_SNAC_FUSE_MIN_COLS (op hook)
     void launch(const float* x, const float* alpha_next, float* y, int B, int64_t T, int cu_count, hipStream_t s, Profiler* prof) const;
 };
 void launch_dwconv(const DwConvLayer& L, const float* x, const float* alpha_in, const float* alpha_out, float* y, int B, int64_t T,
@@ -30,6 +30,8 @@ void launch_layernorm_ct(const float* x, const float* gamma, const float* beta, 
                          Profiler* prof = nullptr);
 void launch_local_attn(const float* qkv, const float* cs, const float* sn, float* out, int B, int C, int64_t T, int W, hipStream_t st,
                        Profiler* prof = nullptr);
+// cos / sin tables [W][64] of the rotary embedding from the checkpoint's inv_freq [32] (nc_snac.hip; host side)
+void rotary_tables(const float* inv_freq, int W, std::vector<float>& cs, std::vector<float>& sn);
 void launch_randn(float* out, int64_t n, uint64_t seed, hipStream_t st);
 
 }  // namespace nc

@@ -13,6 +13,14 @@
 
 namespace nc {
 
+// which kernel form a launcher chose, for tests/test_elem_ops_gpu.py (NC_LAUNCH_LOG)
+static void log_form(const char* name) {
+    if (FILE* lf = launch_log()) {
+        std::fprintf(lf, "elem %s\n", name);
+        std::fflush(lf);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- depthwise conv
 // y[b,c,t] = (chain_k w[c,k] * snake_in(x[b,c,t + k*dil - pad])) + bias[c]  [-> snake_out]
 // One block = one (clip, channel) row segment of DW_TT outputs; the activated input window lives in LDS.
@@ -164,6 +172,7 @@ void launch_dwconv(const DwConvLayer& L, const float* x, const float* alpha_in, 
             dim3 grid((unsigned)((T + DW_TT - 1) / DW_TT), (unsigned)L.C, (unsigned)B);
             if (prof && prof->on) prof->begin(s, NC_KC_DWCONV, 2.0 * L.K * L.C * (double)T * B, 8.0 * L.C * (double)T * B);
             const float* bp = L.has_bias ? L.bias.as<float>() : nullptr;
+            log_form(L.dil == 1 ? "dwconv_vec_kernel<1>" : L.dil == 3 ? "dwconv_vec_kernel<3>" : "dwconv_vec_kernel<9>");
             if (L.dil == 1) hipLaunchKernelGGL(dwconv_vec_kernel<1>, grid, dim3(256), 0, s, x, L.w.as<float>(), bp, alpha_in, alpha_out, y, L.C, (int)T);
             else if (L.dil == 3) hipLaunchKernelGGL(dwconv_vec_kernel<3>, grid, dim3(256), 0, s, x, L.w.as<float>(), bp, alpha_in, alpha_out, y, L.C, (int)T);
             else hipLaunchKernelGGL(dwconv_vec_kernel<9>, grid, dim3(256), 0, s, x, L.w.as<float>(), bp, alpha_in, alpha_out, y, L.C, (int)T);
@@ -173,6 +182,7 @@ void launch_dwconv(const DwConvLayer& L, const float* x, const float* alpha_in, 
         }
     }
     const size_t lds = sizeof(float) * (DW_TT + (L.K - 1) * L.dil);
+    log_form("dwconv_kernel");
     dim3 grid((unsigned)((T + DW_TT - 1) / DW_TT), (unsigned)L.C, (unsigned)B);
     if (prof && prof->on) prof->begin(s, NC_KC_DWCONV, 2.0 * L.K * L.C * (double)T * B, 8.0 * L.C * (double)T * B);
     hipLaunchKernelGGL(dwconv_kernel, grid, dim3(256), lds, s, x, L.w.as<float>(), L.has_bias ? L.bias.as<float>() : nullptr,
@@ -332,6 +342,7 @@ void launch_layernorm_ct(const float* x, const float* gamma, const float* beta, 
     if ((tt == 8 || tt == 16) && (size_t)C * tt * 4 + 2 * tt * 4 <= 96 * 1024) {
         const size_t lds = (size_t)C * tt * 4 + 2 * tt * 4;
         const dim3 grid((unsigned)((T + tt - 1) / tt), (unsigned)B);
+        log_form(tt == 16 ? "layernorm_tile_kernel<16>" : "layernorm_tile_kernel<8>");
         if (tt == 16) {
             ensure_dynamic_lds((const void*)layernorm_tile_kernel<16>, lds);
             hipLaunchKernelGGL(layernorm_tile_kernel<16>, grid, dim3(256), lds, st, x, gamma, beta, y, C, T);
@@ -342,6 +353,7 @@ void launch_layernorm_ct(const float* x, const float* gamma, const float* beta, 
         NC_HIP(hipGetLastError());
         return;
     }
+    log_form("layernorm_ct_kernel");
     hipLaunchKernelGGL(layernorm_ct_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, x, gamma, beta, y, B, C, T);
     NC_HIP(hipGetLastError());
 }
@@ -520,10 +532,12 @@ void launch_local_attn(const float* qkv, const float* cs, const float* sn, float
     ProfScope ps(prof, st, NC_KC_ATTN, 4.0 * W * C * (double)T * B, 16.0 * C * (double)T * B);
     static const bool no_mfma = env_flag("NC_ATTN_NO_MFMA");
     if (W == 32 && !no_mfma && T % 4 == 0) {
+        log_form("local_attn_mfma_kernel");
         hipLaunchKernelGGL(local_attn_mfma_kernel, dim3((unsigned)(T / W), (unsigned)(C / 64), (unsigned)B), dim3(64), 0, st, qkv, cs, sn, out, C, T);
         NC_HIP(hipGetLastError());
         return;
     }
+    log_form("local_attn_kernel");
     hipLaunchKernelGGL(local_attn_kernel, dim3((unsigned)(T / W), (unsigned)(C / 64), (unsigned)B), dim3(64), 0, st, qkv, cs, sn, out,
                        C, T, W);
     NC_HIP(hipGetLastError());

@@ -28,6 +28,17 @@ void fold_weight_norm_snac(const float* v, const float* g, int64_t d0, int64_t i
     }
 }
 
+// rotary tables [W][64] (SinusoidalEmbedding.cs:67-80, RotaryEmbedding.cs:46-68): f = fl32(pos*inv_freq), rounded binary64 cos/sin
+void rotary_tables(const float* inv_freq, int W, std::vector<float>& cs, std::vector<float>& sn) {
+    cs.assign((size_t)W * 64, 0.0f); sn.assign((size_t)W * 64, 0.0f);
+    for (int i = 0; i < W; ++i)
+        for (int j = 0; j < 64; ++j) {
+            const float f = (float)i * inv_freq[j & 31];
+            cs[(size_t)i * 64 + j] = (float)std::cos((double)f);
+            sn[(size_t)i * 64 + j] = (float)std::sin((double)f);
+        }
+}
+
 static const char* G0 = ".parametrizations.weight.original0";
 static const char* G1 = ".parametrizations.weight.original1";
 
@@ -122,16 +133,8 @@ void SnacModel::load_mha(const Blob& b, const std::string& p, Mha& m, int C) {
     m.qkv.build(static_cast<const float*>(wq.data), nullptr, C, 3 * C, 1, 1, 0, 1, 0, false);   // Linear(C -> 3C, no bias)
     m.out.kclass = NC_KC_CONV_K1;
     m.out.build(static_cast<const float*>(wo.data), nullptr, C, C, 1, 1, 0, 1, 0, false);       // Linear(C -> C, no bias)
-    // rotary tables (SinusoidalEmbedding.cs:67-80, RotaryEmbedding.cs:46-68): f = fl32(pos*inv_freq), rounded binary64 cos/sin
-    const int W = cfg.attn_window_size;
-    const float* invf = static_cast<const float*>(fr.data);
-    std::vector<float> cs((size_t)W * 64), sn((size_t)W * 64);
-    for (int i = 0; i < W; ++i)
-        for (int j = 0; j < 64; ++j) {
-            const float f = (float)i * invf[j & 31];
-            cs[(size_t)i * 64 + j] = (float)std::cos((double)f);
-            sn[(size_t)i * 64 + j] = (float)std::sin((double)f);
-        }
+    std::vector<float> cs, sn;
+    rotary_tables(static_cast<const float*>(fr.data), cfg.attn_window_size, cs, sn);
     upload(m.cs, cs.data(), cs.size());
     upload(m.sn, sn.data(), sn.size());
 }

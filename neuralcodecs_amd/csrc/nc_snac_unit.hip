@@ -268,13 +268,13 @@ void SnacFusedUnit::build(int C_, int dil_, const float* w7, const float* b7, co
     ready = true;
 }
 
-bool SnacFusedUnit::usable(const float* x, const float* y, int64_t T, int B) const {
+bool SnacFusedUnit::usable(const float* x, const float* y, int64_t T, int B, bool any_cols) const {
     static const bool off = env_flag("NC_SNAC_NO_FUSE");
     static const int64_t min_cols = env_int("NC_SNAC_FUSE_MIN_COLS", 65536);
     // the epilogue addresses a clip's [C][T] block with 32-bit BYTE offsets off a uniform 64-bit base: C * T floats must stay below 2^30
     // (the bound had been on T alone -- a 254 s clip at C = 96 wrapped); longer clips take the two-launch path
     static const int64_t max_elems = std::min<int64_t>(env_int("NC_SNAC_FUSE_MAX_ELEMS", 1 << 30), (int64_t)1 << 30);
-    return ready && !off && (T & 3) == 0 && T >= 256 && (int64_t)B * T >= min_cols && (int64_t)C * T < max_elems &&
+    return ready && !off && (T & 3) == 0 && T >= 256 && (any_cols || (int64_t)B * T >= min_cols) && (int64_t)C * T < max_elems &&
            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
 }
 
@@ -298,6 +298,10 @@ void SnacFusedUnit::launch(const float* x, const float* alpha_next, float* y, in
         a.trace = tbuf.as<unsigned long long>();
     }
     const bool snk = alpha_next != nullptr;
+    if (FILE* lf = launch_log()) {
+        std::fprintf(lf, "elem snac_unit_kernel<%d,%d,%d>\n", C / 32, dil, snk ? 1 : 0);
+        std::fflush(lf);
+    }
     auto pick = [&](auto tm, auto dl) {
         constexpr int TMv = decltype(tm)::value, DLv = decltype(dl)::value;
         if (snk) go(snac_unit_kernel<TMv, DLv, true>, unit_lds<TMv>(DLv)); else go(snac_unit_kernel<TMv, DLv, false>, unit_lds<TMv>(DLv));

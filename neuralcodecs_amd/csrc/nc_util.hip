@@ -102,6 +102,10 @@ bool env_flag(const char* name) { const char* v = std::getenv(env_row(name, 'b')
 bool env_present(const char* name) { return std::getenv(env_row(name, 'p').name) != nullptr; }
 long env_int(const char* name, long dflt) { const char* v = std::getenv(env_row(name, 'i').name); return v ? atol(v) : dflt; }
 const char* env_str(const char* name) { const char* v = std::getenv(env_row(name, 's').name); return v && v[0] ? v : nullptr; }
+FILE* launch_log() {
+    static FILE* lf = [] { const char* p = env_str("NC_LAUNCH_LOG"); return p ? std::fopen(p, "w") : (FILE*)nullptr; }();
+    return lf;
+}
 const char* env_switch_table() {
     static const std::string text = [] {
         std::string t;

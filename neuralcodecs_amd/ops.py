@@ -70,3 +70,60 @@ def fold_weight_norm(v, g):
     w = np.empty_like(v)
     _lib.check(_lib.lib().nc_op_fold_weight_norm(v.ctypes.data, g.ctypes.data, v.shape[0], int(np.prod(v.shape[1:])), w.ctypes.data))
     return w
+
+
+def _f(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def dwconv1d(x, weight, bias=None, pad=0, dil=1, alpha_in=None, alpha_out=None, device_index=0):
+    """Depthwise convolution on x [B,C,T] with weight [C,K] (or [C,1,K]): the first T outputs over the zero-extended rows."""
+    x = _f(x); w = _f(weight).reshape(x.shape[1], -1)
+    B, Cc, T = x.shape
+    b, ai, ao = _f(bias), _f(alpha_in), _f(alpha_out)
+    y = np.empty_like(x)
+    _lib.check(_lib.lib().nc_op_dwconv1d(device_index, B, Cc, T, w.shape[1], pad, dil, x.ctypes.data, w.ctypes.data, _p(b), _p(ai), _p(ao),
+                                         y.ctypes.data))
+    return y
+
+
+def layer_norm(x, gamma, beta, device_index=0):
+    """LayerNorm over the channel axis of x [B,C,T] (eps 1e-5)."""
+    x, g, b = _f(x), _f(gamma), _f(beta)
+    B, Cc, T = x.shape
+    assert g.size == Cc and b.size == Cc
+    y = np.empty_like(x)
+    _lib.check(_lib.lib().nc_op_layer_norm(device_index, B, Cc, T, x.ctypes.data, g.ctypes.data, b.ctypes.data, y.ctypes.data))
+    return y
+
+
+def local_attn(qkv, window, inv_freq, device_index=0):
+    """Windowed rotary attention on qkv [B,3C,T] -> [B,C,T]; inv_freq [32] is the checkpoint's rel_pos.inv_freq buffer."""
+    qkv = _f(qkv); fr = _f(inv_freq)
+    B, C3, T = qkv.shape
+    assert C3 % 3 == 0 and fr.size == 32
+    y = np.empty((B, C3 // 3, T), np.float32)
+    _lib.check(_lib.lib().nc_op_local_attn(device_index, B, C3 // 3, T, int(window), qkv.ctypes.data, _p(fr), y.ctypes.data))
+    return y
+
+
+def avg_pool(x, s, device_index=0):
+    """avg_pool1d(s) on x [rows,T] -> [rows,T // s]."""
+    x = _f(x)
+    rows, T = x.shape
+    y = np.empty((rows, T // s), np.float32)
+    _lib.check(_lib.lib().nc_op_avg_pool(device_index, rows, T, int(s), x.ctypes.data, y.ctypes.data))
+    return y
+
+
+def snac_unit(x, w7, b7, a1, a2, w1, b1=None, alpha_next=None, dil=1, fused=True, device_index=0):
+    """One depthwise SNAC ResidualUnit on x [B,C,T]: w7 [C,7] (or [C,1,7]), w1 [C,C] (or [C,C,1]); fused=True is the one-launch kernel
+    (NcError status NC_EUNSUPPORTED where it does not serve the shape), fused=False the two-launch path."""
+    x = _f(x)
+    B, Cc, T = x.shape
+    w7 = _f(w7).reshape(Cc, 7); w1 = _f(w1).reshape(Cc, Cc)
+    b7, a1, a2, b1, an = _f(b7), _f(a1), _f(a2), _f(b1), _f(alpha_next)
+    y = np.empty_like(x)
+    _lib.check(_lib.lib().nc_op_snac_unit(device_index, B, Cc, T, dil, x.ctypes.data, w7.ctypes.data, _p(b7), a1.ctypes.data, a2.ctypes.data,
+                                          w1.ctypes.data, _p(b1), _p(an), 1 if fused else 0, y.ctypes.data))
+    return y

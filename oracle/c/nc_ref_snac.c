@@ -153,18 +153,11 @@ static float* res_unit(ref_snac* m, const char* p, float* x, int64_t B, int C, i
     return y;
 }
 
-/* LocalMHA.cs:78-115 on x [B,C,T]; returns a new buffer and frees x */
-static float* local_mha(ref_snac* m, const char* p, float* x, int64_t B, int C, int64_t T) {
-    char nm[320];
-    const int W = m->cfg.attn_window, H = C / 64, NW = (int)(T / W);
-    snprintf(nm, sizeof nm, "%s.norm.weight", p); const float* gam = get_f(m, nm, C);
-    snprintf(nm, sizeof nm, "%s.norm.bias", p); const float* bet = get_f(m, nm, C);
-    snprintf(nm, sizeof nm, "%s.to_qkv.weight", p); const float* wqkv = get_f(m, nm, (int64_t)3 * C * C);
-    snprintf(nm, sizeof nm, "%s.to_out.weight", p); const float* wout = get_f(m, nm, (int64_t)C * C);
-    snprintf(nm, sizeof nm, "%s.rel_pos.inv_freq", p); const float* invf = get_f(m, nm, 32);
-    if (!gam || !bet || !wqkv || !wout || !invf) return x;
-    float* xn = (float*)malloc(sizeof(float) * B * C * T);
-    /* LayerNorm over channels, kept in [B,C,T] layout */
+/* ---- the pieces of LocalMHA and of the quantizer, exported so that the op tests can hold one kernel at a time to them; the model
+ *      functions below are compositions of exactly these ------------------------------------------------------------------------ */
+
+/* LayerNorm over the channels of x [B,C,T], kept in [B,C,T] layout (LocalMHA.cs:85) */
+REF_API void ref_layer_norm_ct(const float* x, int64_t B, int C, int64_t T, const float* gam, const float* bet, float* xn) {
 #pragma omp parallel for collapse(2) schedule(static)
     for (int64_t b = 0; b < B; b++)
         for (int64_t t = 0; t < T; t++) {
@@ -178,9 +171,13 @@ static float* local_mha(ref_snac* m, const char* p, float* x, int64_t B, int C, 
             const float muf = (float)mu;
             for (int c = 0; c < C; c++) xn[(b * C + c) * T + t] = ((xp[(int64_t)c * T] - muf) * r) * gam[c] + bet[c];
         }
-    /* qkv = Linear(C -> 3C, no bias) == 1x1 conv with weight [3C, C, 1] */
-    float* qkv = (float*)malloc(sizeof(float) * B * 3 * C * T);
-    ref_conv1d(xn, B, C, T, wqkv, NULL, 3 * C, 1, 1, 0, 1, 1, NULL, qkv, T);
+}
+
+/* Windowed rotary attention (LocalMHA.cs:84-113) on qkv [B,3C,T] (channel = part*C + head*64 + d) -> att [B,C,T]; window W <= 32,
+ * T a multiple of W, inv_freq [32] (SinusoidalEmbedding.cs:44-47).  Returns -1 on a window it does not serve. */
+REF_API int ref_local_attn(const float* qkv, int64_t B, int C, int64_t T, int W, const float* invf, float* att) {
+    const int H = C / 64, NW = (int)(T / W);
+    if (W <= 0 || W > 32 || T % W != 0 || C % 64 != 0) return -1; /* window sizes above 32 are not on the path */
     /* rotary tables [W][64] */
     float* ct = (float*)malloc(sizeof(float) * W * 64);
     float* st = (float*)malloc(sizeof(float) * W * 64);
@@ -190,13 +187,11 @@ static float* local_mha(ref_snac* m, const char* p, float* x, int64_t B, int C, 
             ct[i * 64 + j] = (float)cos((double)f);
             st[i * 64 + j] = (float)sin((double)f);
         }
-    float* att = xn; /* reuse as the attention output [B,C,T] (channel = head*64 + d) */
 #pragma omp parallel for collapse(3) schedule(static)
     for (int64_t b = 0; b < B; b++)
         for (int h = 0; h < H; h++)
             for (int wdx = 0; wdx < NW; wdx++) {
                 float q[32][64], k[32][64], v[32][64];
-                if (W > 32) continue; /* window sizes above 32 are not on the path */
                 for (int i = 0; i < W; i++)
                     for (int d = 0; d < 64; d++) {
                         const int64_t t = (int64_t)wdx * W + i;
@@ -226,7 +221,39 @@ static float* local_mha(ref_snac* m, const char* p, float* x, int64_t B, int C, 
                     }
                 }
             }
-    free(qkv); free(ct); free(st);
+    free(ct); free(st);
+    return 0;
+}
+
+/* avg_pool1d(s) over rows of T steps -> T / s steps (VectorQuantizer.cs:88): sequential sum, one division */
+REF_API void ref_avg_pool(const float* x, int64_t rows, int64_t T, int s, float* y) {
+    const int64_t Ts = T / s;
+    for (int64_t r = 0; r < rows; r++)
+        for (int64_t t = 0; t < Ts; t++) {
+            float a = x[r * T + t * s];
+            for (int j = 1; j < s; j++) a = a + x[r * T + t * s + j];
+            y[r * Ts + t] = a / (float)s;
+        }
+}
+
+/* LocalMHA.cs:78-115 on x [B,C,T]; returns a new buffer and frees x */
+static float* local_mha(ref_snac* m, const char* p, float* x, int64_t B, int C, int64_t T) {
+    char nm[320];
+    const int W = m->cfg.attn_window;
+    snprintf(nm, sizeof nm, "%s.norm.weight", p); const float* gam = get_f(m, nm, C);
+    snprintf(nm, sizeof nm, "%s.norm.bias", p); const float* bet = get_f(m, nm, C);
+    snprintf(nm, sizeof nm, "%s.to_qkv.weight", p); const float* wqkv = get_f(m, nm, (int64_t)3 * C * C);
+    snprintf(nm, sizeof nm, "%s.to_out.weight", p); const float* wout = get_f(m, nm, (int64_t)C * C);
+    snprintf(nm, sizeof nm, "%s.rel_pos.inv_freq", p); const float* invf = get_f(m, nm, 32);
+    if (!gam || !bet || !wqkv || !wout || !invf) return x;
+    float* xn = (float*)malloc(sizeof(float) * B * C * T);
+    ref_layer_norm_ct(x, B, C, T, gam, bet, xn);
+    /* qkv = Linear(C -> 3C, no bias) == 1x1 conv with weight [3C, C, 1] */
+    float* qkv = (float*)malloc(sizeof(float) * B * 3 * C * T);
+    ref_conv1d(xn, B, C, T, wqkv, NULL, 3 * C, 1, 1, 0, 1, 1, NULL, qkv, T);
+    float* att = xn; /* reuse as the attention output [B,C,T] (channel = head*64 + d) */
+    if (ref_local_attn(qkv, B, C, T, W, invf, att) != 0) m->bad = 1;
+    free(qkv);
     /* out = Linear(C -> C, no bias)(att) + residual */
     float* y = (float*)malloc(sizeof(float) * B * C * T);
     ref_conv1d(att, B, C, T, wout, NULL, C, 1, 1, 0, 1, 1, x, y, T);
@@ -285,12 +312,7 @@ REF_API int ref_snac_encode(ref_snac* m, const float* pcm, int64_t B, int64_t T,
         float* pooled = residual;
         if (s > 1) {
             pooled = (float*)malloc(sizeof(float) * B * LD * Ts);
-            for (int64_t r = 0; r < B * LD; r++)
-                for (int64_t t = 0; t < Ts; t++) {
-                    float a = residual[r * Tz + t * s];
-                    for (int j = 1; j < s; j++) a = a + residual[r * Tz + t * s + j];
-                    pooled[r * Ts + t] = a / (float)s;
-                }
+            ref_avg_pool(residual, B * LD, Tz, s, pooled);
         }
         int64_t Lo; int Co;
         snprintf(nm, sizeof nm, "quantizer.quantizers.%d.in_proj", i);

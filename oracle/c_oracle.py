@@ -79,6 +79,10 @@ def lib():
         L.ref_snac_from_codes.argtypes = [C.c_void_p, i64p, C.c_int64, C.c_int64, f32p]
         L.ref_snac_decode.argtypes = [C.c_void_p, f32p, C.c_int64, C.c_int64, C.c_void_p, f32p]
         L.ref_fold_wn_snac.argtypes = [f32p, f32p, C.c_int64, C.c_int64, f32p]
+        L.ref_layer_norm_ct.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, f32p, f32p, f32p]
+        L.ref_local_attn.restype = C.c_int
+        L.ref_local_attn.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, C.c_int, f32p, f32p]
+        L.ref_avg_pool.argtypes = [f32p, C.c_int64, C.c_int64, C.c_int, f32p]
         L.ref_encodec_create.restype = C.c_void_p
         L.ref_encodec_create.argtypes = [C.POINTER(RefEncodecConfig), C.c_char_p, C.c_int64]
         L.ref_encodec_destroy.argtypes = [C.c_void_p]
@@ -148,6 +152,41 @@ def vq_argmin(z_e, codebook):
     idx = np.empty((B, T), np.int64); st = np.empty_like(z_e); bd = np.empty((B, T), np.float32)
     lib().ref_vq_argmin(z_e, B, D, T, cb, cb.shape[0], idx, st, bd.ctypes.data_as(C.c_void_p))
     return idx, st, bd
+
+
+def layer_norm_ct(x, gamma, beta):
+    """LayerNorm over the channel axis of x [B,C,T] (eps 1e-5), the piece LocalMHA is composed of."""
+    x = np.ascontiguousarray(x, np.float32)
+    g = np.ascontiguousarray(gamma, np.float32).reshape(-1); b = np.ascontiguousarray(beta, np.float32).reshape(-1)
+    y = np.empty_like(x)
+    lib().ref_layer_norm_ct(x, x.shape[0], x.shape[1], x.shape[2], g, b, y)
+    return y
+
+
+def rotary_inv_freq():
+    """SinusoidalEmbedding.cs:44-47: 1 / 10000 ** (arange(0, 64, 2) / 64) in binary32 (the buffer the checkpoints carry)."""
+    power = (np.arange(0, 64, 2, dtype=np.float32) / np.float32(64)).astype(np.float32)
+    return (np.float32(1.0) / np.power(np.float32(10000.0), power, dtype=np.float32)).astype(np.float32)
+
+
+def local_attn(qkv, window, inv_freq=None):
+    """Windowed rotary attention on qkv [B,3C,T] -> [B,C,T] (heads of 64, window <= 32, T a multiple of it)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    B, C3, T = qkv.shape
+    f = rotary_inv_freq() if inv_freq is None else np.ascontiguousarray(inv_freq, np.float32).reshape(-1)
+    y = np.empty((B, C3 // 3, T), np.float32)
+    if C3 % 3 or f.size != 32 or lib().ref_local_attn(qkv, B, C3 // 3, T, int(window), f, y) != 0:
+        raise ValueError(f"local_attn: window {window} / shape {qkv.shape} not served")
+    return y
+
+
+def avg_pool(x, s):
+    """avg_pool1d(s) over the last axis: x [rows, T] -> [rows, T // s]."""
+    x = np.ascontiguousarray(x, np.float32)
+    rows, T = x.shape
+    y = np.empty((rows, T // s), np.float32)
+    lib().ref_avg_pool(x, rows, T, int(s), y)
+    return y
 
 
 class RefDAC:

@@ -34,7 +34,7 @@ def load(path_csv, path_log):
         d = int(r["Dispatch_Id"])
         e = rows.setdefault(d, [r["Kernel_Name"], int(r["Grid_Size"]), {}, int(r["Start_Timestamp"]), int(r["End_Timestamp"])])
         e[2][r["Counter_Name"]] = e[2].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
-    log = [l.split() for l in open(path_log)] if path_log and os.path.exists(path_log) else []
+    log = [l.split() for l in open(path_log) if l.startswith("conv_mfma ")] if path_log and os.path.exists(path_log) else []   # ("elem ..." lines: other launchers)
     li = 0
     out = []
     for d in sorted(rows):
