@@ -25,15 +25,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int N, class F, int... I>
-__device__ __forceinline__ void nc_static_for_1x1_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void nc_static_for_1x1(F&& f) {
-    nc_static_for_1x1_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
 // Waves per SIMD the register budget is held to (the layers this kernel serves are short reductions: occupancy hides their
 // memory latency), matching the workgroups-per-CU table of the launch-time tile choice.
 constexpr int conv1x1_occupancy(int TM) { return TM == 1 ? 6 : TM == 2 ? 5 : 3; }
@@ -67,11 +58,7 @@ __global__ __launch_bounds__(256, conv1x1_occupancy(TM)) void conv1x1_kernel(con
 
     const int nwg = gridDim.x;
     const int bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     const int co_in = __builtin_amdgcn_readfirstlane(lin % p.co_group);   // row tiles in groups: see conv_mfma_kernel's tile map
     lin /= p.co_group;
     const int t_tile = __builtin_amdgcn_readfirstlane(lin % p.n_t_tiles);
@@ -260,7 +247,7 @@ __global__ __launch_bounds__(256, conv1x1_occupancy(TM)) void conv1x1_kernel(con
             }
         };
         if constexpr (RES) load_quad(0, rs[0]);
-        nc_static_for_1x1<4 * TM>([&](auto qt) __attribute__((always_inline)) {
+        nc_static_for<4 * TM>([&](auto qt) __attribute__((always_inline)) {
             constexpr int q = decltype(qt)::value, i = q >> 2, rq = q & 3;
             if constexpr (RES && q + 1 < 4 * TM) {
                 // the reads of quad q+1 wait (data dependence through the offset) for the arithmetic of quad q-1: two quads in

@@ -13,41 +13,10 @@
 // i.e. each half needs the CENTRE tap of the other half's channel once: one v_permlane32_swap per value.  Reflect padding touches only
 // the first / last column of a clip and is an in-lane fix (x[-1] = x[1], x[T] = x[T-2]; T is even, so both live in the same lane).
 // Only the weight tile (shared by the four waves) goes through LDS, double-buffered, one barrier per 16 input channels.
-#include <type_traits>
-#include <utility>
-
 #include "nc_conv.h"
-#include "nc_frag.h"
-#include "nc_gn.h"
-#include "nc_math.h"
+#include "nc_stream.h"
 
 namespace nc {
-
-typedef float c3_f32x16 __attribute__((ext_vector_type(16)));
-typedef float c3_f32x4 __attribute__((ext_vector_type(4)));
-typedef float c3_f32x2 __attribute__((ext_vector_type(2)));
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void c3_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void c3_static_for(F&& f) {
-    c3_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-// lane i <- lane i-1 / lane i+1 of the wavefront (DPP wave_shr:1 / wave_shl:1; the lanes shifted in at the ends are fixed by the caller)
-__device__ __forceinline__ float c3_from_left(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float c3_from_right(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-// the value the same lane of the OTHER half holds
-__device__ __forceinline__ float c3_other_half(float v, int hi) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(hi ? r[0] : r[1]);
-}
 
 constexpr int conv3s_occupancy(int TM) { return TM == 1 ? 5 : TM == 2 ? 4 : 2; }
 
@@ -68,11 +37,7 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     const int co_in = __builtin_amdgcn_readfirstlane(lin % p.co_group);
     lin /= p.co_group;
     const int t_tile = __builtin_amdgcn_readfirstlane(lin % p.n_t_tiles);
@@ -96,11 +61,11 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
     const float* const xb = p.x + (int64_t)b * p.x_bstride;
     const unsigned x_lane_off = (unsigned)hi * x_cstride + (unsigned)colc;
     const unsigned h_lane_off = (unsigned)hi * x_cstride + (unsigned)hcol;
-    const c3_f32x4* const wbase = reinterpret_cast<const c3_f32x4*>(p.w + (int64_t)co_tile * n_cb * A_FLOATS);
+    const f32x4_t* const wbase = reinterpret_cast<const f32x4_t*>(p.w + (int64_t)co_tile * n_cb * A_FLOATS);
     const bool first_col = col == 0, last_col = col + TN == T;    // reflect: x[-1] = x[1] (this lane's second value), x[T] = x[T-2] (its first)
     const bool lane_first = l31 == 0, lane_last = l31 == 31;
 
-    c3_f32x16 acc[TM][TN];
+    f32x16_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -109,13 +74,13 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
     // ring of channel pairs: pair g = channels 2g (lanes 0-31) and 2g+1 (lanes 32-63); rows past Cin meet zero weights
-    c3_f32x2 bq[PF];
+    f32x2_t bq[PF];
     float hq[PF];
     const int last_pair = Cin / 2 - 1;
-    auto load_pair = [&](int g, c3_f32x2& v, float& h) __attribute__((always_inline)) {
+    auto load_pair = [&](int g, f32x2_t& v, float& h) __attribute__((always_inline)) {
         const float* row = xb + (size_t)(2 * min(g, last_pair)) * x_cstride;
         if constexpr (XV2) {
-            v = *reinterpret_cast<const c3_f32x2*>(row + x_lane_off);
+            v = *reinterpret_cast<const f32x2_t*>(row + x_lane_off);
         } else {
             v[0] = row[x_lane_off];
             v[1] = row[x_lane_off + 1];
@@ -125,11 +90,11 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
 #pragma unroll
     for (int u = 0; u < PF; ++u) load_pair(u, bq[u], hq[u]);
 
-    c3_f32x4 ra[NA];
+    f32x4_t ra[NA];
 #pragma unroll
     for (int n = 0; n < NA; ++n) {
         const int idx = tid + 256 * n;
-        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<c3_f32x4*>(As[0])[idx] = wbase[idx];
+        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[0])[idx] = wbase[idx];
     }
     __syncthreads();
 
@@ -143,7 +108,7 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
         const int cur = cb & 1;
         const bool more = cb + 1 < n_cb;
         if (more) {
-            const c3_f32x4* src = wbase + (size_t)(cb + 1) * A_VEC;
+            const f32x4_t* src = wbase + (size_t)(cb + 1) * A_VEC;
 #pragma unroll
             for (int n = 0; n < NA; ++n) {
                 const unsigned idx = (unsigned)(tid + 256 * n);
@@ -151,21 +116,21 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
             }
         }
         const float* Ac = As[cur] + hi * BM + nc_a_lane_off<TM>(l31);
-        c3_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
+        nc_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
             constexpr int pr = decltype(pt)::value;           // channel pair within the block
             const int g = cb * (CB / 2) + pr;
             const float2 gb = (in_mode & 1) ? Gt[2 * g + hi] : make_float2(1.0f, 0.0f);
-            const c3_f32x2 raw = bq[pr % PF];
+            const f32x2_t raw = bq[pr % PF];
             const float hraw = hq[pr % PF];
             load_pair(g + PF, bq[pr % PF], hq[pr % PF]);     // unconditional (clamped)
             const float a = act(raw[0], gb), bb = act(raw[1], gb), hv = act(hraw, gb);
             // neighbours: column col-1 = the left lane's second value (the span's halo for its first lane), col+2 = the right lane's first
-            float aL = c3_from_left(bb), bR = c3_from_right(a);
+            float aL = nc_lane_from_left(bb), bR = nc_lane_from_right(a);
             aL = lane_first ? hv : aL;
             bR = lane_last ? hv : bR;
             aL = first_col ? bb : aL;                         // reflect pad (SConv1d.cs:258-274): x[-1] = x[1]
             bR = last_col ? a : bR;                           //                                    x[T]  = x[T-2]
-            const float ax = c3_other_half(a, hi), bx = c3_other_half(bb, hi);
+            const float ax = nc_other_half(a, hi), bx = nc_other_half(bb, hi);
             // step 0: (c0,k0 | c0,k1)   step 1: (c0,k2 | c1,k0)   step 2: (c1,k1 | c1,k2); per output column j: taps (L, C, R)
             const float s0[2] = {hi ? ax : aL, hi ? bx : a};
             const float s1[2] = {hi ? aL : bb, hi ? a : bR};
@@ -194,7 +159,7 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
 #pragma unroll
             for (int n = 0; n < NA; ++n) {
                 const int idx = tid + 256 * n;
-                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<c3_f32x4*>(As[cur ^ 1])[idx] = ra[n];
+                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[cur ^ 1])[idx] = ra[n];
             }
         }
         __syncthreads();
@@ -244,8 +209,8 @@ __global__ __launch_bounds__(256, conv3s_occupancy(TM)) void conv3_stream_kernel
             const int R = i * 32 + (r & 3) + 8 * (r >> 2);
             if (R >= rows_left) continue;
             const float bias = Ep[R + 4 * hi];
-            const c3_f32x2 v = {acc[i][0][r] + bias, acc[i][1][r] + bias};
-            *reinterpret_cast<c3_f32x2*>(yt + (size_t)R * cstride) = v;
+            const f32x2_t v = {acc[i][0][r] + bias, acc[i][1][r] + bias};
+            *reinterpret_cast<f32x2_t*>(yt + (size_t)R * cstride) = v;
         }
 }
 

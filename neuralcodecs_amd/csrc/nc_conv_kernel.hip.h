@@ -24,15 +24,6 @@ namespace nc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int N, class F, int... I>
-__device__ __forceinline__ void nc_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-// f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{}), in order
-template <int N, class F>
-__device__ __forceinline__ void nc_static_for(F&& f) {
-    nc_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
 // a flag that is either a compile-time constant (std::true_type / std::false_type) or this run-time value
 struct nc_rt_flag {
     bool v;
@@ -133,11 +124,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     // one XCD share a weight panel in that XCD's L2.
     const int nwg = gridDim.x;
     const int bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     // (integer division runs on the vector ALU: hand the wave-uniform results back to scalar registers)
     // Polyphase (transposed) launches: the stride phases of one output tile are adjacent in the order, so they run together on
     // one XCD -- their interleaved 4-byte stores (every stride-th sample of the same lines) merge in that L2 instead of each

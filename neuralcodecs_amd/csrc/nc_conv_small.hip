@@ -21,21 +21,13 @@
 #include <vector>
 
 #include "nc_conv.h"
+#include "nc_frag.h"
 #include "nc_gn.h"
 #include "nc_math.h"
 
 namespace nc {
 
 typedef float small_f32x4 __attribute__((ext_vector_type(4)));
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void nc_static_for_small_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void nc_static_for_small(F&& f) {
-    nc_static_for_small_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
 
 constexpr int SMALL_CB = 8;    // input channels per LDS block
 constexpr int SMALL_PF = 12;   // weight groups (4 matrix-core steps each) in flight per wave
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const ConvSmallArgs a) 
     float bc[4], bn[4];
     read_group(bc);
     for (int gbase = 0; gbase < groups; gbase += SMALL_PF) {
-        nc_static_for_small<SMALL_PF>([&](auto it) __attribute__((always_inline)) {
+        nc_static_for<SMALL_PF>([&](auto it) __attribute__((always_inline)) {
             constexpr int i = decltype(it)::value;
             if (gbase + i < groups) {                                // (wave-uniform)
                 const small_f32x4 wv = ring[i];
@@ -270,7 +262,7 @@ __global__ __launch_bounds__(256) void conv_small_unrolled_kernel(const ConvSmal
     for (int c = 0; c < TN; ++c) acc[c] = small_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int off0 = col * a.stride + kq * dil, cts = 16 * a.stride;   // cts: window offset between adjacent column tiles
     for (int cb0 = 0; cb0 < n_blocks; cb0 += NB) {
-        nc_static_for_small<NB>([&](auto bt) __attribute__((always_inline)) {
+        nc_static_for<NB>([&](auto bt) __attribute__((always_inline)) {
             constexpr int nb = decltype(bt)::value;
             const int cbk = cb0 + nb;
             const float* xc = xs + (cbk & 1) * n_slots;
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(256) void conv_small_unrolled_kernel(const ConvSmal
                 }
             };
             read_group(bv[0]);
-            nc_static_for_small<GPB>([&](auto gt) __attribute__((always_inline)) {
+            nc_static_for<GPB>([&](auto gt) __attribute__((always_inline)) {
                 constexpr int g = decltype(gt)::value, ri = nb * GPB + g;
                 const small_f32x4 wv = ring[ri];
                 ring[ri] = wsrc[(int64_t)min((cbk + NB) * GPB + g, groups - 1) * 64];

@@ -14,38 +14,10 @@
 // the one ConvLayer::build packs for the layer ([n_cb][8 channels x 4 taps][64 rows]); it streams through LDS double-buffered.  Epilogue:
 // GroupNorm block sums in the canonical order with the in-launch finish, bias, stores.  Bit-identical to the windowed two-input launch
 // (NC_NO_DOWN2=1 runs that; tests/test_encodec_gpu.py holds both to the C oracle).
-#include <type_traits>
-#include <utility>
-
 #include "nc_conv.h"
-#include "nc_frag.h"
-#include "nc_gn.h"
-#include "nc_math.h"
+#include "nc_stream.h"
 
 namespace nc {
-
-typedef float d2_f32x16 __attribute__((ext_vector_type(16)));
-typedef float d2_f32x4 __attribute__((ext_vector_type(4)));
-typedef float d2_f32x2 __attribute__((ext_vector_type(2)));
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void d2_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void d2_static_for(F&& f) {
-    d2_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-__device__ __forceinline__ float d2_from_left(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float d2_from_right(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float d2_other_half(float v, int hi) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(hi ? r[0] : r[1]);
-}
 
 // TM: 32-row tiles of the output (Cout / 32, one row tile per workgroup set: Cout <= 128).  XV2: rows 8-byte aligned at even columns.
 template <int TM, bool XV2>
@@ -61,11 +33,7 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     const int t_tile = __builtin_amdgcn_readfirstlane(lin % p.n_t_tiles);
     const int b = __builtin_amdgcn_readfirstlane(lin / p.n_t_tiles);
     const int T = p.T, Tout = p.Tout, n_cb = p.n_cb, Cin = p.Cin;
@@ -91,24 +59,24 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
     const float* const xb = p.xb + (int64_t)b * p.x_bstride;
     const unsigned x_lane_off = (unsigned)hi * x_cstride + (unsigned)colc;
     const unsigned h_lane_off = (unsigned)hi * x_cstride + (unsigned)hcol;
-    const d2_f32x4* const wbase = reinterpret_cast<const d2_f32x4*>(p.w);
+    const f32x4_t* const wbase = reinterpret_cast<const f32x4_t*>(p.w);
     const bool first_col = col == 0, last_col = col + 2 == T;     // reflect: x[-1] = x[1], x[T] = x[T-2]
     const bool lane_first = l31 == 0, lane_last = l31 == 31;
 
-    d2_f32x16 acc[TM];
+    f32x16_t acc[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
 
-    d2_f32x2 qa[PF], qb[PF];
+    f32x2_t qa[PF], qb[PF];
     float ha[PF], hb[PF];
     const int last_pair = Cin / 2 - 1;
-    auto load_pair = [&](int g, d2_f32x2& va, d2_f32x2& vb, float& h_a, float& h_b) __attribute__((always_inline)) {
+    auto load_pair = [&](int g, f32x2_t& va, f32x2_t& vb, float& h_a, float& h_b) __attribute__((always_inline)) {
         const size_t ro = (size_t)(2 * min(g, last_pair)) * x_cstride;
         if constexpr (XV2) {
-            va = *reinterpret_cast<const d2_f32x2*>(xa + ro + x_lane_off);
-            vb = *reinterpret_cast<const d2_f32x2*>(xb + ro + x_lane_off);
+            va = *reinterpret_cast<const f32x2_t*>(xa + ro + x_lane_off);
+            vb = *reinterpret_cast<const f32x2_t*>(xb + ro + x_lane_off);
         } else {
             va[0] = xa[ro + x_lane_off]; va[1] = xa[ro + x_lane_off + 1];
             vb[0] = xb[ro + x_lane_off]; vb[1] = xb[ro + x_lane_off + 1];
@@ -119,11 +87,11 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) load_pair(u, qa[u], qb[u], ha[u], hb[u]);
 
-    d2_f32x4 ra[NA];
+    f32x4_t ra[NA];
 #pragma unroll
     for (int n = 0; n < NA; ++n) {
         const int idx = tid + 256 * n;
-        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<d2_f32x4*>(As[0])[idx] = wbase[idx];
+        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[0])[idx] = wbase[idx];
     }
     __syncthreads();
 
@@ -131,14 +99,14 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
         const int cur = cb & 1;
         const bool more = cb + 1 < n_cb;
         if (more) {
-            const d2_f32x4* src = wbase + (size_t)(cb + 1) * A_VEC;
+            const f32x4_t* src = wbase + (size_t)(cb + 1) * A_VEC;
 #pragma unroll
             for (int n = 0; n < NA; ++n) ra[n] = src[(A_VEC % 256 == 0) ? (unsigned)(tid + 256 * n) : min((unsigned)(tid + 256 * n), (unsigned)(A_VEC - 1))];
         }
         const float* Ac = As[cur] + hi * BM + nc_a_lane_off<TM>(l31);
         // The staged value: GN_a(a) + GN_b(b), then ELU (pad_act_kernel's arithmetic: normalise each operand, add, activate), evaluated on
         // packed pairs -- the lane's two columns of a channel pair, and the halo values of TWO channel pairs together.
-        d2_static_for<CB / 4>([&](auto dt) __attribute__((always_inline)) {
+        nc_static_for<CB / 4>([&](auto dt) __attribute__((always_inline)) {
             constexpr int du = decltype(dt)::value;
             const int g0 = cb * (CB / 2) + 2 * du;
             const float4 gt0 = gn_in ? Gt[2 * g0 + hi] : make_float4(1.0f, 0.0f, 1.0f, 0.0f);
@@ -149,7 +117,7 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
                 hvb = ((hvb - mu_b) * rs_b) * (nc_f2){gt0.z, gt1.z} + (nc_f2){gt0.w, gt1.w};
             }
             const nc_f2 hvv = nc_eluf2(hva + hvb);
-            d2_static_for<2>([&](auto pt) __attribute__((always_inline)) {
+            nc_static_for<2>([&](auto pt) __attribute__((always_inline)) {
                 constexpr int pr = 2 * du + decltype(pt)::value;
                 const int g = cb * (CB / 2) + pr;
                 const float4 gt = decltype(pt)::value ? gt1 : gt0;
@@ -161,13 +129,13 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
                 }
                 const nc_f2 ev = nc_eluf2(va + vb);
                 const float a = ev[0], bb = ev[1], hv = hvv[decltype(pt)::value];
-                float aL = d2_from_left(bb), bR = d2_from_right(a);
+                float aL = nc_lane_from_left(bb), bR = nc_lane_from_right(a);
                 aL = lane_first ? hv : aL;
                 bR = lane_last ? hv : bR;
                 aL = first_col ? bb : aL;                          // reflect pad (SConv1d.cs:258-274)
                 bR = last_col ? a : bR;
                 // the other half's channel: taps of the same output column
-                const float xaL = d2_other_half(aL, hi), xa_ = d2_other_half(a, hi), xbb = d2_other_half(bb, hi), xbR = d2_other_half(bR, hi);
+                const float xaL = nc_other_half(aL, hi), xa_ = nc_other_half(a, hi), xbb = nc_other_half(bb, hi), xbR = nc_other_half(bR, hi);
                 // step 0: (c0,k0 | c0,k1)   step 1: (c0,k2 | c0,k3)   step 2: (c1,k0 | c1,k1)   step 3: (c1,k2 | c1,k3)
                 const float s0 = hi ? xa_ : aL;
                 const float s1 = hi ? xbR : bb;
@@ -192,7 +160,7 @@ __global__ __launch_bounds__(256, 4) void down2_kernel(const Down2Args p) {
 #pragma unroll
             for (int n = 0; n < NA; ++n) {
                 const int idx = tid + 256 * n;
-                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<d2_f32x4*>(As[cur ^ 1])[idx] = ra[n];
+                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[cur ^ 1])[idx] = ra[n];
             }
         }
         __syncthreads();

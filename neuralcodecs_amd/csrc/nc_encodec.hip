@@ -1241,10 +1241,44 @@ static void second_input(ConvIO& io, const EncodecModel::Act& b2) {
     io.in_stats2 = b2.stats; io.in_gamma2 = b2.stats ? b2.gamma : nullptr; io.in_beta2 = b2.stats ? b2.beta : nullptr;
 }
 
+// The streaming two-input kernels (Down2Args / Up2Args: same field names).  Operands: the two pending views with their GroupNorm triples.
+template <class Args>
+static void stream_operands(Args& d, const EncodecModel::Act& a, const EncodecModel::Act& b) {
+    d.xa = a.p + a.off; d.xb = b.p + b.off; d.x_bstride = (int64_t)a.C * a.rs; d.x_cstride = a.rs;
+    d.Cin = a.C;
+    d.stats_a = a.stats; d.gamma_a = a.stats ? a.gamma : nullptr; d.beta_a = a.stats ? a.beta : nullptr;
+    d.stats_b = b.stats; d.gamma_b = b.stats ? b.gamma : nullptr; d.beta_b = b.stats ? b.beta : nullptr;
+}
+// rows 8-byte aligned at even columns for both operands
+template <class Args>
+static bool stream_aligned(const Args& d) {
+    auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; };
+    return al8(d.xa) && al8(d.xb) && !(d.x_cstride & 1) && !(d.x_bstride & 1);
+}
+// GroupNorm block sums of the output (nrb x ncb blocks of 32 x 32 per clip) with the in-launch finish over `count` elements; alloc: the
+// model's pool (partials first, then the [N][2] statistics, which it returns)
+template <class Args, class Alloc>
+static float* stream_gn_out(Args& d, int N, int nrb, int ncb, unsigned* counters, double count, Alloc&& alloc) {
+    d.gn_nrb = nrb; d.gn_ncb = ncb;
+    d.gn_part = reinterpret_cast<double*>(alloc((size_t)N * d.gn_nrb * d.gn_ncb * 4));
+    float* st = alloc((size_t)N * 2);
+    d.gn_stats = st;
+    d.gn_count = counters;
+    d.gn_n = gn_count_arg(count);
+    return st;
+}
+// the raw output of a streaming launch as a pending view: rows of L samples at pitch rs, starting `off` samples in
+static EncodecModel::Act stream_result(const float* y, const EncodecModel::SConv& L, int64_t len, int64_t rs, int64_t off, const float* st) {
+    EncodecModel::Act o;
+    o.p = y; o.C = L.Cout; o.L = len; o.rs = rs; o.off = off;
+    o.stats = st; o.gamma = st ? L.gamma.as<float>() : nullptr; o.beta = st ? L.beta.as<float>() : nullptr;
+    return o;
+}
+
 EncodecModel::Act EncodecModel::sconv(SConv& L, const Act& a, const Act* b2, bool elu, int N) {
     const Plan pl = plan_sconv(a.L, L.K, L.stride, 1);
     static const bool no_fuse = env_flag("NC_ENCODEC_NO_FUSE");
-    {   // the stride-2 / stride-4 down-convolutions behind the first two residual blocks: streaming two-input kernels (nc_down2.hip, nc_down4.hip)
+    {   // the stride-2 / stride-4 down-convolutions behind the first two residual blocks: streaming two-input kernels (nc_down2.hip, nc_down_s.hip)
         static const bool no_down2 = env_flag("NC_NO_DOWN2");
         static const bool no_down4 = env_flag("NC_NO_DOWN4");
         const int64_t T = a.L;
@@ -1261,10 +1295,8 @@ EncodecModel::Act EncodecModel::sconv(SConv& L, const Act& a, const Act* b2, boo
                         T % 5 == 0 && pl.left == 3 && pl.right == 2 && pl.Lout == T / 5;
         if (s2 || s4 || s5) {
             Down2Args d{};
-            d.xa = a.p + a.off; d.xb = b2->p + b2->off; d.x_bstride = (int64_t)a.C * a.rs; d.x_cstride = a.rs;
-            d.Cin = a.C; d.T = (int)T; d.Tout = (int)pl.Lout;
-            d.stats_a = a.stats; d.gamma_a = a.stats ? a.gamma : nullptr; d.beta_a = a.stats ? a.beta : nullptr;
-            d.stats_b = b2->stats; d.gamma_b = b2->stats ? b2->gamma : nullptr; d.beta_b = b2->stats ? b2->beta : nullptr;
+            stream_operands(d, a, *b2);
+            d.T = (int)T; d.Tout = (int)pl.Lout;
             d.w = L.conv.w.as<float>(); d.bias = L.conv.has_bias ? L.conv.bias.as<float>() : nullptr;
             float* y = alloc((size_t)N * L.Cout * pl.Lout);
             d.y = y; d.y_bstride = (int64_t)L.Cout * pl.Lout; d.y_cstride = pl.Lout; d.Cout = L.Cout;
@@ -1275,25 +1307,16 @@ EncodecModel::Act EncodecModel::sconv(SConv& L, const Act& a, const Act* b2, boo
                 d.w_co_stride = (int64_t)((L.Cin + 2) / 3) * 30 * 128;
             }
             float* st = nullptr;
-            if (cfg.time_group_norm) {
-                d.gn_nrb = L.Cout / 32; d.gn_ncb = (int)((pl.Lout + 31) / 32);
-                d.gn_part = reinterpret_cast<double*>(alloc((size_t)N * d.gn_nrb * d.gn_ncb * 4));
-                st = alloc((size_t)N * 2);
-                d.gn_stats = st;
-                d.gn_count = gn_counters.as<unsigned>() + (size_t)cur_group * 2 * GN_MAX_SAMPLES;
-                d.gn_n = gn_count_arg((double)L.Cout * (double)pl.Lout);
-            }
-            auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; };
-            const bool aligned = al8(d.xa) && al8(d.xb) && !(d.x_cstride & 1) && !(d.x_bstride & 1);
+            if (cfg.time_group_norm)
+                st = stream_gn_out(d, N, L.Cout / 32, (int)((pl.Lout + 31) / 32), gn_counters.as<unsigned>() + (size_t)cur_group * 2 * GN_MAX_SAMPLES,
+                                   (double)L.Cout * (double)pl.Lout, [&](size_t n) { return alloc(n); });
+            const bool aligned = stream_aligned(d);
             {
                 ProfScope ps(&prof, stream, L.conv.kclass, L.conv.flops(N, pl.Lp), 4.0 * N * (2.0 * a.C * (double)T + (double)L.Cout * pl.Lout));
                 if (!(s5 ? launch_down5(d, 4, stream) : s4 ? launch_down4(d, 4, stream) : launch_down2(d, 2, aligned, stream)))
                     fail(NC_ESTATE, "internal: no streaming down-convolution instance");
             }
-            Act o;
-            o.p = y; o.C = L.Cout; o.L = pl.Lout; o.rs = pl.Lout; o.off = 0;
-            o.stats = st; o.gamma = st ? L.gamma.as<float>() : nullptr; o.beta = st ? L.beta.as<float>() : nullptr;
-            return o;
+            return stream_result(y, L, pl.Lout, pl.Lout, 0, st);
         }
     }
     float* y = nullptr;
@@ -1338,34 +1361,23 @@ EncodecModel::Act EncodecModel::sconvT(SConv& L, const Act& a, const Act* b2, bo
         const bool u4 = common && !no_up4 && S == 4 && L.conv.cfg.TM == 4 && L.Cout == 64;
         if (u2 || u4) {
             Up2Args d{};
-            d.xa = a.p + a.off; d.xb = b2->p + b2->off; d.x_bstride = (int64_t)a.C * a.rs; d.x_cstride = a.rs;
-            d.Cin = a.C; d.L = (int)T; d.elu = elu ? 1 : 0;
-            d.stats_a = a.stats; d.gamma_a = a.stats ? a.gamma : nullptr; d.beta_a = a.stats ? a.beta : nullptr;
-            d.stats_b = b2->stats; d.gamma_b = b2->stats ? b2->gamma : nullptr; d.beta_b = b2->stats ? b2->beta : nullptr;
+            stream_operands(d, a, *b2);
+            d.L = (int)T; d.elu = elu ? 1 : 0;
             d.w = L.conv.w.as<float>(); d.bias = L.conv.has_bias ? L.conv.bias.as<float>() : nullptr;
             float* y = alloc((size_t)N * L.Cout * Lfull);
             d.y = y; d.y_bstride = (int64_t)L.Cout * Lfull; d.y_cstride = Lfull; d.Cout = L.Cout;
             d.B = N; d.n_t_tiles = (int)((T + 1 + 255) / 256); d.n_cb = (L.Cin + 15) / 16; d.n_co_tiles = S * L.Cout / (32 * L.conv.cfg.TM);
             float* st = nullptr;
-            if (cfg.time_group_norm) {
-                d.gn_nrb = S * L.Cout / 32; d.gn_ncb = (int)(((Lfull + S - 1) / S + 31) / 32);
-                d.gn_part = reinterpret_cast<double*>(alloc((size_t)N * d.gn_nrb * d.gn_ncb * 4));
-                st = alloc((size_t)N * 2);
-                d.gn_stats = st;
-                d.gn_count = gn_counters.as<unsigned>() + (size_t)cur_group * 2 * GN_MAX_SAMPLES;
-                d.gn_n = gn_count_arg((double)L.Cout * (double)Lfull);
-            }
-            auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; };
-            const bool aligned = al8(d.xa) && al8(d.xb) && !(d.x_cstride & 1) && !(d.x_bstride & 1);
+            if (cfg.time_group_norm)
+                st = stream_gn_out(d, N, S * L.Cout / 32, (int)(((Lfull + S - 1) / S + 31) / 32), gn_counters.as<unsigned>() + (size_t)cur_group * 2 * GN_MAX_SAMPLES,
+                                   (double)L.Cout * (double)Lfull, [&](size_t n) { return alloc(n); });
+            const bool aligned = stream_aligned(d);
             {
                 ProfScope ps(&prof, stream, L.conv.kclass, L.conv.flops(N, T), 4.0 * N * (2.0 * a.C * (double)T + (double)L.Cout * Lfull));
                 if (!launch_up2(d, L.conv.cfg.TM, S, aligned, stream)) fail(NC_ESTATE, "internal: no streaming up-convolution instance");
             }
             const int64_t pt = L.K - L.stride, right = pt / 2, left = pt - right;           // non-causal trim (SConvTranspose1d.cs:159-171)
-            Act o;
-            o.p = y; o.C = L.Cout; o.L = Lfull - left - right; o.rs = Lfull; o.off = left;
-            o.stats = st; o.gamma = st ? L.gamma.as<float>() : nullptr; o.beta = st ? L.beta.as<float>() : nullptr;
-            return o;
+            return stream_result(y, L, Lfull - left - right, Lfull, left, st);
         }
     }
     ConvIO io{};

@@ -12,83 +12,10 @@
 // on the output's own counters, bias, 8-byte stores.  The second pass of the block (conv2, k = 1 on h) stays conv1x1_kernel.
 // Arithmetic: operation for operation that of conv1x1_kernel (shortcut) and conv3_stream_kernel (branch): results are bit-identical to
 // the two-launch path (tests/test_encodec_gpu.py runs both and the C oracle).
-#include <type_traits>
-#include <utility>
-
 #include "nc_conv.h"
-#include "nc_frag.h"
-#include "nc_gn.h"
-#include "nc_math.h"
+#include "nc_stream.h"
 
 namespace nc {
-
-typedef float ra_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ra_f32x4 __attribute__((ext_vector_type(4)));
-typedef float ra_f32x2 __attribute__((ext_vector_type(2)));
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void ra_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void ra_static_for(F&& f) {
-    ra_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-__device__ __forceinline__ float ra_from_left(float v) {    // lane i <- lane i-1 (DPP wave_shr:1)
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ra_from_right(float v) {   // lane i <- lane i+1 (DPP wave_shl:1)
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ra_other_half(float v, int hi) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(hi ? r[0] : r[1]);
-}
-
-// GroupNorm block sums of one output (rows = TM tiles of 32, this wave's 64 columns) + the in-launch finish; every thread calls it
-template <int TM>
-__device__ __forceinline__ void ra_gn_out(const ra_f32x16 (&acc)[TM][2], const float* Ep, int rows_total, bool colok, int col0, int l31, int hi, int lane,
-                                          double* gp, int nrb, int ncb, unsigned* count, float* stats, unsigned n_wg, double n) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        double a1[2], a2[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float vv[16];
-            unsigned okm16 = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int R = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                vv[r] = acc[i][j][r] + Ep[R];
-                if (colok && R < rows_total) okm16 |= 1u << r;
-            }
-            nc_gn_slot_sums<false>(vv, okm16, a1[j], a2[j]);
-        }
-        double s1 = a1[0] + a1[1], s2 = a2[0] + a2[1];
-        nc_gn_butterfly_row(s1, s2);
-        s1 = nc_gn_swap_add<true>(s1);
-        s2 = nc_gn_swap_add<true>(s2);
-        const int cbk = (col0 >> 5) + (l31 >> 4);
-        if ((lane & 47) == 0 && i < nrb && cbk < ncb) nc_gn_store_partial(gp + ((int64_t)i * ncb + cbk) * 2, s1, s2);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (count != nullptr) nc_gn_arrive_and_finish(gp, count, stats, nrb * ncb, n_wg, n);
-}
-
-template <int TM>
-__device__ __forceinline__ void ra_store(const ra_f32x16 (&acc)[TM][2], const float* Ep, int rows_total, float* yt, unsigned cstride, int hi) {
-    const int rows_left = rows_total - 4 * hi;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int R = i * 32 + (r & 3) + 8 * (r >> 2);
-            if (R >= rows_left) continue;
-            const float bias = Ep[R + 4 * hi];
-            const ra_f32x2 v = {acc[i][0][r] + bias, acc[i][1][r] + bias};
-            *reinterpret_cast<ra_f32x2*>(yt + (size_t)R * cstride) = v;
-        }
-}
 
 // TMS: 32-row tiles of the shortcut (C / 32); the branch has one (C / 2 <= 32 rows).  XV2: rows 8-byte aligned at even columns.
 template <int TMS, bool XV2>
@@ -97,11 +24,7 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
     constexpr int BMS = 32 * TMS, BMB = 32;
     constexpr int AB_FLOATS = CB * 3 * BMB, AB_VEC = AB_FLOATS / 4, NAB = (AB_VEC + 255) / 256;   // 384 vectors: 2 passes
     constexpr int AS_FLOATS = CB * BMS, AS_VEC = AS_FLOATS / 4;                                    // 128 / 256 vectors: 1 pass
-    // (PF: channel pairs in flight; 8 measured the same as 4)
-
-
-    constexpr int PF = 4;
-
+    constexpr int PF = 4;                          // channel pairs in flight; 8 measured the same as 4
 
     __shared__ __attribute__((aligned(16))) float Asb[2][AB_FLOATS];
     __shared__ __attribute__((aligned(16))) float Ass[2][AS_FLOATS];
@@ -112,11 +35,7 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     const int t_tile = __builtin_amdgcn_readfirstlane(lin % p.n_t_tiles);
     const int b = __builtin_amdgcn_readfirstlane(lin / p.n_t_tiles);
     const int T = p.T, n_cb = p.n_cb, Cin = p.Cin;
@@ -135,13 +54,13 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
     const int colc = min(col, T - 2);
     const float* const xb = p.x + (int64_t)b * p.x_bstride;
     const unsigned x_lane_off = (unsigned)hi * x_cstride + (unsigned)colc;
-    const ra_f32x4* const wb_base = reinterpret_cast<const ra_f32x4*>(p.w_b);
-    const ra_f32x4* const ws_base = reinterpret_cast<const ra_f32x4*>(p.w_s);
+    const f32x4_t* const wb_base = reinterpret_cast<const f32x4_t*>(p.w_b);
+    const f32x4_t* const ws_base = reinterpret_cast<const f32x4_t*>(p.w_s);
     const bool first_col = col == 0, last_col = col + 2 == T;
     const bool lane_first = l31 == 0, lane_last = l31 == 31;
     const int hsel_addr = 4 * (32 * hi + (lane_last ? 2 : 0));   // ds_bpermute byte address of this lane's halo value for pair 0
 
-    ra_f32x16 accs[TMS][2], accb[1][2];
+    f32x16_t accs[TMS][2], accb[1][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -151,12 +70,12 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
             for (int i = 0; i < TMS; ++i) accs[i][j][r] = 0.0f;
         }
 
-    ra_f32x2 bq[PF];
+    f32x2_t bq[PF];
     const int last_pair = Cin / 2 - 1;
-    auto load_pair = [&](int g, ra_f32x2& v) __attribute__((always_inline)) {
+    auto load_pair = [&](int g, f32x2_t& v) __attribute__((always_inline)) {
         const float* row = xb + (size_t)(2 * min(g, last_pair)) * x_cstride;
         if constexpr (XV2) {
-            v = *reinterpret_cast<const ra_f32x2*>(row + x_lane_off);
+            v = *reinterpret_cast<const f32x2_t*>(row + x_lane_off);
         } else {
             v[0] = row[x_lane_off];
             v[1] = row[x_lane_off + 1];
@@ -176,20 +95,20 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
     };
     float hb_next = load_halo_block(0);
 
-    ra_f32x4 rab[NAB], ras;
+    f32x4_t rab[NAB], ras;
 #pragma unroll
     for (int n = 0; n < NAB; ++n) {
         const int idx = tid + 256 * n;
-        if (idx < AB_VEC) reinterpret_cast<ra_f32x4*>(Asb[0])[idx] = wb_base[idx];
+        if (idx < AB_VEC) reinterpret_cast<f32x4_t*>(Asb[0])[idx] = wb_base[idx];
     }
-    if (tid < AS_VEC) reinterpret_cast<ra_f32x4*>(Ass[0])[tid] = ws_base[tid];
+    if (tid < AS_VEC) reinterpret_cast<f32x4_t*>(Ass[0])[tid] = ws_base[tid];
     __syncthreads();
 
     for (int cb = 0; cb < n_cb; ++cb) {
         const int cur = cb & 1;
         const bool more = cb + 1 < n_cb;
         if (more) {
-            const ra_f32x4* srcb = wb_base + (size_t)(cb + 1) * AB_VEC;
+            const f32x4_t* srcb = wb_base + (size_t)(cb + 1) * AB_VEC;
 #pragma unroll
             for (int n = 0; n < NAB; ++n) rab[n] = srcb[min((unsigned)(tid + 256 * n), (unsigned)(AB_VEC - 1))];
             ras = (ws_base + (size_t)(cb + 1) * AS_VEC)[min((unsigned)tid, (unsigned)(AS_VEC - 1))];
@@ -203,11 +122,11 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
             hvb = ((hvb - in_mu) * in_rs) * gbh.x + gbh.y;
         }
         hvb = nc_eluf(hvb);
-        ra_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
+        nc_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
             constexpr int pr = decltype(pt)::value;
             const int g = cb * (CB / 2) + pr;
             const float2 gb = gn_in ? Gt[2 * g + hi] : make_float2(1.0f, 0.0f);
-            const ra_f32x2 raw = bq[pr % PF];
+            const f32x2_t raw = bq[pr % PF];
             load_pair(g + PF, bq[pr % PF]);
             float na = raw[0], nb = raw[1];
             if (gn_in) {                                       // GroupNorm(1,C) apply (NormConv1d.cs:155)
@@ -225,20 +144,15 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
                 }
             }
             // branch: ELU, then the three taps (conv3_stream_kernel's step layout)
-
-
-
-
-
             const float a = nc_eluf(na), bb = nc_eluf(nb);
-            float aL = ra_from_left(bb), bR = ra_from_right(a);
+            float aL = nc_lane_from_left(bb), bR = nc_lane_from_right(a);
             // the span's halo for the first / last lane of either half: lanes 4 pr (+32) hold the left values, 4 pr + 2 (+32) the right ones
             const float hs = __int_as_float(__builtin_amdgcn_ds_bpermute(hsel_addr + 16 * pr, __float_as_int(hvb)));
             aL = lane_first ? hs : aL;
             bR = lane_last ? hs : bR;
             aL = first_col ? bb : aL;                          // reflect pad (SConv1d.cs:258-274): x[-1] = x[1]
             bR = last_col ? a : bR;                            //                                    x[T]  = x[T-2]
-            const float ax = ra_other_half(a, hi), bx = ra_other_half(bb, hi);
+            const float ax = nc_other_half(a, hi), bx = nc_other_half(bb, hi);
             const float s0[2] = {hi ? ax : aL, hi ? bx : a};
             const float s1[2] = {hi ? aL : bb, hi ? a : bR};
             const float s2[2] = {hi ? bb : ax, hi ? bR : bx};
@@ -257,25 +171,23 @@ __global__ __launch_bounds__(256, TMS == 1 ? 4 : 3) void res_a_kernel(const ResA
 #pragma unroll
             for (int n = 0; n < NAB; ++n) {
                 const int idx = tid + 256 * n;
-                if (idx < AB_VEC) reinterpret_cast<ra_f32x4*>(Asb[cur ^ 1])[idx] = rab[n];
+                if (idx < AB_VEC) reinterpret_cast<f32x4_t*>(Asb[cur ^ 1])[idx] = rab[n];
             }
-            if (tid < AS_VEC) reinterpret_cast<ra_f32x4*>(Ass[cur ^ 1])[tid] = ras;
+            if (tid < AS_VEC) reinterpret_cast<f32x4_t*>(Ass[cur ^ 1])[tid] = ras;
         }
         __syncthreads();
     }
 
     const bool colok = col < T;
-
     if (p.gn_part_s != nullptr) {
-        ra_gn_out<TMS>(accs, Eps, p.Cs, colok, col0, l31, hi, lane, p.gn_part_s + (int64_t)b * p.gn_nrb_s * p.gn_ncb * 2, p.gn_nrb_s, p.gn_ncb,
+        nc_stream_gn_out2<TMS>(accs, Eps, p.Cs, colok, colok, col0, l31, hi, lane, p.gn_part_s + (int64_t)b * p.gn_nrb_s * p.gn_ncb * 2, 0, p.gn_nrb_s, p.gn_ncb,
                        p.gn_count_s ? p.gn_count_s + b : nullptr, p.gn_stats_s + 2 * b, (unsigned)p.n_t_tiles, p.gn_n_s);
-        ra_gn_out<1>(accb, Epb, p.Cb, colok, col0, l31, hi, lane, p.gn_part_b + (int64_t)b * p.gn_nrb_b * p.gn_ncb * 2, p.gn_nrb_b, p.gn_ncb,
+        nc_stream_gn_out2<1>(accb, Epb, p.Cb, colok, colok, col0, l31, hi, lane, p.gn_part_b + (int64_t)b * p.gn_nrb_b * p.gn_ncb * 2, 0, p.gn_nrb_b, p.gn_ncb,
                      p.gn_count_b ? p.gn_count_b + b : nullptr, p.gn_stats_b + 2 * b, (unsigned)p.n_t_tiles, p.gn_n_b);
     }
-
     if (!colok) return;
-    ra_store<TMS>(accs, Eps, p.Cs, p.ys + (int64_t)b * p.ys_bstride + (unsigned)(4 * hi) * (unsigned)p.ys_cstride + (unsigned)col, (unsigned)p.ys_cstride, hi);
-    ra_store<1>(accb, Epb, p.Cb, p.yb + (int64_t)b * p.yb_bstride + (unsigned)(4 * hi) * (unsigned)p.yb_cstride + (unsigned)col, (unsigned)p.yb_cstride, hi);
+    nc_stream_store2<TMS>(accs, Eps, p.Cs, p.ys + (int64_t)b * p.ys_bstride + (unsigned)(4 * hi) * (unsigned)p.ys_cstride + (unsigned)col, (unsigned)p.ys_cstride, hi);
+    nc_stream_store2<1>(accb, Epb, p.Cb, p.yb + (int64_t)b * p.yb_bstride + (unsigned)(4 * hi) * (unsigned)p.yb_cstride + (unsigned)col, (unsigned)p.yb_cstride, hi);
 }
 
 bool launch_res_a(const ResAArgs& a, int TMS, bool aligned, hipStream_t stream) {

@@ -26,11 +26,6 @@ namespace nc {
 
 namespace {
 
-template <int N, class F, int... I>
-__device__ __forceinline__ void nc_static_for_su_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void nc_static_for_su(F&& f) { nc_static_for_su_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
-
 typedef float su_f32x4 __attribute__((ext_vector_type(4)));
 typedef float su_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -200,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void snac_unit_kernel(const UnitArgs p) {
                     rsa[i][2 * r + 1] = xr[R * uT + cc1];
                 }
         }
-        nc_static_for_su<TM>([&](auto it) __attribute__((always_inline)) {
+        nc_static_for<TM>([&](auto it) __attribute__((always_inline)) {
             constexpr int i = decltype(it)::value;
             float rs[32];
 #pragma unroll

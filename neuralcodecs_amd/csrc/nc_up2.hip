@@ -17,35 +17,10 @@
 // sub-pixel rows = two row tiles of 128 (TM = 4), one workgroup each over the same columns (adjacent in the tile map: the second reads the
 // operands out of L2); a lane stores FOUR consecutive samples per output channel and column (16-byte stores).  It replaces a summed copy
 // (pad_act_kernel, 56 us) + the windowed instance (378 us).  NC_NO_UP4=1 runs those.
-#include <type_traits>
-#include <utility>
-
 #include "nc_conv.h"
-#include "nc_frag.h"
-#include "nc_gn.h"
-#include "nc_math.h"
+#include "nc_stream.h"
 
 namespace nc {
-
-typedef float u2_f32x16 __attribute__((ext_vector_type(16)));
-typedef float u2_f32x4 __attribute__((ext_vector_type(4)));
-typedef float u2_f32x2 __attribute__((ext_vector_type(2)));
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void u2_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void u2_static_for(F&& f) {
-    u2_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-__device__ __forceinline__ float u2_from_left(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float u2_other_half(float v, int hi) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(hi ? r[0] : r[1]);
-}
 
 // TM: 32-row tiles of the sub-pixel rows (2 * Cout / 32; one row tile per workgroup: 2 * Cout <= 128).  XV2: rows 8-byte aligned at even columns.
 template <int TM, int S, bool XV2>
@@ -61,11 +36,7 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int lin;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lin = nc_xcd_tile_id(bid, nwg);
     const int co_tile = __builtin_amdgcn_readfirstlane(lin % p.n_co_tiles);      // (the row tiles of a column tile are neighbours in the launch order)
     lin /= p.n_co_tiles;
     const int t_tile = __builtin_amdgcn_readfirstlane(lin % p.n_t_tiles);
@@ -93,12 +64,12 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
     const float* const xb = p.xb + (int64_t)b * p.x_bstride;
     const unsigned x_lane_off = (unsigned)hi * x_cstride + (unsigned)colc;
     const unsigned h_lane_off = (unsigned)hi * x_cstride + (unsigned)hcol;
-    const u2_f32x4* const wbase = reinterpret_cast<const u2_f32x4*>(p.w) + (size_t)co_tile * n_cb * A_VEC;
+    const f32x4_t* const wbase = reinterpret_cast<const f32x4_t*>(p.w) + (size_t)co_tile * n_cb * A_VEC;
     const bool lane_first = l31 == 0;
     const bool ok0 = col < L, ok1 = col + 1 < L;                   // x[q] = 0 for q >= L (zero extension of the activated tensor)
     const bool halo_ok = col0 >= 1 && col0 - 1 < L;                // x[-1] = 0
 
-    u2_f32x16 acc[TM][2];
+    f32x16_t acc[TM][2];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -106,14 +77,14 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    u2_f32x2 qa[PF], qb[PF];
+    f32x2_t qa[PF], qb[PF];
     float ha[PF], hb[PF];
     const int last_pair = Cin / 2 - 1;
-    auto load_pair = [&](int g, u2_f32x2& va, u2_f32x2& vb, float& h_a, float& h_b) __attribute__((always_inline)) {
+    auto load_pair = [&](int g, f32x2_t& va, f32x2_t& vb, float& h_a, float& h_b) __attribute__((always_inline)) {
         const size_t ro = (size_t)(2 * min(g, last_pair)) * x_cstride;
         if constexpr (XV2) {
-            va = *reinterpret_cast<const u2_f32x2*>(xa + ro + x_lane_off);
-            vb = *reinterpret_cast<const u2_f32x2*>(xb + ro + x_lane_off);
+            va = *reinterpret_cast<const f32x2_t*>(xa + ro + x_lane_off);
+            vb = *reinterpret_cast<const f32x2_t*>(xb + ro + x_lane_off);
         } else {
             va[0] = xa[ro + x_lane_off]; va[1] = xa[ro + x_lane_off + 1];
             vb[0] = xb[ro + x_lane_off]; vb[1] = xb[ro + x_lane_off + 1];
@@ -124,11 +95,11 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
 #pragma unroll
     for (int u = 0; u < PF; ++u) load_pair(u, qa[u], qb[u], ha[u], hb[u]);
 
-    u2_f32x4 ra[NA];
+    f32x4_t ra[NA];
 #pragma unroll
     for (int n = 0; n < NA; ++n) {
         const int idx = tid + 256 * n;
-        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<u2_f32x4*>(As[0])[idx] = wbase[idx];
+        if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[0])[idx] = wbase[idx];
     }
     __syncthreads();
 
@@ -147,25 +118,25 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
         const int cur = cb & 1;
         const bool more = cb + 1 < n_cb;
         if (more) {
-            const u2_f32x4* src = wbase + (size_t)(cb + 1) * A_VEC;
+            const f32x4_t* src = wbase + (size_t)(cb + 1) * A_VEC;
 #pragma unroll
             for (int n = 0; n < NA; ++n) ra[n] = src[(A_VEC % 256 == 0) ? (unsigned)(tid + 256 * n) : min((unsigned)(tid + 256 * n), (unsigned)(A_VEC - 1))];
         }
         const float* Ac = As[cur] + hi * BM + nc_a_lane_off<TM>(l31);
-        u2_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
+        nc_static_for<CB / 2>([&](auto pt) __attribute__((always_inline)) {
             constexpr int pr = decltype(pt)::value;
             const int g = cb * (CB / 2) + pr;
             const float4 gt = gn_in ? Gt[2 * g + hi] : make_float4(1.0f, 0.0f, 1.0f, 0.0f);
-            const u2_f32x2 rawa = qa[pr % PF], rawb = qb[pr % PF];
+            const f32x2_t rawa = qa[pr % PF], rawb = qb[pr % PF];
             const float hra = ha[pr % PF], hrb = hb[pr % PF];
             load_pair(g + PF, qa[pr % PF], qb[pr % PF], ha[pr % PF], hb[pr % PF]);
             float a = act(rawa[0], rawb[0], gt), bb = act(rawa[1], rawb[1], gt), hv = act(hra, hrb, gt);
             a = ok0 ? a : 0.0f;
             bb = ok1 ? bb : 0.0f;
             hv = halo_ok ? hv : 0.0f;
-            float aL = u2_from_left(bb);                       // x[col - 1]: the left lane's second value (the span's halo for its first lane)
+            float aL = nc_lane_from_left(bb);                       // x[col - 1]: the left lane's second value (the span's halo for its first lane)
             aL = lane_first ? hv : aL;
-            const float xaL = u2_other_half(aL, hi), xa_ = u2_other_half(a, hi), xbb = u2_other_half(bb, hi);
+            const float xaL = nc_other_half(aL, hi), xa_ = nc_other_half(a, hi), xbb = nc_other_half(bb, hi);
             // step 0: (c0,x[q] | c0,x[q-1])   step 1: (c1,x[q] | c1,x[q-1]);  column j = 0: q = col, j = 1: q = col + 1
             const float s0[2] = {hi ? xaL : a, hi ? xa_ : bb};
             const float s1[2] = {hi ? aL : xa_, hi ? a : xbb};
@@ -187,7 +158,7 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
 #pragma unroll
             for (int n = 0; n < NA; ++n) {
                 const int idx = tid + 256 * n;
-                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<u2_f32x4*>(As[cur ^ 1])[idx] = ra[n];
+                if ((A_VEC % 256 == 0) || idx < A_VEC) reinterpret_cast<f32x4_t*>(As[cur ^ 1])[idx] = ra[n];
             }
         }
         __syncthreads();
@@ -238,18 +209,18 @@ __global__ __launch_bounds__(256, TM <= 2 ? 3 : 2) void up2_kernel(const Up2Args
             float* yr = yb + (size_t)((co_tile * BM + R) / S) * (unsigned)p.y_cstride;
             const float b0 = Ep[R];
             if constexpr (S == 2) {
-                const u2_f32x2 v0 = {acc[i][0][r] + b0, acc[i][0][r + 1] + b0};
-                *reinterpret_cast<u2_f32x2*>(yr) = v0;
+                const f32x2_t v0 = {acc[i][0][r] + b0, acc[i][0][r + 1] + b0};
+                *reinterpret_cast<f32x2_t*>(yr) = v0;
                 if (second) {
-                    const u2_f32x2 v1 = {acc[i][1][r] + b0, acc[i][1][r + 1] + b0};
-                    *reinterpret_cast<u2_f32x2*>(yr + 2) = v1;
+                    const f32x2_t v1 = {acc[i][1][r] + b0, acc[i][1][r + 1] + b0};
+                    *reinterpret_cast<f32x2_t*>(yr + 2) = v1;
                 }
             } else {
-                const u2_f32x4 v0 = {acc[i][0][r] + b0, acc[i][0][r + 1] + b0, acc[i][0][r + 2] + b0, acc[i][0][r + 3] + b0};
-                *reinterpret_cast<u2_f32x4*>(yr) = v0;
+                const f32x4_t v0 = {acc[i][0][r] + b0, acc[i][0][r + 1] + b0, acc[i][0][r + 2] + b0, acc[i][0][r + 3] + b0};
+                *reinterpret_cast<f32x4_t*>(yr) = v0;
                 if (second) {
-                    const u2_f32x4 v1 = {acc[i][1][r] + b0, acc[i][1][r + 1] + b0, acc[i][1][r + 2] + b0, acc[i][1][r + 3] + b0};
-                    *reinterpret_cast<u2_f32x4*>(yr + 4) = v1;
+                    const f32x4_t v1 = {acc[i][1][r] + b0, acc[i][1][r + 1] + b0, acc[i][1][r + 2] + b0, acc[i][1][r + 3] + b0};
+                    *reinterpret_cast<f32x4_t*>(yr + 4) = v1;
                 }
             }
         }
