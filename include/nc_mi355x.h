@@ -211,6 +211,50 @@ NC_API nc_status nc_snac_process_audio_len(const nc_codec* h, int64_t n, int32_t
 NC_API nc_status nc_snac_process_audio(nc_codec* h, const float* audio, int64_t n, int32_t sample_rate, const float* noise, uint64_t seed,
                                        float* out);
 
+/* ------------------------------------------------------------------------------------ long clips
+ * One-shot size limit.  The convolution kernels address a layer's output with 32-bit offsets, so a one-shot call is refused with
+ * NC_EUNSUPPORTED once a layer has (rows of a tile + 4) * row_length + row_length >= 2^31, or, for the up-convolutions,
+ * (4 * Cout + 5) * row_length >= 2^31: about two minutes of DAC-44.1k / SNAC-44k audio per clip, whatever B.  Below that limit the
+ * activation arena of a one-shot call still grows with the clip (3 * B * max(C * L) * 4 bytes: about 3.4 GB per minute of DAC-44.1k
+ * decode at B = 1).
+ * DAC and SNAC have a finite receptive field, so a clip can be run in chunks of latent frames with a halo of recomputed frames on
+ * each side; every kept output is the number the one-shot call produces, bit for bit.  nc_dac_halo / nc_snac_halo derive the halo in
+ * closed form from the config alone (host functions: no handle, no device):
+ *   enc_left / enc_right   how many frames before / after its own frame a change of one input sample can move the encoder output
+ *   dec_left / dec_right   the same for a change of one latent frame and the output samples, in frames of hop samples
+ *   align                  chunk boundaries are multiples of this (SNAC: lcm(vq_strides[0], attention window); DAC: 1)
+ * Every halo is a multiple of align.  A chunk needs to its LEFT what a change reaches to its RIGHT, and the other way round. */
+typedef struct nc_halo {
+    int64_t enc_left, enc_right;
+    int64_t dec_left, dec_right;
+    int64_t align;
+} nc_halo;
+NC_API nc_status nc_dac_halo(const nc_dac_config* cfg, nc_halo* out);
+NC_API nc_status nc_snac_halo(const nc_snac_config* cfg, nc_halo* out);
+
+/* Per-handle chunk size, in latent frames, of nc_{dac,snac}_{encode,decode,from_codes}[_dev] and the DAC code-matrix pair:
+ *   NC_CHUNK_AUTO (default)  one-shot whenever the one-shot call would be served (so every call that succeeds without this setting
+ *                            issues exactly the same launches); chunked with a built-in chunk size only where the one-shot call
+ *                            would be refused for size.  Decided before anything is launched.
+ *   > 0                      every call with more frames than this runs chunked (rounded up to align)
+ *   NC_CHUNK_OFF             never chunk: long clips return NC_EUNSUPPORTED
+ * Chunked calls keep device memory independent of the clip length: the arena is sized by chunk + halos, and the host-pointer
+ * entry points upload and download per chunk.  nc_snac_encode_tensor*, nc_snac_process_audio and the group calls are never chunked.
+ * Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context). */
+#define NC_CHUNK_AUTO 0
+#define NC_CHUNK_OFF (-1)
+NC_API nc_status nc_codec_set_chunk_frames(nc_codec* h, int64_t chunk_frames);
+
+/* What a call on `frames` latent frames (decode != 0: decode, else encode) would do under the handle's setting: n_chunks (1 = one
+ * shot), the chunk size, the halos a window carries, and the activation-arena bytes the call needs. */
+typedef struct nc_chunk_plan {
+    int64_t n_chunks;
+    int64_t chunk_frames;
+    int64_t halo_left, halo_right;
+    int64_t arena_bytes;
+} nc_chunk_plan;
+NC_API nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t B, int64_t frames, nc_chunk_plan* out);
+
 /* -------------------------------------------------------------------------------------- Encodec
  * replaces: new Encodec(EncodecConfig)             NeuralCodecs.Torch/Models/Encodec.cs:46-90
  * Only channels / dimension / norm / causal reach SEANet in the reference (Encodec.cs:57-68, deviation D11); the other SEANet

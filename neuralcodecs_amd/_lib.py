@@ -58,6 +58,17 @@ class NcConvDesc(C.Structure):
                 ("transposed", C.c_int32), ("tanh_out", C.c_int32)]
 
 
+class NcHalo(C.Structure):
+    _fields_ = [("enc_left", C.c_int64), ("enc_right", C.c_int64), ("dec_left", C.c_int64), ("dec_right", C.c_int64), ("align", C.c_int64)]
+
+
+class NcChunkPlan(C.Structure):
+    _fields_ = [("n_chunks", C.c_int64), ("chunk_frames", C.c_int64), ("halo_left", C.c_int64), ("halo_right", C.c_int64),
+                ("arena_bytes", C.c_int64)]
+
+
+NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
+
 _lib = None
 
 # every symbol include/nc_mi355x.h declares: (name, restype, argtypes)
@@ -103,6 +114,10 @@ SYMBOLS = [
     ("nc_snac_from_codes_dev", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
     ("nc_snac_decode", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, C.c_uint64, _P]),
     ("nc_snac_decode_dev", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, C.c_uint64, _P]),
+    ("nc_dac_halo", C.c_int, [C.POINTER(NcDacConfig), C.POINTER(NcHalo)]),
+    ("nc_snac_halo", C.c_int, [C.POINTER(NcSnacConfig), C.POINTER(NcHalo)]),
+    ("nc_codec_set_chunk_frames", C.c_int, [_P, C.c_int64]),
+    ("nc_codec_chunk_plan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(NcChunkPlan)]),
     ("nc_encodec_create", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int, C.POINTER(_P)]),
     ("nc_encodec_set_bandwidth", C.c_int, [_P, C.c_float]),
     ("nc_encodec_query", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32,
@@ -228,6 +243,16 @@ class ProfileMixin:
         """nc_codec_check_errors: device-side failures of an earlier device-pointer call (raises NcDeviceError); call it once the
         caller's own synchronisation (torch.cuda.synchronize) has made the stream idle."""
         check(lib().nc_codec_check_errors(self._h))
+
+    def set_chunk_frames(self, n: int) -> None:
+        """nc_codec_set_chunk_frames: NC_CHUNK_AUTO (0, default), NC_CHUNK_OFF (-1) or a chunk size in latent frames (long clips)."""
+        check(lib().nc_codec_set_chunk_frames(self._h, int(n)))
+
+    def chunk_plan(self, frames: int, decode: bool = False, B: int = 1) -> dict:
+        """nc_codec_chunk_plan: what a call on `frames` latent frames would do under the handle's chunk setting."""
+        p = NcChunkPlan()
+        check(lib().nc_codec_chunk_plan(self._h, 1 if decode else 0, int(B), int(frames), C.byref(p)))
+        return {k: int(getattr(p, k)) for k, _ in NcChunkPlan._fields_}
 
     def profile_enable(self, on: bool = True):
         check(lib().nc_codec_profile_enable(self._h, 1 if on else 0))

@@ -46,6 +46,13 @@ EncodecModel& as_encodec(nc_codec* h) {
     return static_cast<EncodecModel&>(*h->impl);
 }
 
+// the plan of a device-pointer call; arguments the one-shot call rejects by itself go there untouched
+template <class M>
+ChunkPlan plan_or_oneshot(const M& m, ChunkKind kind, int B, int64_t frames) {
+    if (B <= 0 || frames <= 0) return ChunkPlan{};
+    return m.chunk_plan(kind, B, frames);
+}
+
 void h2d(void* d, const void* h, size_t n, hipStream_t s) { NC_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); }
 void d2h(void* h, const void* d, size_t n, hipStream_t s) { NC_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s)); }
 
@@ -172,15 +179,28 @@ nc_status nc_dac_query(const nc_codec* h, int64_t T, int64_t* T_padded, int64_t*
 
 nc_status nc_dac_encode_dev(nc_codec* h, const float* pcm, int32_t B, int64_t T, int32_t sample_rate, int32_t n_q, int64_t* codes,
                             float* z, float* latents) {
-    return guard([&] { as_dac(h).encode_dev(pcm, B, T, sample_rate, n_q, codes, z, latents); });
+    return guard([&] {
+        DacModel& m = as_dac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_ENCODE, B, T > 0 ? m.frames(T) : 0); P.n_chunks > 1)
+            return m.encode_chunked(P, false, pcm, B, T, sample_rate, n_q, codes, z, latents, nullptr);
+        m.encode_dev(pcm, B, T, sample_rate, n_q, codes, z, latents);
+    });
 }
 
 nc_status nc_dac_decode_dev(nc_codec* h, const float* z, int32_t B, int64_t frames, float* pcm) {
-    return guard([&] { as_dac(h).decode_dev(z, B, frames, pcm); });
+    return guard([&] {
+        DacModel& m = as_dac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_DECODE, B, frames); P.n_chunks > 1) return m.decode_chunked(P, false, z, nullptr, 0, B, frames, pcm);
+        m.decode_dev(z, B, frames, pcm);
+    });
 }
 
 nc_status nc_dac_from_codes_dev(nc_codec* h, const int64_t* codes, int32_t B, int32_t n_q, int64_t frames, float* z) {
-    return guard([&] { as_dac(h).from_codes_dev(codes, B, n_q, frames, z); });
+    return guard([&] {
+        DacModel& m = as_dac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_FROM_CODES, B, frames); P.n_chunks > 1) return m.from_codes_chunked(P, false, codes, B, n_q, frames, z);
+        m.from_codes_dev(codes, B, n_q, frames, z);
+    });
 }
 
 nc_status nc_dac_encode(nc_codec* h, const float* pcm, int32_t B, int64_t T, int32_t sample_rate, int32_t n_q, int64_t* codes,
@@ -193,6 +213,11 @@ nc_status nc_dac_encode(nc_codec* h, const float* pcm, int32_t B, int64_t T, int
         OwnStreamScope own(m);
         const int nq = (n_q <= 0 || n_q > m.cfg.n_codebooks) ? m.cfg.n_codebooks : n_q;
         const int64_t Tz = m.frames(T);
+        if (const ChunkPlan P = m.chunk_plan(CK_ENCODE, B, Tz); P.n_chunks > 1) {   // long clip: upload / download per chunk
+            m.encode_chunked(P, true, pcm, B, T, sample_rate, n_q, codes, z, latents, nullptr);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_in = (size_t)B * T * 4, n_codes = (size_t)B * nq * Tz * 8, n_z = (size_t)B * m.latent * Tz * 4,
                      n_lat = (size_t)B * nq * m.cfg.codebook_dim * Tz * 4;
         m.h_in.reserve(n_in); m.h_codes.reserve(n_codes); m.h_aux0.reserve(n_z); m.h_aux1.reserve(n_lat);
@@ -212,6 +237,11 @@ nc_status nc_dac_decode(nc_codec* h, const float* z, int32_t B, int64_t frames, 
         if (B <= 0 || frames <= 0) fail(NC_EINVAL, "B and frames must be positive");
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_DECODE, B, frames); P.n_chunks > 1) {
+            m.decode_chunked(P, true, z, nullptr, 0, B, frames, pcm);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_z = (size_t)B * m.latent * frames * 4, n_out = (size_t)B * m.decoded_len(frames) * 4;
         m.h_aux0.reserve(n_z); m.h_out.reserve(n_out);
         h2d(m.h_aux0.p, z, n_z, m.stream);
@@ -228,6 +258,11 @@ nc_status nc_dac_from_codes(nc_codec* h, const int64_t* codes, int32_t B, int32_
         if (B <= 0 || frames <= 0 || n_q <= 0) fail(NC_EINVAL, "bad codes shape");
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_FROM_CODES, B, frames); P.n_chunks > 1) {
+            m.from_codes_chunked(P, true, codes, B, n_q, frames, z);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_codes = (size_t)B * n_q * frames * 8, n_z = (size_t)B * m.latent * frames * 4;
         m.h_codes.reserve(n_codes); m.h_aux0.reserve(n_z);
         h2d(m.h_codes.p, codes, n_codes, m.stream);
@@ -238,10 +273,19 @@ nc_status nc_dac_from_codes(nc_codec* h, const int64_t* codes, int32_t B, int32_
 }
 
 nc_status nc_dac_decode_code_matrix_dev(nc_codec* h, const int64_t* codes_tq, int32_t B, int64_t frames, int32_t n_q, float* pcm) {
-    return guard([&] { as_dac(h).decode_code_matrix_dev(codes_tq, B, frames, n_q, pcm); });
+    return guard([&] {
+        DacModel& m = as_dac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_DECODE, B, frames); P.n_chunks > 1) return m.decode_chunked(P, false, nullptr, codes_tq, n_q, B, frames, pcm);
+        m.decode_code_matrix_dev(codes_tq, B, frames, n_q, pcm);
+    });
 }
 nc_status nc_dac_encode_code_matrix_dev(nc_codec* h, const float* pcm, int32_t B, int64_t T, int32_t sample_rate, int64_t* codes_tq) {
-    return guard([&] { as_dac(h).encode_code_matrix_dev(pcm, B, T, sample_rate, codes_tq); });
+    return guard([&] {
+        DacModel& m = as_dac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_ENCODE, B, T > 0 ? m.frames(T) : 0); P.n_chunks > 1)
+            return m.encode_chunked(P, false, pcm, B, T, sample_rate, 0, nullptr, nullptr, nullptr, codes_tq);
+        m.encode_code_matrix_dev(pcm, B, T, sample_rate, codes_tq);
+    });
 }
 nc_status nc_dac_decode_code_matrix(nc_codec* h, const int64_t* codes_tq, int32_t B, int64_t frames, int32_t n_q, float* pcm) {
     return guard([&] {
@@ -250,6 +294,11 @@ nc_status nc_dac_decode_code_matrix(nc_codec* h, const int64_t* codes_tq, int32_
         if (B <= 0 || frames <= 0 || n_q <= 0) fail(NC_EINVAL, "bad code matrix shape");
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_DECODE, B, frames); P.n_chunks > 1) {
+            m.decode_chunked(P, true, nullptr, codes_tq, n_q, B, frames, pcm);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_codes = (size_t)B * n_q * frames * 8, n_out = (size_t)B * m.decoded_len(frames) * 4;
         m.h_codes.reserve(n_codes); m.h_out.reserve(n_out);
         h2d(m.h_codes.p, codes_tq, n_codes, m.stream);
@@ -265,6 +314,11 @@ nc_status nc_dac_encode_code_matrix(nc_codec* h, const float* pcm, int32_t B, in
         if (B <= 0 || T <= 0) fail(NC_EINVAL, "B and T must be positive");
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_ENCODE, B, m.frames(T)); P.n_chunks > 1) {
+            m.encode_chunked(P, true, pcm, B, T, sample_rate, 0, nullptr, nullptr, nullptr, codes_tq);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_in = (size_t)B * T * 4, n_codes = (size_t)B * m.cfg.n_codebooks * m.frames(T) * 8;
         m.h_in.reserve(n_in); m.h_codes.reserve(n_codes);
         h2d(m.h_in.p, pcm, n_in, m.stream);
@@ -312,7 +366,12 @@ nc_status nc_snac_noise_len(const nc_codec* h, int32_t B, int64_t frames, int64_
 }
 
 nc_status nc_snac_encode_dev(nc_codec* h, const float* pcm, int32_t B, int64_t T, int64_t* codes, float* z, float* zq) {
-    return guard([&] { as_snac(h).encode_dev(pcm, B, T, codes, z, zq); });
+    return guard([&] {
+        SnacModel& m = as_snac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_ENCODE, B, T > 0 ? m.padded_len(T) / m.hop : 0); P.n_chunks > 1)
+            return m.encode_chunked(P, false, pcm, B, T, codes, z, zq);
+        m.encode_dev(pcm, B, T, codes, z, zq);
+    });
 }
 nc_status nc_snac_encode_tensor_dev(nc_codec* h, const float* pcm, int32_t B, int64_t T, int64_t* codes, float* z, float* zq) {
     return guard([&] { as_snac(h).encode_dev(pcm, B, T, codes, z, zq, false); });
@@ -329,11 +388,19 @@ nc_status nc_snac_query_tensor(const nc_codec* h, int64_t T, int64_t* frames, in
     });
 }
 nc_status nc_snac_from_codes_dev(nc_codec* h, const int64_t* codes, int32_t B, int64_t frames, float* zq) {
-    return guard([&] { as_snac(h).from_codes_dev(codes, B, frames, zq); });
+    return guard([&] {
+        SnacModel& m = as_snac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_FROM_CODES, B, frames); P.n_chunks > 1) return m.from_codes_chunked(P, false, codes, B, frames, zq);
+        m.from_codes_dev(codes, B, frames, zq);
+    });
 }
 nc_status nc_snac_decode_dev(nc_codec* h, const int64_t* codes, int32_t B, int64_t frames, const float* noise, uint64_t seed,
                              float* pcm) {
-    return guard([&] { as_snac(h).decode_dev(codes, B, frames, noise, seed, pcm); });
+    return guard([&] {
+        SnacModel& m = as_snac(h);
+        if (const ChunkPlan P = plan_or_oneshot(m, CK_DECODE, B, frames); P.n_chunks > 1) return m.decode_chunked(P, false, codes, B, frames, noise, seed, pcm);
+        m.decode_dev(codes, B, frames, noise, seed, pcm);
+    });
 }
 
 static void snac_encode_host(nc_codec* h, const float* pcm, int32_t B, int64_t T, int64_t* codes, float* z, float* zq, bool pad) {
@@ -343,6 +410,12 @@ static void snac_encode_host(nc_codec* h, const float* pcm, int32_t B, int64_t T
     m.use_device();
     OwnStreamScope own(m);
     const int64_t Tz = pad ? m.padded_len(T) / m.hop : m.unpadded_frames(T);
+    if (pad)   // (the un-padded Tensor overload is never chunked)
+        if (const ChunkPlan P = m.chunk_plan(CK_ENCODE, B, Tz); P.n_chunks > 1) {
+            m.encode_chunked(P, true, pcm, B, T, codes, z, zq);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
     const size_t n_in = (size_t)B * T * 4, n_codes = (size_t)B * m.codes_per_clip(Tz) * 8, n_z = (size_t)B * m.latent * Tz * 4;
     m.h_in.reserve(n_in); m.h_codes.reserve(n_codes); m.h_aux0.reserve(n_z); m.h_aux1.reserve(n_z);
     h2d(m.h_in.p, pcm, n_in, m.stream);
@@ -367,6 +440,11 @@ nc_status nc_snac_from_codes(nc_codec* h, const int64_t* codes, int32_t B, int64
         if (B <= 0 || frames <= 0) fail(NC_EINVAL, "B and frames must be positive");
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_FROM_CODES, B, frames); P.n_chunks > 1) {
+            m.from_codes_chunked(P, true, codes, B, frames, zq);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_codes = (size_t)B * m.codes_per_clip(frames) * 8, n_z = (size_t)B * m.latent * frames * 4;
         m.h_codes.reserve(n_codes); m.h_aux0.reserve(n_z);
         h2d(m.h_codes.p, codes, n_codes, m.stream);
@@ -384,6 +462,11 @@ nc_status nc_snac_decode(nc_codec* h, const int64_t* codes, int32_t B, int64_t f
         if (B <= 0 || frames <= 0) fail(NC_EINVAL, "Codes list cannot be empty");   // ArgumentException, SNAC.cs:177-180
         m.use_device();
         OwnStreamScope own(m);
+        if (const ChunkPlan P = m.chunk_plan(CK_DECODE, B, frames); P.n_chunks > 1) {
+            m.decode_chunked(P, true, codes, B, frames, noise, seed, pcm);
+            NC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
         const size_t n_codes = (size_t)B * m.codes_per_clip(frames) * 8, n_out = (size_t)B * m.decoded_len(frames) * 4;
         const size_t n_noise = (size_t)m.noise_len(B, frames) * 4;
         m.h_codes.reserve(n_codes); m.h_out.reserve(n_out);

@@ -5,6 +5,7 @@
 #include <set>
 
 #include "nc_conv.h"
+#include "nc_limits.h"
 
 namespace nc {
 
@@ -745,11 +746,11 @@ void launch_conv(const ConvLayer& L, const ConvIO& io, int B, hipStream_t stream
     if (L.sub_stride && !L.sub_shift) {
         if (io.epi & EPI_NOISE) fail(NC_ESTATE, "internal: noise epilogue on the multiply-shift sub-pixel form");
         a.sub_stride = L.sub_stride; a.sub_cout = L.Cout; a.sub_magic = magic_div(L.sub_stride, L.rows() + 256);
-        if ((int64_t)(L.Cout + 4) * io.y_cstride + Tout + 3 * io.y_bstride >= (int64_t)1 << 31)
+        if (!conv_subpixel_fits32(L.Cout, io.y_cstride, io.y_bstride, Tout))
             fail(NC_EUNSUPPORTED, "conv output of %lld samples per row exceeds the 32-bit offsets of the sub-pixel form", (long long)io.y_cstride);
     }
     a.Tout = (int32_t)Tout;
-    if ((int64_t)(c.BM() + 4) * io.y_cstride + Tout >= (int64_t)1 << 31)
+    if (!conv_rows_fit32(c.BM(), io.y_cstride, Tout))
         fail(NC_EUNSUPPORTED, "conv output rows of %lld samples exceed the 32-bit tile offsets", (long long)io.y_cstride);
     int sx;  // x step per output column
     if (L.transposed) {

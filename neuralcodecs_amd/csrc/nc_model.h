@@ -48,6 +48,14 @@ void launch_vq_gather(const Codebook& cb, const int64_t* codes, int64_t codes_bs
                       Profiler* prof);
 
 // ---- codec objects ---------------------------------------------------------------------------
+// How one call is cut along the frame axis (nc_chunk.hip).  n_chunks == 1: the one-shot launch sequence.
+struct ChunkPlan {
+    int64_t n_chunks = 1, chunk = 0, halo_l = 0, halo_r = 0;
+    int64_t arena_bytes = 0;
+};
+enum ChunkKind { CK_ENCODE = 0, CK_DECODE = 1, CK_FROM_CODES = 2 };
+void launch_copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipStream_t s);
+
 struct Codec {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -56,6 +64,12 @@ struct Codec {
     int cu_count = 0;              // compute units of the device (multiProcessorCount)
     size_t lds_per_cu = 0;         // LDS a workgroup may opt into (maxSharedMemoryPerMultiProcessor)
     Profiler prof;
+    // long clips (nc_chunk.hip): NC_CHUNK_AUTO (0) / NC_CHUNK_OFF (-1) / chunk size in latent frames, and the dense per-window buffers
+    int64_t chunk_frames = 0;
+    DevBuf ck_in, ck_codes, ck_a, ck_b, ck_out, ck_noise, ck_noise_full;
+    // rows x width bytes between two pitched arrays on `stream`; either side may be a host pointer (then a 2-D memcpy), device to
+    // device is the copy kernel of nc_util.hip.  All sizes are multiples of 4 bytes.
+    void copy2d(void* dst, bool dst_host, size_t dpitch, const void* src, bool src_host, size_t spitch, size_t width, size_t rows);
     virtual ~Codec();
     virtual void load(const Blob& blob) = 0;
     void init_device(int device_index);
@@ -123,6 +137,12 @@ struct DacModel : Codec {
     void from_codes_dev(const int64_t* codes, int B, int n_q, int64_t frames, float* z);
     void decode_code_matrix_dev(const int64_t* codes_tq, int B, int64_t frames, int n_q, float* pcm);
     void encode_code_matrix_dev(const float* pcm, int B, int64_t T, int sample_rate, int64_t* codes_tq);
+    // long clips (nc_chunk.hip): the same calls run window by window; `host`: the caller's arrays are host pointers
+    ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
+    void encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z,
+                        float* latents, int64_t* codes_tq);
+    void decode_chunked(const ChunkPlan& P, bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t frames, float* pcm);
+    void from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int n_q, int64_t frames, float* z);
 
   private:
     float* run_res_unit(ResUnit& ru, int dil, float* cur, int C, int64_t L, int B, int& cur_idx, const float* alpha_next);
@@ -186,6 +206,11 @@ struct SnacModel : Codec {
     int64_t unpadded_frames(int64_t T) const;
     void from_codes_dev(const int64_t* codes, int B, int64_t frames, float* zq);
     void decode_dev(const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
+    // long clips (nc_chunk.hip)
+    ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
+    void encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq);
+    void from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t frames, float* zq);
+    void decode_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
 
   private:
     void load_res_unit(const Blob& b, const std::string& q, ResUnit& ru, int C, int dil);

@@ -260,4 +260,24 @@ Profiler::~Profiler() {
     for (auto e : pool) (void)hipEventDestroy(e);
 }
 
+// ---- pitched copy (long clips, nc_chunk.hip) ------------------------------------------------------
+// rows of `width_w` 32-bit words between two pitched device arrays: the window gather / kept-column scatter of the chunked calls.
+__global__ void copy_rows_kernel(const uint32_t* __restrict__ src, int64_t spitch_w, uint32_t* __restrict__ dst, int64_t dpitch_w, int64_t width_w,
+                                 int64_t rows) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * width_w) return;
+    const int64_t r = i / width_w, c = i - r * width_w;
+    dst[r * dpitch_w + c] = src[r * spitch_w + c];
+}
+
+void launch_copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipStream_t s) {
+    if (!width || !rows) return;
+    if ((dpitch | spitch | width) & 3 || width > dpitch || width > spitch) fail(NC_ESTATE, "internal: pitched copy of %zu bytes per row (pitches %zu, %zu)", width, spitch, dpitch);
+    const int64_t n = (int64_t)rows * (int64_t)(width / 4), grid = (n + 255) / 256;
+    if (grid > 0x7fffffff) fail(NC_EUNSUPPORTED, "pitched copy of %lld words exceeds one grid", (long long)n);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)grid), dim3(256), 0, s, static_cast<const uint32_t*>(src), (int64_t)(spitch / 4),
+                       static_cast<uint32_t*>(dst), (int64_t)(dpitch / 4), (int64_t)(width / 4), (int64_t)rows);
+    NC_HIP(hipGetLastError());
+}
+
 }  // namespace nc

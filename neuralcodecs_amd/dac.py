@@ -32,21 +32,33 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+def _c_config(config: DACConfig) -> "_lib.NcDacConfig":
+    c = _lib.NcDacConfig()
+    c.sample_rate, c.encoder_dim, c.decoder_dim = config.sample_rate, config.encoder_dim, config.decoder_dim
+    c.n_encoder_rates, c.n_decoder_rates = len(config.encoder_rates), len(config.decoder_rates)
+    for i, r in enumerate(config.encoder_rates):
+        c.encoder_rates[i] = r
+    for i, r in enumerate(config.decoder_rates):
+        c.decoder_rates[i] = r
+    c.latent_dim = config.latent_dim or 0
+    c.n_codebooks, c.codebook_size, c.codebook_dim = config.n_codebooks, config.codebook_size, config.codebook_dim
+    return c
+
+
+def dac_halo(config: DACConfig) -> dict:
+    """nc_dac_halo: the frames a chunk of a long clip recomputes on each side, derived from the config alone (no device needed)."""
+    h = _lib.NcHalo()
+    _lib.check(_lib.lib().nc_dac_halo(C.byref(_c_config(config)), C.byref(h)))
+    return {k: int(getattr(h, k)) for k, _ in _lib.NcHalo._fields_}
+
+
 class DAC(_lib.ProfileMixin):
     def __init__(self, config: Optional[DACConfig] = None, device_index: int = 0):
         if config is None:
             raise ValueError("config must not be null")  # ArgumentNullException.ThrowIfNull(config)
         self.config = config
         self.device_index = device_index
-        c = _lib.NcDacConfig()
-        c.sample_rate, c.encoder_dim, c.decoder_dim = config.sample_rate, config.encoder_dim, config.decoder_dim
-        c.n_encoder_rates, c.n_decoder_rates = len(config.encoder_rates), len(config.decoder_rates)
-        for i, r in enumerate(config.encoder_rates):
-            c.encoder_rates[i] = r
-        for i, r in enumerate(config.decoder_rates):
-            c.decoder_rates[i] = r
-        c.latent_dim = config.latent_dim or 0
-        c.n_codebooks, c.codebook_size, c.codebook_dim = config.n_codebooks, config.codebook_size, config.codebook_dim
+        c = _c_config(config)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().nc_dac_create(C.byref(c), device_index, C.byref(self._h)))
         self.latent_dim = config.resolved_latent_dim

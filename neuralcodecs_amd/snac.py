@@ -32,25 +32,37 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+def _c_config(config: SNACConfig) -> "_lib.NcSnacConfig":
+    c = _lib.NcSnacConfig()
+    c.sample_rate, c.encoder_dim, c.decoder_dim = config.sampling_rate, config.encoder_dim, config.decoder_dim
+    c.n_encoder_rates, c.n_decoder_rates, c.n_vq_strides = len(config.encoder_rates), len(config.decoder_rates), len(config.vq_strides)
+    for i, r in enumerate(config.encoder_rates):
+        c.encoder_rates[i] = r
+    for i, r in enumerate(config.decoder_rates):
+        c.decoder_rates[i] = r
+    for i, r in enumerate(config.vq_strides):
+        c.vq_strides[i] = r
+    c.latent_dim = config.latent_dim or 0
+    c.attn_window_size = config.attn_window_size or 0
+    c.codebook_size, c.codebook_dim = config.codebook_size, config.codebook_dim
+    c.noise, c.depthwise = int(config.noise), int(config.depthwise)
+    return c
+
+
+def snac_halo(config: SNACConfig) -> dict:
+    """nc_snac_halo: the frames a chunk of a long clip recomputes on each side, derived from the config alone (no device needed)."""
+    h = _lib.NcHalo()
+    _lib.check(_lib.lib().nc_snac_halo(C.byref(_c_config(config)), C.byref(h)))
+    return {k: int(getattr(h, k)) for k, _ in _lib.NcHalo._fields_}
+
+
 class SNAC(_lib.ProfileMixin):
     def __init__(self, config: Optional[SNACConfig] = None, device_index: int = 0):
         if config is None:
             raise ValueError("config must not be null")
         self.config = config
         self.device_index = device_index
-        c = _lib.NcSnacConfig()
-        c.sample_rate, c.encoder_dim, c.decoder_dim = config.sampling_rate, config.encoder_dim, config.decoder_dim
-        c.n_encoder_rates, c.n_decoder_rates, c.n_vq_strides = len(config.encoder_rates), len(config.decoder_rates), len(config.vq_strides)
-        for i, r in enumerate(config.encoder_rates):
-            c.encoder_rates[i] = r
-        for i, r in enumerate(config.decoder_rates):
-            c.decoder_rates[i] = r
-        for i, r in enumerate(config.vq_strides):
-            c.vq_strides[i] = r
-        c.latent_dim = config.latent_dim or 0
-        c.attn_window_size = config.attn_window_size or 0
-        c.codebook_size, c.codebook_dim = config.codebook_size, config.codebook_dim
-        c.noise, c.depthwise = int(config.noise), int(config.depthwise)
+        c = _c_config(config)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().nc_snac_create(C.byref(c), device_index, C.byref(self._h)))
         self.latent_dim = config.resolved_latent_dim

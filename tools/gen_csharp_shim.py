@@ -80,6 +80,28 @@ def parse_header(path=HDR):
     return enums, structs, funcs, defines
 
 
+def parse_result_structs(path=HDR):
+    """The tagged structs of the header (`typedef struct nc_x { ... } nc_x;`): plain result records the engine fills in (nc_halo,
+    nc_chunk_plan), as opposed to the untagged config / descriptor structs parse_header lists.  Same (name, fields) shape."""
+    src = strip_comments(open(path).read())
+    out = []
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        fields = []
+        for decl in m.group(2).split(";"):
+            decl = " ".join(decl.split())
+            if not decl:
+                continue
+            ty, rest = decl.split(" ", 1)
+            fields += [(ty, nm.strip(), 0) for nm in rest.split(",")]
+        out.append((m.group(3), fields))
+    return out
+
+
+def parse_signed_defines(path=HDR):
+    """`#define NC_X (-1)`: the negative constants parse_header's unsigned pattern leaves out"""
+    return [(m.group(1), int(m.group(2))) for m in re.finditer(r"#define\s+(NC_[A-Z_]+)\s+\((-\d+)\)", strip_comments(open(path).read()))]
+
+
 def cs_struct_name(c):
     return pascal(c)            # nc_dac_config -> NcDacConfig
 
@@ -311,7 +333,7 @@ def generate():
     errs, _ = check_templates(funcs)
     if errs:
         raise SystemExit("gen_csharp_shim: " + "; ".join(errs))
-    return {"NcMi355x.cs": gen_native(enums, structs, funcs, defines)}
+    return {"NcMi355x.cs": gen_native(enums, structs + parse_result_structs(), funcs, defines + parse_signed_defines())}
 
 
 if __name__ == "__main__":
