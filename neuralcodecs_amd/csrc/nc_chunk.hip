@@ -1,4 +1,5 @@
-// Long clips: halo derivation, the chunk planner, and DAC / SNAC Encode / Decode / FromCodes run window by window.
+// Halo derivation, the chunk planner, and DAC / SNAC Encode / Decode / FromCodes run window by window: long clips in several windows,
+// and every host-pointer call (a clip that is not cut is one window, the ck_* buffers are its staging).
 //
 // DAC and SNAC are convolutional with a finite receptive field (SNAC's attention is local to non-overlapping windows), so a clip can be
 // cut along the frame axis: chunk j keeps frames [f0, f1) and runs the EXISTING launch sequence on the window
@@ -37,8 +38,8 @@
 // A chunk needs on its LEFT what a change reaches to its RIGHT: halo_left = *_right, halo_right = *_left.
 #include <algorithm>
 
+#include "nc_guard.h"
 #include "nc_limits.h"
-#include "nc_model.h"
 
 namespace nc {
 
@@ -132,6 +133,14 @@ Window window_of(const ChunkPlan& P, int64_t j, int64_t frames) {
 }
 int64_t max_window(const ChunkPlan& P, int64_t frames) { return std::min(frames, P.chunk + P.halo_l + P.halo_r); }
 
+// Plans a call of model m.  True: a device-pointer call that is not cut, which is the *_dev launch sequence on the caller's own arrays
+// with no window buffer in between.  Arguments that sequence rejects by itself go there untouched.
+template <class M>
+bool plan_call(const M& m, bool host, ChunkKind kind, int B, int64_t frames, ChunkPlan& P) {
+    if (B > 0 && frames > 0) P = m.chunk_plan(kind, B, frames);
+    return !host && P.n_chunks == 1;
+}
+
 }  // namespace
 
 void Codec::copy2d(void* dst, bool dst_host, size_t dpitch, const void* src, bool src_host, size_t spitch, size_t width, size_t rows) {
@@ -171,9 +180,10 @@ ChunkPlan DacModel::chunk_plan(ChunkKind kind, int B, int64_t Tz) const {
     return P;
 }
 
-// Encode (codes / z / latents) or, with codes_tq, Dia's Encode ([B, T', n_q] matrix, all codebooks)
-void DacModel::encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z,
-                              float* latents, int64_t* codes_tq) {
+void DacModel::encode(bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents, int64_t* codes_tq) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_ENCODE, B, T > 0 ? frames(T) : 0, P))
+        return codes_tq ? encode_code_matrix_dev(pcm, B, T, sample_rate, codes_tq) : encode_dev(pcm, B, T, sample_rate, n_q, codes, z, latents);
     if (!pcm || !(codes || codes_tq)) fail(NC_EINVAL, "pcm and codes must not be null");
     if (B <= 0 || T <= 0) fail(NC_EINVAL, "B and T must be positive");
     if (T > (int64_t)1 << 30) fail(NC_EINVAL, "clip too long");
@@ -201,7 +211,9 @@ void DacModel::encode_chunked(const ChunkPlan& P, bool host, const float* pcm, i
     }
 }
 
-void DacModel::from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int n_q, int64_t Tz, float* z) {
+void DacModel::from_codes(bool host, const int64_t* codes, int B, int n_q, int64_t Tz, float* z) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_FROM_CODES, B, Tz, P)) return from_codes_dev(codes, B, n_q, Tz, z);
     if (!codes || !z) fail(NC_EINVAL, "codes and z must not be null");
     if (B <= 0 || Tz <= 0 || n_q <= 0 || n_q > cfg.n_codebooks) fail(NC_EINVAL, "bad codes shape [%d,%d,%lld]", B, n_q, (long long)Tz);
     use_device();
@@ -216,8 +228,9 @@ void DacModel::from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* 
     }
 }
 
-// Decode(z), or with codes_tq Dia's Decode of a [B, T', n_q] code matrix
-void DacModel::decode_chunked(const ChunkPlan& P, bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t Tz, float* pcm) {
+void DacModel::decode(bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t Tz, float* pcm) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_DECODE, B, Tz, P)) return codes_tq ? decode_code_matrix_dev(codes_tq, B, Tz, n_q, pcm) : decode_dev(z, B, Tz, pcm);
     if (!(z || codes_tq) || !pcm) fail(NC_EINVAL, "z and pcm must not be null");
     if (B <= 0 || Tz <= 0) fail(NC_EINVAL, "B and frames must be positive");
     if (codes_tq && (n_q <= 0 || n_q > cfg.n_codebooks)) fail(NC_EINVAL, "bad code matrix shape [%d,%lld,%d]", B, (long long)Tz, n_q);
@@ -284,46 +297,43 @@ ChunkPlan SnacModel::chunk_plan(ChunkKind kind, int B, int64_t frames_in) const 
     return P;
 }
 
-void SnacModel::encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq) {
+void SnacModel::copy_levels(int64_t* dst, bool dst_host, int64_t Td, int64_t d0, const int64_t* src, bool src_host, int64_t Ts, int64_t s0, int64_t n, int B) {
+    const int64_t td = codes_per_clip(Td), ts = codes_per_clip(Ts);
+    if (n == Td && n == Ts) return copy2d(dst, dst_host, (size_t)td * 8, src, src_host, (size_t)ts * 8, (size_t)td * 8, (size_t)B);   // the window is the clip: the level blocks coincide
+    int64_t od = 0, os = 0;
+    for (int i = 0; i < cfg.n_vq_strides; ++i) {   // every level at its own rate
+        const int s = cfg.vq_strides[i];
+        copy2d(dst + od + d0 / s, dst_host, (size_t)td * 8, src + os + s0 / s, src_host, (size_t)ts * 8, (size_t)(n / s) * 8, (size_t)B);
+        od += Td / s; os += Ts / s;
+    }
+}
+
+void SnacModel::encode(bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_ENCODE, B, T > 0 ? padded_len(T) / hop : 0, P)) return encode_dev(pcm, B, T, codes, z, zq);
     if (!pcm || !codes) fail(NC_EINVAL, "pcm and codes must not be null");
     if (B <= 0 || T <= 0 || T > ((int64_t)1 << 30)) fail(NC_EINVAL, "B and T must be positive");
     use_device();
-    const int64_t Tz = padded_len(T) / hop, total = codes_per_clip(Tz);
+    const int64_t Tz = padded_len(T) / hop;
     for (int64_t j = 0; j < P.n_chunks; ++j) {
         const Window w = window_of(P, j, Tz);
         const int64_t s0 = w.w0 * hop, Tw = std::min(T, w.w1 * hop) - s0, Wf = w.w1 - w.w0, k0 = w.f0 - w.w0, n = w.f1 - w.f0;
-        const int64_t total_w = codes_per_clip(Wf);
         if (Tw <= 0 || padded_len(Tw) / hop != Wf) fail(NC_ESTATE, "internal: window of %lld samples does not give %lld frames", (long long)Tw, (long long)Wf);
         ck_in.reserve((size_t)B * Tw * 4);
-        ck_codes.reserve((size_t)B * total_w * 8);
+        ck_codes.reserve((size_t)B * codes_per_clip(Wf) * 8);
         if (z) ck_a.reserve((size_t)B * latent * Wf * 4);
         if (zq) ck_b.reserve((size_t)B * latent * Wf * 4);
         copy2d(ck_in.p, false, (size_t)Tw * 4, pcm + s0, host, (size_t)T * 4, (size_t)Tw * 4, (size_t)B);
         encode_dev(ck_in.as<float>(), B, Tw, ck_codes.as<int64_t>(), z ? ck_a.as<float>() : nullptr, zq ? ck_b.as<float>() : nullptr, true);
-        int64_t off = 0, off_w = 0;
-        for (int i = 0; i < cfg.n_vq_strides; ++i) {   // every level at its own rate
-            const int s = cfg.vq_strides[i];
-            copy2d(codes + off + w.f0 / s, host, (size_t)total * 8, ck_codes.as<int64_t>() + off_w + k0 / s, false, (size_t)total_w * 8, (size_t)(n / s) * 8, (size_t)B);
-            off += Tz / s; off_w += Wf / s;
-        }
+        copy_levels(codes, host, Tz, w.f0, ck_codes.as<int64_t>(), false, Wf, k0, n, B);
         if (z) copy2d(z + w.f0, host, (size_t)Tz * 4, ck_a.as<float>() + k0, false, (size_t)Wf * 4, (size_t)n * 4, (size_t)B * latent);
         if (zq) copy2d(zq + w.f0, host, (size_t)Tz * 4, ck_b.as<float>() + k0, false, (size_t)Wf * 4, (size_t)n * 4, (size_t)B * latent);
     }
 }
 
-// the window's slice of every level, laid side by side as the one-shot calls take them
-static void gather_levels(SnacModel& m, bool host, const int64_t* codes, int B, int64_t Tz, int64_t w0, int64_t Wf) {
-    const int64_t total = m.codes_per_clip(Tz), total_w = m.codes_per_clip(Wf);
-    m.ck_codes.reserve((size_t)B * total_w * 8);
-    int64_t off = 0, off_w = 0;
-    for (int i = 0; i < m.cfg.n_vq_strides; ++i) {
-        const int s = m.cfg.vq_strides[i];
-        m.copy2d(m.ck_codes.as<int64_t>() + off_w, false, (size_t)total_w * 8, codes + off + w0 / s, host, (size_t)total * 8, (size_t)(Wf / s) * 8, (size_t)B);
-        off += Tz / s; off_w += Wf / s;
-    }
-}
-
-void SnacModel::from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t Tz, float* zq_out) {
+void SnacModel::from_codes(bool host, const int64_t* codes, int B, int64_t Tz, float* zq_out) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_FROM_CODES, B, Tz, P)) return from_codes_dev(codes, B, Tz, zq_out);
     if (!codes || !zq_out) fail(NC_EINVAL, "codes and zq must not be null");
     if (B <= 0 || Tz <= 0) fail(NC_EINVAL, "B and frames must be positive");
     for (int i = 0; i < cfg.n_vq_strides; ++i)
@@ -332,46 +342,58 @@ void SnacModel::from_codes_chunked(const ChunkPlan& P, bool host, const int64_t*
     for (int64_t j = 0; j < P.n_chunks; ++j) {   // per pooling block: no halo, boundaries are multiples of align
         const Window w = window_of(P, j, Tz);
         const int64_t n = w.f1 - w.f0;
-        gather_levels(*this, host, codes, B, Tz, w.f0, n);
+        ck_codes.reserve((size_t)B * codes_per_clip(n) * 8);
         ck_a.reserve((size_t)B * latent * n * 4);
+        copy_levels(ck_codes.as<int64_t>(), false, n, 0, codes, host, Tz, w.f0, n, B);
         from_codes_dev(ck_codes.as<int64_t>(), B, n, ck_a.as<float>());
         copy2d(zq_out + w.f0, host, (size_t)Tz * 4, ck_a.p, false, (size_t)n * 4, (size_t)n * 4, (size_t)B * latent);
     }
 }
 
-void SnacModel::decode_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t Tz, const float* noise, uint64_t seed, float* pcm) {
+void SnacModel::decode(bool host, const int64_t* codes, int B, int64_t Tz, const float* noise, uint64_t seed, float* pcm) {
+    ChunkPlan P;
+    if (plan_call(*this, host, CK_DECODE, B, Tz, P)) return decode_dev(codes, B, Tz, noise, seed, pcm);
     if (!codes || !pcm) fail(NC_EINVAL, "codes and pcm must not be null");
     if (B <= 0 || Tz <= 0) fail(NC_EINVAL, "B and frames must be positive");
     for (int i = 0; i < cfg.n_vq_strides; ++i)
         if (Tz % cfg.vq_strides[i] != 0) fail(NC_EINVAL, "frame count %lld is not a multiple of vq stride %d", (long long)Tz, cfg.vq_strides[i]);
     use_device();
-    // NoiseBlock inputs: one [B,1,T_i] block per decoder stage, T_i = frames * (product of the strides so far).  Without caller noise
-    // the whole clip's noise is drawn from `seed` exactly as the one-shot call draws it (about the size of the PCM), then sliced.
+    // NoiseBlock inputs: one [B,1,T_i] block per decoder stage, T_i = frames * (product of the strides so far).  A window takes its
+    // slice of the caller's noise.  Without caller noise a window that is the whole clip leaves the draw from `seed` to the launch
+    // sequence; any other window slices the whole clip's noise, drawn once exactly as the launch sequence draws it (about the size of
+    // the PCM).
     const float* nz = noise;
     bool nz_host = host;
-    if (cfg.noise && !noise) {
-        const int64_t n = noise_len(B, Tz);
-        ck_noise_full.reserve((size_t)n * 4);
-        launch_randn(ck_noise_full.as<float>(), n, seed, stream);
-        nz = ck_noise_full.as<float>();
-        nz_host = false;
-    }
     const int64_t Lfull = decoded_len(Tz);   // = Tz * hop: every SNAC up-conv maps L -> L * s
     for (int64_t j = 0; j < P.n_chunks; ++j) {
         const Window w = window_of(P, j, Tz);
         const int64_t Wf = w.w1 - w.w0, Lw = decoded_len(Wf);
-        gather_levels(*this, host, codes, B, Tz, w.w0, Wf);
-        if (cfg.noise) {
-            ck_noise.reserve((size_t)noise_len(B, Wf) * 4);
-            int64_t S = 1, off = 0, off_w = 0;
-            for (int i = 0; i < cfg.n_decoder_rates; ++i) {
-                S *= cfg.decoder_rates[i];
-                copy2d(ck_noise.as<float>() + off_w, false, (size_t)Wf * S * 4, nz + off + w.w0 * S, nz_host, (size_t)Tz * S * 4, (size_t)Wf * S * 4, (size_t)B);
-                off += (int64_t)B * Tz * S; off_w += (int64_t)B * Wf * S;
+        ck_codes.reserve((size_t)B * codes_per_clip(Wf) * 8);
+        copy_levels(ck_codes.as<int64_t>(), false, Wf, 0, codes, host, Tz, w.w0, Wf, B);
+        const bool slice = cfg.noise && (noise || Wf != Tz);
+        if (slice) {
+            if (!nz) {
+                const int64_t n = noise_len(B, Tz);
+                ck_noise_full.reserve((size_t)n * 4);
+                launch_randn(ck_noise_full.as<float>(), n, seed, stream);
+                nz = ck_noise_full.as<float>();
+                nz_host = false;
+            }
+            const size_t n_w = (size_t)noise_len(B, Wf) * 4;
+            ck_noise.reserve(n_w);
+            if (Wf == Tz) {   // the window is the clip: the stage blocks coincide
+                copy2d(ck_noise.p, false, n_w, nz, nz_host, n_w, n_w, 1);
+            } else {
+                int64_t S = 1, off = 0, off_w = 0;
+                for (int i = 0; i < cfg.n_decoder_rates; ++i) {
+                    S *= cfg.decoder_rates[i];
+                    copy2d(ck_noise.as<float>() + off_w, false, (size_t)Wf * S * 4, nz + off + w.w0 * S, nz_host, (size_t)Tz * S * 4, (size_t)Wf * S * 4, (size_t)B);
+                    off += (int64_t)B * Tz * S; off_w += (int64_t)B * Wf * S;
+                }
             }
         }
         ck_out.reserve((size_t)B * Lw * 4);
-        decode_dev(ck_codes.as<int64_t>(), B, Wf, cfg.noise ? ck_noise.as<float>() : nullptr, seed, ck_out.as<float>());
+        decode_dev(ck_codes.as<int64_t>(), B, Wf, slice ? ck_noise.as<float>() : nullptr, seed, ck_out.as<float>());
         const int64_t Hs = Lfull / Tz, o0 = w.f0 * Hs, cnt = (w.f1 - w.f0) * Hs, k0 = (w.f0 - w.w0) * Hs;
         copy2d(pcm + o0, host, (size_t)Lfull * 4, ck_out.as<float>() + k0, false, (size_t)Lw * 4, (size_t)cnt * 4, (size_t)B);
     }
@@ -382,33 +404,17 @@ void SnacModel::decode_chunked(const ChunkPlan& P, bool host, const int64_t* cod
 // ================================================================================================ C ABI
 using namespace nc;
 
-namespace {
-template <class F>
-nc_status guard_host(F&& f) {
-    try {
-        f();
-        return NC_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return NC_ESTATE;
-    }
-}
-}  // namespace
-
 extern "C" {
 
 nc_status nc_dac_halo(const nc_dac_config* cfg, nc_halo* out) {
-    return guard_host([&] {
+    return guard([&] {
         if (!cfg || !out) fail(NC_EINVAL, "cfg and out must not be null");
         dac_halo(*cfg, out);
     });
 }
 
 nc_status nc_snac_halo(const nc_snac_config* cfg, nc_halo* out) {
-    return guard_host([&] {
+    return guard([&] {
         if (!cfg || !out) fail(NC_EINVAL, "cfg and out must not be null");
         if (cfg->attn_window_size < 0 || cfg->attn_window_size > 32) fail(NC_EINVAL, "attention window must be in 0..32");
         snac_halo(*cfg, out);
@@ -416,22 +422,21 @@ nc_status nc_snac_halo(const nc_snac_config* cfg, nc_halo* out) {
 }
 
 nc_status nc_codec_set_chunk_frames(nc_codec* h, int64_t chunk_frames) {
-    return guard_host([&] {
-        if (!h || !h->impl) fail(NC_EINVAL, "null codec handle");
-        if (h->kind == 2) fail(NC_EUNSUPPORTED, "Encodec handles are not chunked: 48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context");
+    return guard([&] {
+        Codec& c = codec_of(h);
+        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles are not chunked: 48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context");
         if (chunk_frames < NC_CHUNK_OFF) fail(NC_EINVAL, "chunk_frames must be NC_CHUNK_OFF (-1), NC_CHUNK_AUTO (0) or a positive frame count");
-        h->impl->chunk_frames = chunk_frames;
+        c.chunk_frames = chunk_frames;
     });
 }
 
 nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t B, int64_t frames, nc_chunk_plan* out) {
-    return guard_host([&] {
+    return guard([&] {
         if (!h || !h->impl || !out) fail(NC_EINVAL, "null argument");
-        if (h->kind == 2) fail(NC_EUNSUPPORTED, "Encodec handles are not chunked");
+        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles are not chunked");
         if (B <= 0 || frames <= 0) fail(NC_EINVAL, "B and frames must be positive");
         const ChunkKind kind = decode ? CK_DECODE : CK_ENCODE;
-        const ChunkPlan P = h->kind == 0 ? static_cast<const DacModel&>(*h->impl).chunk_plan(kind, B, frames)
-                                         : static_cast<const SnacModel&>(*h->impl).chunk_plan(kind, B, frames);
+        const ChunkPlan P = h->kind == DacModel::kKind ? as<DacModel>(h).chunk_plan(kind, B, frames) : as<SnacModel>(h).chunk_plan(kind, B, frames);
         out->n_chunks = P.n_chunks; out->chunk_frames = P.chunk; out->halo_left = P.halo_l; out->halo_right = P.halo_r;
         out->arena_bytes = P.arena_bytes;
     });

@@ -140,11 +140,6 @@ struct ConvLayer {
     // host: dense folded weight in the reference's layout ([Cout,Cin,K] or [Cin,Cout,K])
     void build(const float* dense_w, const float* bias_h, int Cin, int Cout, int K, int stride, int pad, int dil, int out_pad,
                bool transposed);
-    void release_all() {   // op-level hooks build throw-away layers
-        w.release(); bias.release(); w_skinny.release(); w_fused.release(); w_thin.release(); w_stem.release(); w_small.release();
-        for (auto& a : alts) a->w.release();
-        alts.clear();
-    }
     int64_t out_len(int64_t Tin) const;
     double flops(int B, int64_t Tin) const;
 };

@@ -48,7 +48,7 @@ void launch_vq_gather(const Codebook& cb, const int64_t* codes, int64_t codes_bs
                       Profiler* prof);
 
 // ---- codec objects ---------------------------------------------------------------------------
-// How one call is cut along the frame axis (nc_chunk.hip).  n_chunks == 1: the one-shot launch sequence.
+// How one call is cut along the frame axis (nc_chunk.hip).  n_chunks == 1: the window is the clip.
 struct ChunkPlan {
     int64_t n_chunks = 1, chunk = 0, halo_l = 0, halo_r = 0;
     int64_t arena_bytes = 0;
@@ -64,7 +64,8 @@ struct Codec {
     int cu_count = 0;              // compute units of the device (multiProcessorCount)
     size_t lds_per_cu = 0;         // LDS a workgroup may opt into (maxSharedMemoryPerMultiProcessor)
     Profiler prof;
-    // long clips (nc_chunk.hip): NC_CHUNK_AUTO (0) / NC_CHUNK_OFF (-1) / chunk size in latent frames, and the dense per-window buffers
+    // nc_chunk.hip: NC_CHUNK_AUTO (0) / NC_CHUNK_OFF (-1) / chunk size in latent frames, and the dense per-window buffers (grow-only).
+    // They are the staging buffers of every host-pointer call too: a clip that is not cut is one window.
     int64_t chunk_frames = 0;
     DevBuf ck_in, ck_codes, ck_a, ck_b, ck_out, ck_noise, ck_noise_full;
     // rows x width bytes between two pitched arrays on `stream`; either side may be a host pointer (then a 2-D memcpy), device to
@@ -92,6 +93,8 @@ struct OwnStreamScope {
 };
 
 struct DacModel : Codec {
+    static constexpr int kKind = 0;
+    static constexpr const char* kKindName = "a DAC";
     nc_dac_config cfg{};
     int latent = 0, hop = 1;
     bool fuse_res_units = true;  // NC_NO_FUSE=1 in the environment selects the two-launch residual units (A/B, tests)
@@ -124,31 +127,35 @@ struct DacModel : Codec {
     ConvLayer dec_out;
 
     // workspace (grow-only)
-    DevBuf act[3], resid, zq, lat, st, codes_ws, h_in, h_out, h_codes, h_aux0, h_aux1;
+    DevBuf act[3], resid, zq, lat, st, codes_ws;
 
     explicit DacModel(const nc_dac_config& c);
     void load(const Blob& blob) override;
     int64_t padded_len(int64_t T) const { return (T + hop - 1) / hop * hop; }
     int64_t frames(int64_t T) const { return (T + hop - 1) / hop; }
     int64_t decoded_len(int64_t frames) const;
-    // device-pointer entry points (async on `stream`)
+    // the launch sequences on device pointers (async on `stream`)
     void encode_dev(const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents);
     void decode_dev(const float* z, int B, int64_t frames, float* pcm);
     void from_codes_dev(const int64_t* codes, int B, int n_q, int64_t frames, float* z);
     void decode_code_matrix_dev(const int64_t* codes_tq, int B, int64_t frames, int n_q, float* pcm);
     void encode_code_matrix_dev(const float* pcm, int B, int64_t T, int sample_rate, int64_t* codes_tq);
-    // long clips (nc_chunk.hip): the same calls run window by window; `host`: the caller's arrays are host pointers
+    // The operations of the C ABI (nc_chunk.hip), async on `stream`.  `host`: the caller's arrays are host pointers.  Each plans the
+    // call and runs the launch sequence above window by window through the ck_* buffers; a device-pointer call that is not cut is the
+    // launch sequence on the caller's own arrays.  encode: codes / z / latents or, with codes_tq, Dia's [B, T', n_q] matrix of all
+    // codebooks; decode: from z or, with codes_tq, from such a matrix.
     ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
-    void encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z,
-                        float* latents, int64_t* codes_tq);
-    void decode_chunked(const ChunkPlan& P, bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t frames, float* pcm);
-    void from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int n_q, int64_t frames, float* z);
+    void encode(bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents, int64_t* codes_tq);
+    void decode(bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t frames, float* pcm);
+    void from_codes(bool host, const int64_t* codes, int B, int n_q, int64_t frames, float* z);
 
   private:
     float* run_res_unit(ResUnit& ru, int dil, float* cur, int C, int64_t L, int B, int& cur_idx, const float* alpha_next);
 };
 
 struct SnacModel : Codec {
+    static constexpr int kKind = 1;
+    static constexpr const char* kKindName = "a SNAC";
     nc_snac_config cfg{};
     int latent = 0, hop = 1;
     int64_t pad_to = 1;
@@ -186,7 +193,7 @@ struct SnacModel : Codec {
     DevBuf dec_alpha_out;
     ConvLayer dec_out;
 
-    DevBuf act[3], resid, zq, pooled, qbuf, lat, st, qkv_ws, noise_ws, h_in, h_out, h_codes, h_aux0, h_aux1, h_noise;
+    DevBuf act[3], resid, zq, pooled, qbuf, lat, st, qkv_ws, noise_ws;
 
     explicit SnacModel(const nc_snac_config& c);
     void load(const Blob& blob) override;
@@ -206,13 +213,15 @@ struct SnacModel : Codec {
     int64_t unpadded_frames(int64_t T) const;
     void from_codes_dev(const int64_t* codes, int B, int64_t frames, float* zq);
     void decode_dev(const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
-    // long clips (nc_chunk.hip)
+    // the operations of the C ABI (nc_chunk.hip), as DacModel's; encode is the padded form
     ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
-    void encode_chunked(const ChunkPlan& P, bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq);
-    void from_codes_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t frames, float* zq);
-    void decode_chunked(const ChunkPlan& P, bool host, const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
+    void encode(bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq);
+    void from_codes(bool host, const int64_t* codes, int B, int64_t frames, float* zq);
+    void decode(bool host, const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
 
   private:
+    // n frames of every code level from frame s0 of src ([B][codes_per_clip(Ts)]) to frame d0 of dst ([B][codes_per_clip(Td)])
+    void copy_levels(int64_t* dst, bool dst_host, int64_t Td, int64_t d0, const int64_t* src, bool src_host, int64_t Ts, int64_t s0, int64_t n, int B);
     void load_res_unit(const Blob& b, const std::string& q, ResUnit& ru, int C, int dil);
     void load_mha(const Blob& b, const std::string& p, Mha& m, int C);
     float* run_res_unit(ResUnit& ru, float* cur, int C, int64_t L, int B, int& cur_idx, const float* alpha_next);
@@ -221,6 +230,8 @@ struct SnacModel : Codec {
 };
 
 struct EncodecModel : Codec {
+    static constexpr int kKind = 2;
+    static constexpr const char* kKindName = "an Encodec";
     nc_encodec_config cfg{};
     int hop = 1, n_q = 1;
 
@@ -290,6 +301,10 @@ struct EncodecModel : Codec {
     int64_t frames_for(int64_t L) const;
     int64_t decoded_for(int64_t Tz) const;
     std::vector<Seg> segments(int64_t T) const;
+    int64_t decoded_len(const std::vector<Seg>& segs) const {   // samples of the clip decoded from these segments (overlap-add at segment_stride)
+        return cfg.segment_length <= 0 ? decoded_for(segs[0].frames)
+                                       : (int64_t)cfg.segment_stride * ((int64_t)segs.size() - 1) + decoded_for(segs.back().frames);
+    }
     void encode_dev(const float* pcm, int B, int64_t T, int64_t* codes, float* scales, float* emb);
     void decode_dev(const int64_t* codes, const float* scales, int B, int64_t T, int nq, float* pcm);
 
@@ -321,5 +336,5 @@ struct EncodecModel : Codec {
 // the opaque handle of the C ABI
 struct nc_codec {
     std::unique_ptr<nc::Codec> impl;
-    int kind = 0;  // 0 = DAC, 1 = SNAC, 2 = Encodec
+    int kind = 0;  // the model's kKind
 };

@@ -210,6 +210,99 @@ def test_snac_small_chunked_device_api():
         m.set_chunk_frames(_lib.NC_CHUNK_OFF)
 
 
+# ------------------------------------------------------------------------------------ one staging path for host-pointer calls
+# A host-pointer call that is not cut runs the window loop with the clip as its one window, on the same ck_* buffers as the chunked
+# calls; a device-pointer call that is not cut is the launch sequence on the caller's arrays.  Same fixtures, np.array_equal only.
+# Launches of the fixtures' one-shot encode / decode (profiled kernel classes) as counted on commit 3541718, the last one with the
+# hand-written host staging: a clip that is one window launches no more.
+PARENT_LAUNCHES = {"dac_small": (39, 30), "snac_small": (44, 44)}
+
+
+def _modes(h):
+    return [_lib.NC_CHUNK_OFF, 3 * h["align"], _lib.NC_CHUNK_AUTO, h["align"], _lib.NC_CHUNK_OFF]
+
+
+def test_dac_host_encode_without_optional_outputs(dac_small):
+    """z = NULL, latents = NULL: the merged path hands the launch sequence null where the hand-written branch handed it staging."""
+    d = dac_small
+    m, one, pcm = d["m"], d["one"], d["pcm"]
+    codes = np.full_like(one["codes"], -1)
+    _lib.check(_lib.lib().nc_dac_encode(m._h, pcm.ctypes.data, B, pcm.shape[-1], 0, 0, codes.ctypes.data, None, None))
+    assert np.array_equal(codes, one["codes"])
+
+
+def test_dac_one_handle_alternating_chunk_modes(dac_small):
+    """OFF, 3 * align, AUTO, align, OFF on one handle: the shared window buffers only grow and keep no stale bytes."""
+    d = dac_small
+    m, one, pcm = d["m"], d["one"], d["pcm"]
+    try:
+        for setting in _modes(d["h"]):
+            m.set_chunk_frames(setting)
+            z, codes, lat, _, _ = m.encode(pcm)
+            for got, key in ((z, "z"), (codes, "codes"), (lat, "lat"), (m.decode(one["z"]), "audio"), (m.from_codes(one["codes"]), "from_codes")):
+                assert np.array_equal(got, one[key]), (setting, key)
+    finally:
+        m.set_chunk_frames(_lib.NC_CHUNK_OFF)
+
+
+def test_dac_one_shot_launch_counts_host_and_device(dac_small):
+    """A one-shot host call launches what it launched before the host calls moved onto the window path (as does the fixture's), and the
+    device-pointer one-shot call launches the same (the pitched-copy kernel is outside the profiler: equal counts are what the existing
+    switches can show)."""
+    import torch
+    d = dac_small
+    m, one, pcm = d["m"], d["one"], d["pcm"]
+    (_, codes, _, _, _), n_enc = _launches(m, lambda: m.encode(pcm))
+    audio, n_dec = _launches(m, lambda: m.decode(one["z"]))
+    assert (n_enc, n_dec) == (one["n_enc"], one["n_dec"]) == PARENT_LAUNCHES["dac_small"]
+    dev = torch.device("cuda", m.device_index)
+    tp, tz = torch.from_numpy(pcm).to(dev), torch.from_numpy(one["z"]).to(dev)
+    (_, tcodes, _, _, _), n_enc_dev = _launches(m, lambda: m.encode(tp))
+    taudio, n_dec_dev = _launches(m, lambda: m.decode(tz))
+    assert (n_enc_dev, n_dec_dev) == (n_enc, n_dec)
+    assert np.array_equal(tcodes.cpu().numpy(), codes) and np.array_equal(taudio.cpu().numpy(), audio)
+
+
+def test_snac_host_encode_without_optional_outputs():
+    d = _snac_small("snac_small")
+    m, one, pcm = d["m"], d["one"], d["pcm"]
+    want = np.concatenate(one["codes"], axis=1)
+    codes = np.full_like(want, -1)
+    _lib.check(_lib.lib().nc_snac_encode(m._h, pcm.ctypes.data, B, pcm.shape[-1], codes.ctypes.data, None, None))
+    assert np.array_equal(codes, want)
+
+
+def test_snac_one_handle_alternating_chunk_modes():
+    d = _snac_small("snac_small")
+    m, one, pcm, noises = d["m"], d["one"], d["pcm"], d["noises"]
+    try:
+        for setting in _modes(d["h"]):
+            m.set_chunk_frames(setting)
+            codes, z, zq = m.encode(pcm, return_latents=True)
+            for a, b in zip(codes, one["codes"]):
+                assert np.array_equal(a, b), setting
+            for got, key in ((z, "z"), (zq, "zq"), (m.decode(one["codes"], noises), "audio"), (m.decode(one["codes"], None, seed=7), "audio_seed")):
+                assert np.array_equal(got, one[key]), (setting, key)
+    finally:
+        m.set_chunk_frames(_lib.NC_CHUNK_OFF)
+
+
+def test_snac_one_shot_launch_counts_host_and_device():
+    import torch
+    d = _snac_small("snac_small")
+    m, one, pcm, noises = d["m"], d["one"], d["pcm"], d["noises"]
+    codes, n_enc = _launches(m, lambda: m.encode(pcm))
+    audio, n_dec = _launches(m, lambda: m.decode(one["codes"], noises))
+    assert (n_enc, n_dec) == (one["n_enc"], one["n_dec"]) == PARENT_LAUNCHES["snac_small"]
+    dev = torch.device("cuda", m.device_index)
+    tp = torch.from_numpy(pcm).to(dev)
+    tc, tn = [torch.from_numpy(c).to(dev) for c in one["codes"]], [torch.from_numpy(n).to(dev) for n in noises]
+    tcodes, n_enc_dev = _launches(m, lambda: m.encode(tp))
+    taudio, n_dec_dev = _launches(m, lambda: m.decode(tc, tn))
+    assert (n_enc_dev, n_dec_dev) == (n_enc, n_dec)
+    assert all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(tcodes, codes)) and np.array_equal(taudio.cpu().numpy(), audio)
+
+
 def test_snac_fixtures_are_released():
     for d in _SNAC.values():
         d["m"].dispose()
