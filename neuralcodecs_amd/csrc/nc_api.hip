@@ -37,6 +37,22 @@ void on_own_stream(Codec& m, F&& f) {
 void h2d(void* d, const void* h, size_t n, hipStream_t s) { NC_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); }
 void d2h(void* h, const void* d, size_t n, hipStream_t s) { NC_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s)); }
 
+// A host-pointer Encodec call: `stage` queues the copies in, `run` the launch sequence on the staged arrays.  A timeout left behind by an
+// EARLIER device-pointer call is not this call's failure: take note of it (step-wise LSTM kernels from here on) and carry on; that call's
+// caller learns of it through nc_codec_check_errors / nc_codec_synchronize as documented.  A timeout of this call's own: run once more.
+template <class Stage, class Run>
+void encodec_host_call(EncodecModel& m, Stage&& stage, Run&& run) {
+    m.lstm.note_timeout();
+    stage();
+    for (int attempt = 0;; ++attempt) {
+        run();
+        NC_HIP(hipStreamSynchronize(m.stream));
+        if (!m.lstm.timed_out() || attempt) break;
+        try { m.check_async_errors(); } catch (const Error&) {}   // clears the word, switches the handle to the step-wise LSTM: run again
+    }
+    m.check_async_errors();
+}
+
 // ---- helpers of the op-level test hooks ----
 void op_set_device(int device_index) {
     int n = 0;
@@ -172,8 +188,8 @@ nc_status nc_codec_check_errors(nc_codec* h) {
 nc_status nc_encodec_lstm_stats(const nc_codec* h, int32_t* stepwise, int64_t* timeouts) {
     return guard([&] {
         EncodecModel& m = as<EncodecModel>(h);
-        if (stepwise) *stepwise = m.lstm_force_stepwise ? 1 : 0;
-        if (timeouts) *timeouts = m.lstm_timeouts;
+        if (stepwise) *stepwise = m.lstm.force_stepwise ? 1 : 0;
+        if (timeouts) *timeouts = m.lstm.timeouts;
     });
 }
 
@@ -462,19 +478,13 @@ nc_status nc_encodec_encode(nc_codec* h, const float* pcm, int32_t B, int64_t T,
         for (auto& s : segs) fr += s.frames;
         const size_t n_in = (size_t)B * m.cfg.channels * T * 4, n_codes = (size_t)B * m.n_q * fr * 8, n_sc = segs.size() * (size_t)B * 4,
                      n_emb = (size_t)B * m.cfg.dimension * fr * 4;
-        m.h_in.reserve(n_in); m.h_codes.reserve(n_codes); m.h_scales.reserve(n_sc); m.h_emb.reserve(n_emb);
-        m.absorb_stale_timeout();
-        h2d(m.h_in.p, pcm, n_in, m.stream);
-        for (int attempt = 0;; ++attempt) {
-            m.encode_dev(m.h_in.as<float>(), B, T, m.h_codes.as<int64_t>(), m.h_scales.as<float>(), emb ? m.h_emb.as<float>() : nullptr);
-            NC_HIP(hipStreamSynchronize(m.stream));
-            if (!m.lstm_timed_out() || attempt) break;
-            try { m.check_async_errors(); } catch (const Error&) {}   // clears the word, switches the handle to the step-wise LSTM: run again
-        }
-        m.check_async_errors();
-        d2h(codes, m.h_codes.p, n_codes, m.stream);
-        if (scales && m.cfg.normalize) d2h(scales, m.h_scales.p, n_sc, m.stream);
-        if (emb) d2h(emb, m.h_emb.p, n_emb, m.stream);
+        m.ck_in.reserve(n_in); m.ck_codes.reserve(n_codes); m.ck_a.reserve(n_sc); m.ck_b.reserve(n_emb);   // pcm, codes, scales, emb
+        encodec_host_call(m, [&] { h2d(m.ck_in.p, pcm, n_in, m.stream); }, [&] {
+            m.encode_dev(m.ck_in.as<float>(), B, T, m.ck_codes.as<int64_t>(), m.ck_a.as<float>(), emb ? m.ck_b.as<float>() : nullptr);
+        });
+        d2h(codes, m.ck_codes.p, n_codes, m.stream);
+        if (scales && m.cfg.normalize) d2h(scales, m.ck_a.p, n_sc, m.stream);
+        if (emb) d2h(emb, m.ck_b.p, n_emb, m.stream);
         NC_HIP(hipStreamSynchronize(m.stream));
     });
 }
@@ -492,18 +502,12 @@ nc_status nc_encodec_decode(nc_codec* h, const int64_t* codes, const float* scal
         for (auto& s : segs) fr += s.frames;
         const int64_t Lout = m.decoded_len(segs);
         const size_t n_codes = (size_t)B * n_q * fr * 8, n_sc = segs.size() * (size_t)B * 4, n_out = (size_t)B * m.cfg.channels * Lout * 4;
-        m.h_codes.reserve(n_codes); m.h_scales.reserve(n_sc); m.h_out.reserve(n_out);
-        m.absorb_stale_timeout();
-        h2d(m.h_codes.p, codes, n_codes, m.stream);
-        if (scales) h2d(m.h_scales.p, scales, n_sc, m.stream);
-        for (int attempt = 0;; ++attempt) {
-            m.decode_dev(m.h_codes.as<int64_t>(), scales ? m.h_scales.as<float>() : nullptr, B, T, n_q, m.h_out.as<float>());
-            NC_HIP(hipStreamSynchronize(m.stream));
-            if (!m.lstm_timed_out() || attempt) break;
-            try { m.check_async_errors(); } catch (const Error&) {}   // step-wise LSTM from here on: run again
-        }
-        m.check_async_errors();
-        d2h(pcm, m.h_out.p, n_out, m.stream);
+        m.ck_codes.reserve(n_codes); m.ck_a.reserve(n_sc); m.ck_out.reserve(n_out);   // codes, scales, pcm
+        encodec_host_call(m, [&] {
+            h2d(m.ck_codes.p, codes, n_codes, m.stream);
+            if (scales) h2d(m.ck_a.p, scales, n_sc, m.stream);
+        }, [&] { m.decode_dev(m.ck_codes.as<int64_t>(), scales ? m.ck_a.as<float>() : nullptr, B, T, n_q, m.ck_out.as<float>()); });
+        d2h(pcm, m.ck_out.p, n_out, m.stream);
         NC_HIP(hipStreamSynchronize(m.stream));
     });
 }

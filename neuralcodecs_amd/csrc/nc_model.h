@@ -5,12 +5,17 @@
 #include "nc_common.h"
 #include "nc_conv.h"
 #include "nc_elem.h"
+#include "nc_lstm.h"
 
 namespace nc {
 
 const char* get_last_error();
 void fold_weight_norm_dac(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
 void fold_weight_norm_snac(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
+inline void upload_f32(DevBuf& d, const float* h, size_t n) {   // n floats of the host into d, grown to hold them
+    d.reserve(n * sizeof(float));
+    NC_HIP(hipMemcpy(d.p, h, n * sizeof(float), hipMemcpyHostToDevice));
+}
 
 // ---- RVQ kernels (nc_rvq.hip) ----------------------------------------------------------------
 // Codebook resident on the device in the two layouts the kernels want.
@@ -40,12 +45,27 @@ bool launch_dac_rvq_fused(const RvqStage* stages_dev, int n_q, int L, int D, int
 void launch_vq_argmin(const Codebook& cb, const float* z_e, int64_t ze_bstride, int B, int64_t T, int64_t* codes,
                       int64_t codes_bstride, float* st, hipStream_t s, Profiler* prof);
 // codes -> out [B,D,T] = cb[codes]  (Embedding + transpose, VectorQuantizer.cs:135-142)
-// Test hook (nc_op_euclid_rvq): the Encodec Euclidean RVQ (ResidualVectorQuantizer.cs:133-157) on residual [B,D,T] (updated in place) with n_q
-// codebooks [n_q][N][D] (host): form 0 = the per-stage kernel, 1 = the all-stages matrix-core kernel (D == 128, N % 512 == 0)
-void op_euclid_rvq(const float* residual_in, int B, int D, int64_t T, const float* books_host, int n_q, int N, int form, int64_t* codes_host,
-                   float* residual_out);
 void launch_vq_gather(const Codebook& cb, const int64_t* codes, int64_t codes_bstride, int B, int64_t T, float* out, hipStream_t s,
                       Profiler* prof);
+
+// ---- Euclidean RVQ of Encodec (nc_euclid_rvq.hip) ----------------------------------------------
+constexpr int EUCLID_MAX_D = 128;   // widest code vector the kernels hold in LDS
+// The stages' codebooks as the kernels take them: device pointers per stage on the host (cb [N][D], cbT [D][N], c2 [N]) and as device arrays
+struct EuclidBooks {
+    int N = 0, D = 0;
+    std::vector<const float*> cb, cbT, c2;
+    DevBuf d_cb, d_cbT, d_c2;
+    void add(const Codebook& b);   // the next stage (all stages share N and D)
+    void upload();                 // after the last add
+};
+// ResidualVectorQuantizer.Encode (:133-157), first n_q stages: residual [B,D,T] -> codes [B,n_q,T].  form < 0: all stages in one matrix-core
+// launch where the shape has the instance (D == 128, N = 512 or 1024) and NC_EUCLID_NO_MFMA is unset, else one launch per stage (updates the
+// residual in place); form 0 / 1 force the per-stage / the matrix-core form (which fails on a shape it does not take).
+void launch_euclid_rvq(const EuclidBooks& bk, int n_q, int form, float* residual, int B, int64_t T, int64_t* codes, hipStream_t s);
+// ResidualVectorQuantizer.Decode (:107-124): codes [B,n_q,T] -> emb [B,D,T], the stages' code vectors added in ascending order
+void launch_emb_sum(const EuclidBooks& bk, const int64_t* codes, int n_q, int B, int64_t T, float* emb, hipStream_t s);
+// Test hook (nc_op_euclid_rvq): the quantizer on host arrays, residual [B,D,T] and n_q codebooks [n_q][N][D]; form as above, 0 or 1
+void op_euclid_rvq(const float* residual_in, int B, int D, int64_t T, const float* books_host, int n_q, int N, int form, int64_t* codes_host, float* residual_out);
 
 // ---- codec objects ---------------------------------------------------------------------------
 // How one call is cut along the frame axis (nc_chunk.hip).  n_chunks == 1: the window is the clip.
@@ -242,8 +262,6 @@ struct EncodecModel : Codec {
         DevBuf gamma, beta;
     };
     struct ResBlock { SConv c1, c2, sc; };
-    struct LstmLayer { ConvLayer ih; DevBuf whh, whhp, bhh, bih; };
-    struct Lstm { int C = 0; std::vector<std::unique_ptr<LstmLayer>> layers; };
     struct Plan { int64_t left = 0, right = 0, Lz = 0, Lp = 0, Lout = 0; };
     struct Seg { int64_t off = 0, len = 0, frames = 0; };
     struct Act {                   // [N,C,L] view of a raw conv output + its pending GroupNorm
@@ -259,42 +277,31 @@ struct EncodecModel : Codec {
     ResBlock enc_res[8], dec_res[8];
     Lstm enc_lstm, dec_lstm;
     std::vector<std::unique_ptr<Codebook>> books;
-    DevBuf book_ptrs, book_ptrsT, book_ptrs2;   // per stage: codebook [N][D], its transpose [D][N], squared norms [N] (device pointer arrays)
+    EuclidBooks book_tab;                        // their pointer tables (nc_euclid_rvq.hip)
 
     std::vector<std::unique_ptr<DevBuf>> pool;   // per-call intermediates, same allocation order every call (grow-only)
     size_t pool_i = 0;
-    DevBuf h_in, h_out, h_codes, h_scales, h_emb;
-    // Timeout word of the persistent LSTM kernels: ONE word of pinned, device-mapped host memory -- a kernel that gives up its spin
-    // writes it over PCIe, the host reads it without touching the stream.  After a timeout the handle runs the step-wise kernels
-    // (lstm_force_stepwise): the persistent form needs its workgroups co-resident, which a busy / partitioned device may not grant.
-    unsigned* lstm_tmo_host = nullptr;
-    unsigned* lstm_tmo_dev = nullptr;
-    bool lstm_force_stepwise = false;
-    int64_t lstm_timeouts = 0;                   // timeouts this handle has seen (nc_encodec_lstm_stats)
-    struct LstmTicket* lstm_ticket = nullptr;    // per-device serialisation of persistent LSTM sections across handles (nc_encodec.hip)
-    bool lstm_timed_out() const { return lstm_tmo_host && *reinterpret_cast<volatile unsigned*>(lstm_tmo_host) != 0; }
+    LstmRuntime lstm{*this};                     // timeout word, ticket, second stream and events of the LSTM launches (nc_lstm.hip)
     // segment groups of one call are independent until the overlap-add: the first runs on the handle's stream, the others on side
     // streams (forked / joined with events), so the short tail segment of a clip hides behind the full-length batch
     hipStream_t side_stream[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    // layer-pipelined LSTM (run_lstm): second stream for layer 1 and the chunk events; only the primary segment group pipelines
-    hipStream_t lstm_stream = nullptr;
-    std::vector<hipEvent_t> lstm_events;
     // overlap-add operands (decode_dev): the window and the weight sum depend on the frame geometry only and stay on the device;
     // the per-call frame pointers travel through a small ring of pinned host slots, so decode_dev never synchronises the stream
-    std::vector<int64_t> ola_key;
-    DevBuf ola_w, ola_sw;
-    void* ola_pin = nullptr;
-    size_t ola_slot_bytes = 0;
-    int ola_next = 0;
-    hipEvent_t ola_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ola_ev_used[4] = {false, false, false, false};
+    struct Ola {
+        std::vector<int64_t> key;
+        DevBuf w, sw;
+        void* pin = nullptr;
+        size_t slot_bytes = 0;
+        int next = 0;
+        hipEvent_t ev[4] = {};
+        bool ev_used[4] = {};
+    } ola;
     bool on_side_group = false;
     ~EncodecModel() override;
 
     explicit EncodecModel(const nc_encodec_config& c);
     void check_async_errors() override;
-    void absorb_stale_timeout();
     void load(const Blob& blob) override;
     void set_bandwidth(float bw);
     Plan plan_sconv(int64_t L, int k, int stride, int dil) const;
@@ -307,26 +314,34 @@ struct EncodecModel : Codec {
     }
     void encode_dev(const float* pcm, int B, int64_t T, int64_t* codes, float* scales, float* emb);
     void decode_dev(const int64_t* codes, const float* scales, int B, int64_t T, int nq, float* pcm);
+    float* alloc(size_t n_floats);   // the next buffer of the pool, grown to n_floats
 
   private:
     void load_sconv(const Blob& b, const std::string& key, SConv& L, int Cin, int Cout, int K, int stride, bool transposed);
     void load_resblock(const Blob& b, const std::string& key, ResBlock& r, int dim);
-    void load_lstm(const Blob& b, const std::string& key, Lstm& l, int C);
-    float* alloc(size_t n_floats);
     float* pad_act(const Act& a, const Act* b2, bool elu, int N, const Plan& pl);
     struct GnJob { bool on = false, fused = false, finished = false; int sub = 1, nrb = 0, ncb = 0; double* part = nullptr; float* stats = nullptr; };
     static constexpr int GN_MAX_SAMPLES = 4096;   // rows of a segment group (encode_dev caps a group at 4096)
     DevBuf gn_counters;                           // [3 groups][2][GN_MAX_SAMPLES] arrival counters of the in-launch GroupNorm finish (zero between launches; the second set: the
                                                   // branch output of the fused first pass of a residual block, two outputs finishing in one launch)
     int cur_group = 0;
+    unsigned* group_counters() { return gn_counters.as<unsigned>() + (size_t)cur_group * 2 * GN_MAX_SAMPLES; }   // the running segment group's set
+    bool gn_finishes_in_launch(int N) const;      // GroupNorm sums emitted by a launch over N rows can be finished inside it
     GnJob gn_begin(const ConvLayer& conv, ConvIO& io, int N, int C, int64_t L, int sub);
     const float* gn_end(const GnJob& j, const float* raw, int N, int C, int64_t L, int64_t rs = 0);   // rs: row pitch of `raw` (0 = dense rows of L)
+    // the streaming two-input kernels in front of sconv / sconvT: false = not this shape (nothing launched)
+    bool try_stream_down(SConv& L, const Act& a, const Act* b2, bool elu, int N, const Plan& pl, Act& out);
+    bool try_stream_up(SConv& L, const Act& a, const Act* b2, bool elu, int N, Act& out);
     Act sconv(SConv& L, const Act& a, const Act* b2, bool elu, int N);
     Act sconvT(SConv& L, const Act& a, const Act* b2, bool elu, int N);
     void resblock(ResBlock& r, const Act& x, int N, Act& s, Act& y);
     bool resblock_first_pass(ResBlock& r, const Act& x, int N, Act& s, Act& h);   // shortcut + k = 3 branch in one launch (nc_resa.hip); false: not this shape
     float* materialize(const Act& a, int N, const float* scale, int mode);
-    float* run_lstm(Lstm& l, const float* x, int N, int64_t T, bool elu_out);
+    // body(first, G) per group of consecutive segments with equal `key` (at most 4096 rows): the first on the handle's stream, the others on side streams
+    template <class Body>
+    void for_each_group(const std::vector<Seg>& segs, int B, int64_t Seg::*key, Body&& body);
+    void ola_tables(const std::vector<int64_t>& flen, int64_t stride, int64_t total);
+    char* ola_stage(const std::vector<const float*>& fp, const std::vector<int64_t>& flen);
     void encode_batch(const float* x, int N, int64_t L, int64_t Tz, int64_t* codes, float* scale_out, float* emb_out);
     float* decode_batch(const int64_t* codes, int N, int nq, int64_t Tz, const float* scale, int64_t* Lout);
 };

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Soak of the fence-free hand-offs (runs ON THE GPU BOX; test infrastructure).  VERDICT r4 item 7.
 
-The persistent LSTM's h exchange (csrc/nc_encodec.hip lstm_seq_kernel: write-through payload -> drain -> barrier -> relaxed flag; the
+The persistent LSTM's h exchange (csrc/nc_lstm.hip lstm_seq_kernel: write-through payload -> drain -> barrier -> relaxed flag; the
 consumer polls the flags and reads the payload with agent-scope loads, NO acquire fence) and the in-launch GroupNorm finish (csrc/nc_gn.h)
 are validated empirically: a stale read would be a silently wrong h / mean, not a timeout.  This tool runs `--iters` Encodec 48 kHz stereo
 encode + decode steps at the BASELINE C3 shape (16 x 2 s; ~300 LSTM time steps x 4 LSTM sections and ~130 GroupNorm finishes per step) and
