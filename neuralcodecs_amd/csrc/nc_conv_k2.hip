@@ -2,6 +2,6 @@
 // up to 20 prefetched window words per lane).
 #include "nc_conv_kernel.hip.h"
 NC_INSTANTIATE_CONV_K(2, 16, 20)
-NC_INSTANTIATE_CONV_NARROW(2, 16, 20)
-NC_INSTANTIATE_CONV_SUB(2, 16, 20)
-NC_INSTANTIATE_CONV_SUB_NARROW(2, 16, 20)
+NC_INSTANTIATE_CONV(narrow_k2, NC_ARGS_TM, TM * 10 + 1, NC_TILES_TN1, 2, 16, 20, false, 2, 3)
+NC_INSTANTIATE_CONV(sub_k2, NC_ARGS_TM_TN, TM * 10 + TN, NC_TILES_ALL, 2, 16, 20, false, 2, 4, false, 1)
+NC_INSTANTIATE_CONV(sub_narrow_k2, NC_ARGS_TM, TM * 10 + 1, NC_TILES_TN1, 2, 16, 20, false, 2, 3, false, 1)

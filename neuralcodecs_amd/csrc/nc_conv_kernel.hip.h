@@ -24,14 +24,6 @@ namespace nc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// a flag that is either a compile-time constant (std::true_type / std::false_type) or this run-time value
-struct nc_rt_flag {
-    bool v;
-    __device__ constexpr operator bool() const { return v; }
-};
-typedef __attribute__((address_space(1))) const void* nc_gptr;
-typedef __attribute__((address_space(3))) void* nc_lptr;
-
 // Block = NW waves (4, or 3 for the narrow variants).  Wave w owns all BM = 32*TM output channels of the tile and the
 // 32*TN columns [w*32*TN, (w+1)*32*TN).  The reduction runs over blocks of CB input channels
 // (KB = CB*K flattened kk = ci*K + k, ascending: the canonical chain order).  Per block the
@@ -79,7 +71,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     constexpr int A_FLOATS = KB * BM;
     constexpr int A_VEC = A_FLOATS / 4;            // float4 words in the weight tile
     constexpr int NA = (A_VEC + NT - 1) / NT;      // float4 copies per thread
-    constexpr bool A_DMA = false;
     constexpr int NSEG = DIST ? 2 : (KP >= 16 ? 4 : 2);
     constexpr int NG = NSEG - 1;
     constexpr int GA = (NA + NG - 1) / NG;         // per-group register footprint
@@ -194,14 +185,15 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     // loop-invariant part of the window reads: item i of this wave covers channel xc[i] (wave-uniform) of the reduction block and
     // the 64 window slots starting at xj[i]; its lanes read x[clamp(xs0 + slot)] = xg[i] of that channel row
     unsigned xg[NX];
-    int xc[NX];
+    int xc[DIST ? NX : 1];   // DIST: the item's channel, held (the other forms recompute it)
     unsigned okm = 0;   // bit i = window item i of this lane reads a real sample (else zero padding / the zero extension / tile overrun)
     if constexpr (!XVK)
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
         const int item = swave + NW * i;
-        xc[i] = (item * chunk_magic) >> 20;
-        const int jw = (item - xc[i] * nchunk) * 64 + lane;          // window slot of this lane
+        const int c = (item * chunk_magic) >> 20;
+        if constexpr (DIST) xc[i] = c;
+        const int jw = (item - c * nchunk) * 64 + lane;              // window slot of this lane
         const int sg = seg_of(col0 * s + jw, flat_px);               // its segment (0 without p.flat)
         const int gp = xs0 + jw - sg * flat_px;                      // x position within clip b + sg
         xg[i] = (unsigned)min(sg, p.Bc - 1 - b) * (unsigned)p.x_bstride + (unsigned)min(max(gp, 0), x_len - 1);   // (address stays inside the tensor)
@@ -231,21 +223,19 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     // is raised for that) and row lengths that are multiples of 4, so that a float4 is inside the row or outside it as a whole.
     // K = 7 (every launch whose rows start on 64-byte boundaries -- NC_XV_K7_MIN_COLS=<n> raises a column floor; NC_NO_XV_K7=1 keeps the legacy instances): the same for the dilated residual-unit convolutions with 8-byte words -- [8][320] floats = 5
     // float2 per thread, so the Snake work per thread stays exactly the item form's 10 elements, as packed pairs of one channel.
-    constexpr bool XVCAND = XVK;
     static_assert(!XVK || (TN == 2 && NW == 4 && !IN2 && !DIST && ((K == 2 && SUB != 0 && !FUSE) || (K == 7 && SUB == 0))),
                   "XV-only instances: two-tap sub-pixel or k = 7, 256-column tiles");
     constexpr int XVW = K == 2 ? 4 : 2;                          // floats per staged word
     constexpr int XVROW = 320;                                   // (== XROWC of the 256-column tiles, defined with the fragment reads below)
     constexpr int XVN = CB * XVROW / XVW;                        // words of the window image
-    constexpr int NV = XVCAND ? (XVN + NT - 1) / NT : 1;
+    constexpr int NV = XVK ? (XVN + NT - 1) / NT : 1;
     typedef float xv_t __attribute__((ext_vector_type(XVW)));
-    constexpr bool use_xv = XVCAND;                              // (the host launches these instances only where the form applies)
     unsigned xvo[NV];                                            // float offset of word n from the first channel row of a reduction block
     unsigned xvok = 0;                                           // bit n: word n lies inside its row (else zero padding)
-    int xvc[(XVCAND && K == 7) ? NV : 1];                        // K = 7: channel (within the block) of word n, for its Snake operands
+    int xvc[(XVK && K == 7) ? NV : 1];                        // K = 7: channel (within the block) of word n, for its Snake operands
     xv_t rxv[NV];
-    f32x4 rav[XVCAND ? NA : 1];
-    if constexpr (XVCAND) {
+    f32x4 rav[XVK ? NA : 1];
+    if constexpr (XVK) {
         {
 #pragma unroll
             for (int n = 0; n < NV; ++n) {
@@ -261,7 +251,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     }
     const bool xv_allok = __builtin_amdgcn_ballot_w64(xvok != (1u << NV) - 1u) == 0;
     auto xv_issue = [&](int cbn) __attribute__((always_inline)) {
-        if constexpr (XVCAND) {
+        if constexpr (XVK) {
             const float* base = xb + (size_t)((unsigned)(cbn * CB) * x_cstride);   // uniform
 #pragma unroll
             for (int n = 0; n < NV; ++n) rxv[n] = *reinterpret_cast<const xv_t*>(base + xvo[n]);
@@ -271,7 +261,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
         }
     };
     auto xv_store = [&](int cbn, float* Ad, float* Xd, auto allok_tag, auto snake_tag) __attribute__((always_inline)) {
-        if constexpr (XVCAND) {
+        if constexpr (XVK) {
 #pragma unroll
             for (int n = 0; n < NA; ++n)
                 if ((A_VEC % NT == 0) || stid + NT * n < A_VEC) reinterpret_cast<f32x4*>(Ad)[stid + NT * n] = rav[n];
@@ -306,7 +296,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     };
     // one rotation of the XV schedule inside block cb: the words of block cb + 1 to the idle buffers, the reads of block cb + 2 behind them
     auto xv_stage = [&](int cb, float* An, float* Xn) __attribute__((always_inline)) {
-        if constexpr (XVCAND) {
+        if constexpr (XVK) {
             if (K == 7 && alpha_in != nullptr) {
                 if (xv_allok) xv_store(cb + 1, An, Xn, std::true_type{}, std::true_type{});
                 else xv_store(cb + 1, An, Xn, std::false_type{}, std::true_type{});
@@ -351,8 +341,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
             constexpr int u = decltype(ut)::value, n = g * GA + u;
             if constexpr (n < NA) {
                 const int idx = stid + NT * n;
-                if constexpr (!A_DMA)
-                    if ((A_VEC % NT == 0) || idx < A_VEC) reinterpret_cast<f32x4*>(Ad)[idx] = ra[u];
+                if ((A_VEC % NT == 0) || idx < A_VEC) reinterpret_cast<f32x4*>(Ad)[idx] = ra[u];
             }
         });
         float2 al[GX] = {};
@@ -562,7 +551,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
             for (int j = 0; j < TN; ++j) fb[kp % (FD + 1)][j] = smem[(j == 0 ? o : o + ej[j]) + j * 32];
         }
     };
-    auto load_frag = [&](const float* Ac, int xsc, auto kp_tag) __attribute__((always_inline)) { load_frag_x(Ac, xsc, kp_tag, std::integral_constant<int, 0>{}); };
 
     if constexpr (DIST) {
         static_assert(!DIST || NG == 1, "distributed staging holds the whole next block in one register group");
@@ -605,11 +593,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
                 const int cbn = min(cb + 1, n_cb - 1);
                 issue_group(cbn, std::integral_constant<int, 0>{});
                 nc_static_for<FD>([&](auto d) __attribute__((always_inline)) {
-                    if constexpr (decltype(d)::value < KP) load_frag(Ac, Xc, d);
+                    if constexpr (decltype(d)::value < KP) load_frag_x(Ac, Xc, d, std::integral_constant<int, 0>{});
                 });
                 nc_static_for<KP>([&](auto d) __attribute__((always_inline)) {
                     constexpr int kp = decltype(d)::value;
-                    if constexpr (kp + FD < KP) load_frag(Ac, Xc, std::integral_constant<int, kp + FD>{});
+                    if constexpr (kp + FD < KP) load_frag_x(Ac, Xc, std::integral_constant<int, kp + FD>{}, std::integral_constant<int, 0>{});
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
@@ -636,8 +624,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
     } else {
     auto main_loop = [&](auto xr_tag) __attribute__((always_inline)) {
     constexpr int XR = decltype(xr_tag)::value;   // 0 generic, 1 constant pitch
-    if constexpr (XVCAND && XR == 1) {
-        if (use_xv && n_cb > 1) xv_issue(1);      // (block 0 came through the prologue; see the rotating schedule below)
+    if constexpr (XVK && XR == 1) {
+        if (n_cb > 1) xv_issue(1);      // (block 0 came through the prologue; see the rotating schedule below)
     }
     for (int cb = 0; cb < n_cb; ++cb) {
         const int cur = cb & 1;
@@ -661,7 +649,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
             if constexpr (seg == 0) NC_STAMP(cb, 0);
             else if constexpr (seg <= 3) NC_STAMP(cb, 2 * seg - 1);
             if (more) {
-                if constexpr (XVCAND && XR == 1) {   // (the XV-only instances)
+                if constexpr (XVK && XR == 1) {   // (the XV-only instances)
                     // rotating schedule: ONE register set.  At the head of segment 3 the words of block cb + 1 (in flight since the same
                     // point of the block before: a whole block of latency cover) go to the idle LDS buffers, and the reads of block cb + 2
                     // are issued straight behind them (that block's buffers are the ones being read now, but its words stay in registers
@@ -857,8 +845,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
                     const float a0 = ao_t[R], i0 = ao_t[BM + R], a1 = ao_t[R + 1], i1 = ao_t[BM + R + 1];
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        if constexpr (XVK) nc_snake_pair_m(vq[rr][j], vq[rr + 1][j], a0, i0, a1, i1);   // (sign-free sine: nc_math.h)
-                        else nc_snake_pair(vq[rr][j], vq[rr + 1][j], a0, i0, a1, i1);
+                        nc_snake_pair(vq[rr][j], vq[rr + 1][j], a0, i0, a1, i1);
                     }
                 }
             }
@@ -1063,8 +1050,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     float x0 = acc[i][j][r] + b0, x1 = acc[i][j][r + 1] + b1;
-                    if constexpr (XVK) nc_snake_pair_m(x0, x1, a0, i0, a1, i1);
-                    else nc_snake_pair(x0, x1, a0, i0, a1, i1);
+                    nc_snake_pair(x0, x1, a0, i0, a1, i1);
                     acc[i][j][r] = x0;
                     acc[i][j][r + 1] = x1;
                 }
@@ -1192,183 +1178,33 @@ __global__ __launch_bounds__(64 * NW, OCC) void conv_mfma_kernel(const ConvArgs 
 
 typedef void (*conv_kernel_fn)(const ConvArgs);
 
-template <int TM, int TN, int K, int CB, int NX, bool FUSE = false, int OCC = 2, int NW = 4, bool DIST = false, int SUB = 0,
-          bool IN2 = false, bool XVK = false>
-inline conv_kernel_fn get_conv_kernel() {
-    return &conv_mfma_kernel<TM, TN, K, CB, NX, FUSE, OCC, NW, DIST, SUB, IN2, XVK>;
-}
-
 }  // namespace nc
 
-// Instantiation helper: one translation unit per K registers its 8 (TM,TN) variants.
-#define NC_INSTANTIATE_CONV_K(KVAL, CBVAL, NXVAL)                                                          \
+// Instantiation: one macro defines the table function nc::conv_kernel_table_<NAME> (declared in nc_conv_plan.h) of a translation unit.
+// ARGS is its parameter list, KEY the switch value TM * 10 + TN built from it, TILES the (TM, TN) case list, and the trailing arguments
+// are the template arguments behind (TM, TN): K, CB, NX[, FUSE, OCC, NW, DIST, SUB, IN2, XVK].
+#define NC_TILES_22(X, ...) X(1, 1, __VA_ARGS__) X(1, 2, __VA_ARGS__) X(2, 1, __VA_ARGS__) X(2, 2, __VA_ARGS__)
+#define NC_TILES_34(X, ...) X(3, 1, __VA_ARGS__) X(3, 2, __VA_ARGS__) X(4, 1, __VA_ARGS__) X(4, 2, __VA_ARGS__)
+#define NC_TILES_ALL(X, ...) NC_TILES_22(X, __VA_ARGS__) NC_TILES_34(X, __VA_ARGS__)
+#define NC_TILES_TN1(X, ...) X(1, 1, __VA_ARGS__) X(2, 1, __VA_ARGS__) X(3, 1, __VA_ARGS__) X(4, 1, __VA_ARGS__)              // 96-column (3-wave) forms
+#define NC_TILES_FUSED(X, ...) X(2, 1, __VA_ARGS__) X(2, 2, __VA_ARGS__) NC_TILES_34(X, __VA_ARGS__)                          // Cin == Cout == 32 * TM
+#define NC_TILES_FUSEDW(X, ...) X(6, 1, __VA_ARGS__) X(8, 1, __VA_ARGS__)                                                     // C = 192 / 256, 128 columns
+#define NC_TILES_DIST(X, ...) NC_TILES_22(X, __VA_ARGS__) X(4, 1, __VA_ARGS__)
+#define NC_TILES_XV(X, ...) X(2, 2, __VA_ARGS__) X(3, 2, __VA_ARGS__) X(4, 2, __VA_ARGS__)                                    // 256-column tiles
+#define NC_CONV_CASE(TMV, TNV, ...) case TMV * 10 + TNV: return &conv_mfma_kernel<TMV, TNV, __VA_ARGS__>;
+#define NC_ARGS_TM_TN (int TM, int TN)
+#define NC_ARGS_TM (int TM)
+#define NC_INSTANTIATE_CONV(NAME, ARGS, KEY, TILES, ...)                                                   \
     namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_k##KVAL(int TM, int TN) {                                             \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL>();                                   \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL>();                                   \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL>();                                   \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL>();                                   \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL>();                                   \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL>();                                   \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL>();                                   \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL>();                                   \
-        }                                                                                                  \
+    conv_kernel_fn conv_kernel_table_##NAME ARGS {                                                         \
+        switch (KEY) { TILES(NC_CONV_CASE, __VA_ARGS__) }                                                  \
         return nullptr;                                                                                    \
     }                                                                                                      \
+    }
+// The plain instances of a K also export the reduction block and the staging depth they were compiled for.
+#define NC_INSTANTIATE_CONV_K(KVAL, CBVAL, NXVAL)                                                          \
+    NC_INSTANTIATE_CONV(k##KVAL, NC_ARGS_TM_TN, TM * 10 + TN, NC_TILES_ALL, KVAL, CBVAL, NXVAL)            \
+    namespace nc {                                                                                         \
     int conv_kernel_cb_k##KVAL() { return CBVAL; }                                                         \
     int conv_kernel_nx_k##KVAL() { return NXVAL; }                                                         \
-    }
-
-// Two-input variants of the Encodec input mode (IN2): the strided down-convolutions and the up-convolutions that consume the sum of a
-// residual block's shortcut and branch.  SUBV selects the sub-pixel form.
-#define NC_INSTANTIATE_CONV_IN2(NAME, KVAL, CBVAL, NXVAL, SUBV)                                            \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_##NAME(int TM, int TN) {                                              \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, SUBV, true>();   \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Sub-pixel transposed-convolution variants (stride 2 / 4 / 8 up-convolutions: rows = (channel, phase) pairs).
-#define NC_INSTANTIATE_CONV_SUB(KVAL, CBVAL, NXVAL)                                                        \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_sub_k##KVAL(int TM, int TN) {                                         \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, true>();         \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-#define NC_INSTANTIATE_CONV_SUB_NARROW(KVAL, CBVAL, NXVAL)                                                 \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_sub_narrow_k##KVAL(int TM) {                                          \
-        switch (TM) {                                                                                      \
-            case 1: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
-            case 2: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
-            case 3: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
-            case 4: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 3, false, true>();          \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Fused residual-unit variants (k=7 conv + Snake + 1x1 conv + skip in one launch): Cin == Cout == 32*TM.
-#define NC_INSTANTIATE_CONV_FUSED(KVAL, CBVAL, NXVAL)                                                      \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_fused_k##KVAL(int TM, int TN) {                                       \
-        switch (TM * 10 + TN) {                                                                            \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, true>();                             \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, true>();                             \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, true>();                             \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, true>();                             \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, true>();                             \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, true>();                             \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Wide fused residual units (C = 192 / 256): the tile spans all channels at 128 columns (TM = 6 / 8, TN = 1), reduction block of 4
-// channels so two workgroups share a CU; W1 streamed through LDS by row block.
-#define NC_INSTANTIATE_CONV_FUSED_WIDE(KVAL, CBVAL, NXVAL)                                                 \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_fusedw_k##KVAL(int TM, int TN) {                                      \
-        switch (TM * 10 + TN) {                                                                            \
-            case 61: return get_conv_kernel<6, 1, KVAL, CBVAL, NXVAL, true>();                             \
-            case 81: return get_conv_kernel<8, 1, KVAL, CBVAL, NXVAL, true>();                             \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Slim variants: half-size reduction block (half the LDS per workgroup) compiled for 4 waves per SIMD, for the narrow long-T layers
-// (Cout <= 64) whose workgroups are bound by their memory round trips: more workgroups per CU overlap them.  Same packed weight image.
-#define NC_INSTANTIATE_CONV_SLIM(KVAL, CBVAL, NXVAL) NC_INSTANTIATE_CONV_SLIM_N(slim, KVAL, CBVAL, NXVAL)
-#define NC_INSTANTIATE_CONV_SLIM_N(NAME, KVAL, CBVAL, NXVAL)                                               \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_##NAME##_k##KVAL(int TM, int TN) {                                        \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 4>();                         \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 4>();                         \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 4>();                         \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 4>();                         \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Narrow variants: 3 waves / 96 columns per workgroup (TN = 1), for the deep layers whose rows hold ~90 frames: a 128-column
-// tile would idle a quarter of its matrix-core work on padding.
-#define NC_INSTANTIATE_CONV_NARROW(KVAL, CBVAL, NXVAL)                                                     \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_narrow_k##KVAL(int TM) {                                              \
-        switch (TM) {                                                                                      \
-            case 1: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 3>();                       \
-            case 2: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 3>();                       \
-            case 3: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 3>();                       \
-            case 4: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 3>();                       \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Distributed staging for the one-workgroup-per-CU grids of the deep strided / sub-pixel layers (Encodec at 150 frames): with no
-// co-resident partner to feed the matrix pipe during a workgroup's staging runs, the runs are dealt into the matrix-core shadows.
-#define NC_INSTANTIATE_CONV_DIST_SMALL(NAME, KVAL, CBVAL, NXVAL, SUBV)                                     \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_##NAME(int TM, int TN) {                                              \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, true, SUBV>();          \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// Sub-pixel transposed convolution for ANY stride with two taps per phase (SUB == 2: multiply-shift row -> (channel, phase) map).
-#define NC_INSTANTIATE_CONV_SUBG(KVAL, CBVAL, NXVAL)                                                       \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_subg_k##KVAL(int TM, int TN) {                                        \
-        switch (TM * 10 + TN) {                                                                            \
-            case 11: return get_conv_kernel<1, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 12: return get_conv_kernel<1, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 21: return get_conv_kernel<2, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 22: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 31: return get_conv_kernel<3, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 32: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 41: return get_conv_kernel<4, 1, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-            case 42: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, false, 2, 4, false, 2>();            \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
-    }
-
-// XV-only instances (see XVK above): NAME_k<K>(TM) for the 256-column tiles; FUSEV selects the fused residual unit, SUBV the sub-pixel form.
-#define NC_INSTANTIATE_CONV_XV(NAME, KVAL, CBVAL, NXVAL, FUSEV, SUBV)                                       \
-    namespace nc {                                                                                         \
-    conv_kernel_fn conv_kernel_table_##NAME(int TM) {                                                      \
-        switch (TM) {                                                                                      \
-            case 2: return get_conv_kernel<2, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
-            case 3: return get_conv_kernel<3, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
-            case 4: return get_conv_kernel<4, 2, KVAL, CBVAL, NXVAL, FUSEV, 2, 4, false, SUBV, false, true>(); \
-        }                                                                                                  \
-        return nullptr;                                                                                    \
-    }                                                                                                      \
     }

@@ -44,15 +44,9 @@ ROWS = [
 ]
 
 
-# Forms the lists of tests/test_ops_gpu.py do not reach, each at the smallest shape that does.  The XV instances need 256-column one-clip
-# tiles that the 128-column rule for small grids leaves alone (a weight set above 4 MB) on a row tile of 64 or 96 rows without packed
-# alternatives (fewer than 128 rows: no 32-row tile for the tiny-grid rule), rows of a multiple of 16 samples; the distributed k = 16
-# instance a layer the short-row kernel does not serve (fewer than 64 output channels).
-EXTRA_CONV1D = [(3200, 48, 7, 1, 3, 1, 256, 1),      # xv
-                (32, 32, 16, 8, 4, 1, 256, 1)]       # dist
-EXTRA_SUBPIXEL = [(5472, 48, 2, 1, 256, 1, False),   # xv_sub
-                  (5472, 32, 3, 2, 256, 1, False)]   # xv_subg
-EXTRA_RES_UNIT = [(64, 256, 1, 1)]                   # xv_fused
+# Forms the case lists of tests/test_ops_gpu.py do not reach, each at the smallest shape that does: its EXTRA_* lists (kept there, where
+# the same shapes are held to the oracle by value).
+EXTRA_CONV1D, EXTRA_SUBPIXEL, EXTRA_RES_UNIT = T.EXTRA_CONV1D, T.EXTRA_SUBPIXEL, T.EXTRA_RES_UNIT
 
 
 def row_key(row):

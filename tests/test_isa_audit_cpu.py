@@ -69,3 +69,13 @@ def test_scratch_and_vector_register_spills_do_not_rise(now):
                 worse.append((r["what"], key, r.get(key), n.get(key)))
     assert not worse, "audited instances spill more than the record (what, counter, recorded, now): %r" % (worse,)
     assert any(r.get("scratch_bytes") is not None for r in rec.values()), "the record carries no scratch figures: re-record with tools/isa_audit.py --table"
+
+
+def test_diff_of_a_build_with_itself_is_all_identical():
+    """tools/isa_audit.py --diff (disassembly and kernel metadata of two builds, kernel by kernel): one unit of the build against itself."""
+    import isa_audit
+    if not os.path.exists(os.path.join(BUILD, "nc_conv_k7g.o")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("no build directory / LLVM tools: run __graft_entry__.build() first")
+    d = isa_audit.diff_builds(BUILD, BUILD, objects=r"nc_conv_k7g\.o$")
+    assert len(d) > 0
+    assert all(v is None for v in d.values()), d

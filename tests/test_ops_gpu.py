@@ -116,6 +116,10 @@ RES_UNIT_CASES = [(64, 700, 1, 2), (96, 523, 3, 1), (128, 300, 9, 2), (64, 40, 9
 def test_fused_res_unit_bit_exact(C, T, d, B):
     if C >= 192 and any(os.environ.get(k) == "1" for k in ("NC_NO_WIDE_FUSE", "NC_NO_TILE_ALTS")):
         pytest.skip("the whole-channel fused unit is switched off in this environment (tools/probe/envmatrix.sh row)")
+    _check_res_unit(C, T, d, B)
+
+
+def _check_res_unit(C, T, d, B):
     """Single-launch ResidualUnit (conv7 + Snake + 1x1 on the accumulators + skip) == oracle == two-launch path."""
     rng = np.random.default_rng(C + d)
     x = _rand(rng, B, C, T, scale=1.5)
@@ -551,3 +555,92 @@ def test_euclid_rvq_matrix_core_form_refuses_large_codebooks():
         idx = c_oracle.vq_argmin(r, books[q])[0]
         assert np.array_equal(c0[:, q, :], idx)
         r = r - books[q][idx].transpose(0, 2, 1)
+
+
+# ---- The XV-only and distributed-staging instances of the template (csrc/nc_conv_kernel.hip.h), by value AND by launched form.
+# The lists above do not reach these forms; each shape is the smallest that does.  The XV instances need 256-column one-clip tiles that
+# the 128-column rule for small grids leaves alone (a weight set above 4 MB) on a row tile of 64 or 96 rows without packed alternatives
+# (fewer than 128 rows: no 32-row tile for the tiny-grid rule), rows of a multiple of 16 samples; the distributed k = 16 instance a layer
+# the short-row kernel does not serve (fewer than 64 output channels).  (tests/test_conv_plan_gpu.py holds their launch lines.)
+EXTRA_CONV1D = [(3200, 48, 7, 1, 3, 1, 256, 1),      # xv
+                (32, 32, 16, 8, 4, 1, 256, 1)]       # dist
+EXTRA_SUBPIXEL = [(5472, 48, 2, 1, 256, 1, False),   # xv_sub
+                  (5472, 32, 3, 2, 256, 1, False)]   # xv_subg
+EXTRA_RES_UNIT = [(64, 256, 1, 1)]                   # xv_fused
+
+
+def case_xv_epilogue(T, snake_in, snake_out, with_res):
+    """The xv shape of EXTRA_CONV1D over rows of T samples with the epilogue variants the models use on it."""
+    cin, cout, k, s, p, d, _, B = EXTRA_CONV1D[0]
+    rng = np.random.default_rng(cin + T + snake_in + 2 * snake_out + 4 * with_res)
+    x = _rand(rng, B, cin, T)
+    w = _rand(rng, cout, cin, k, scale=1.0 / np.sqrt(cin * k)); b = _rand(rng, cout, scale=0.1)
+    return spec(x, w, b, s, p, d, alpha_in=_alpha(rng, cin) if snake_in else None, alpha_out=_alpha(rng, cout) if snake_out else None,
+                residual=_rand(rng, B, cout, T) if with_res else None)
+
+
+# Rows of 256 samples are ONE 256-column tile: a first-and-last tile (zero-select staging), full in the epilogue.  Rows of 592 = 2.3 tiles
+# add an interior tile (the straight-line staging of a tile without padding) and a partial last tile (the quad emitter).
+FORM_CASES = [
+    ("xv", lambda: case_conv1d(*EXTRA_CONV1D[0])),
+    ("dist", lambda: case_conv1d(*EXTRA_CONV1D[1])),
+    ("xv_sub", lambda: case_subpixel(*EXTRA_SUBPIXEL[0])),
+    ("xv_subg", lambda: case_subpixel(*EXTRA_SUBPIXEL[1])),
+    ("xv", lambda: case_xv_epilogue(256, True, False, False)),          # Snake on the input: the K = 7 Snake branch of the XV store
+    ("xv", lambda: case_xv_epilogue(256, False, True, True)),           # Snake on the output and a residual
+    ("xv_sub", lambda: case_subpixel(*EXTRA_SUBPIXEL[0][:-1], True)),   # Snake on the output of the sub-pixel form
+    ("xv", lambda: case_xv_epilogue(592, True, True, True)),
+    ("xv_sub", lambda: case_subpixel(5472, 48, 2, 1, 592, 1, True)),
+    ("xv_subg", lambda: case_subpixel(5472, 32, 3, 2, 592, 1, False)),
+]
+FORM_RES_UNITS = EXTRA_RES_UNIT + [(64, 592, 1, 1)]
+
+# The form a launch took is OBSERVED in the child of test_xv_and_dist_cases_launch_the_form_they_name: it runs with NC_LAUNCH_LOG set from
+# its first launch on (the engine opens the log once per process) and every case asserts the "conv_plan <form> ..." lines of its launches.
+_LOG = os.environ.get("NC_LAUNCH_LOG") if os.environ.get("NC_OPS_FORMS_CHILD") == "1" else None
+_log_pos = 0
+
+
+def _forms_launched():
+    """The forms of the "conv_plan" lines the engine logged since the last call (None where no log is kept)."""
+    global _log_pos
+    if _LOG is None:
+        return None
+    if not os.path.exists(_LOG):         # (the engine opens the log at its first launch)
+        return []
+    with open(_LOG) as f:
+        f.seek(_log_pos)
+        new = f.read()
+        _log_pos = f.tell()
+    return [ln.split()[1] for ln in new.splitlines() if ln.startswith("conv_plan ")]
+
+
+@pytest.mark.parametrize("n", range(len(FORM_CASES)))
+def test_xv_and_dist_forms_bit_exact(n):
+    form, case = FORM_CASES[n]
+    _forms_launched()
+    _check(case())
+    seen = _forms_launched()
+    assert seen is None or seen == [form], f"the case is meant for the {form} instances, launch_conv took {seen}"
+
+
+@pytest.mark.parametrize("C,T,d,B", FORM_RES_UNITS)
+def test_xv_fused_res_unit_bit_exact(C, T, d, B):
+    _forms_launched()
+    _check_res_unit(C, T, d, B)
+    seen = _forms_launched()
+    assert seen is None or "xv_fused" in seen, f"the case is meant for the xv_fused instances, launch_conv took {seen}"
+
+
+def test_xv_and_dist_cases_launch_the_form_they_name(tmp_path):
+    """One child that keeps the launch log runs the cases above again; there each asserts the form it was launched as, so a planner change
+    cannot silently turn them into tests of the plain instances."""
+    if os.environ.get("NC_OPS_FORMS_CHILD") == "1":
+        return                                              # (a child does not start children)
+    import subprocess
+    import sys
+    e = dict(os.environ, NC_OPS_FORMS_CHILD="1", NC_LAUNCH_LOG=str(tmp_path / "launch.log"))
+    cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", os.path.abspath(__file__), "-k", "test_xv_"]
+    r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=300, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-1500:])
+    assert f"{len(FORM_CASES) + len(FORM_RES_UNITS) + 1} passed" in r.stdout, r.stdout[-500:]

@@ -6,6 +6,8 @@ kernel's register and spill counts.  Static counts over ALL paths of a loop (run
 
     python tools/isa_audit.py neuralcodecs_amd/csrc/nc_conv_k7.hip [--grep 'ILi3ELi2ELi7'] [--min-mfma 64] [-D...]
     python tools/isa_audit.py neuralcodecs_amd/csrc/build/nc_conv_k7.o [--grep ...] [--json out.json]     # a BUILT object: seconds
+    python tools/isa_audit.py --diff <buildA> <buildB>     # two build directories: per conv_mfma_kernel instance `identical`, or the
+                                                           # metadata figures and audited-loop counts that differ (a refactor's check)
 """
 import argparse
 import os
@@ -49,13 +51,11 @@ def meta(asm):
     return out
 
 
-def audit_object(obj, grep="", min_mfma=64):
-    """Round 5: the same audit over a BUILT object (neuralcodecs_amd/csrc/build/*.o) -- the gfx950 code object is unbundled and
-    disassembled (about two seconds, no compilation), so a test can hold the shipped kernels to a committed table.  Returns
-    {kernel: {"loops": [{"mfma", "valu", "v_readlane", "ds_read", "waits"}, ...]}} for the loops with >= min_mfma matrix-core instructions
-    (static counts over all paths of a loop, like the source form)."""
+def read_object(obj):
+    """Unbundle and disassemble the gfx950 code object of a BUILT object (about two seconds, no compilation).  Returns (metadata, code):
+    the kernel metadata of the code object's notes per kernel symbol, and per kernel its instructions and `<L..>:` labels as text with
+    addresses and encodings stripped (branch targets are symbolic), so two builds of the same kernel compare equal line by line."""
     llvm = "/opt/rocm/lib/llvm/bin"
-    out = {}
     with tempfile.TemporaryDirectory() as td:
         fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "k.co")
         subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
@@ -77,35 +77,13 @@ def audit_object(obj, grep="", min_mfma=64):
             continue
         if cur is not None:
             cur[k] = int(v)
-    name, lines = None, []
-
-    def flush():
-        if name is None or (grep and not re.search(grep, name)):
-            return
-        labels = {t[1:-2]: i for i, t in enumerate(lines) if re.match(r"^<L\d+>:$", t)}
-        loops, seen = [], set()
-        for i, t in enumerate(lines):
-            m = re.match(r"s_c?branch\w*\s+(L\d+)", t)
-            if m and m.group(1) in labels and labels[m.group(1)] < i:
-                lo = labels[m.group(1)]
-                c = Counter(x.split()[0] for x in lines[lo:i] if not x.startswith("<"))
-                n = sum(v for k, v in c.items() if k.startswith("v_mfma"))
-                if n >= min_mfma and (lo, n) not in seen:
-                    seen.add((lo, n))
-                    loops.append({"mfma": n, "valu": sum(v for k, v in c.items() if k.startswith("v_") and not k.startswith("v_mfma")),
-                                  "v_readlane": c["v_readlane_b32"], "ds_read": sum(v for k, v in c.items() if k.startswith("ds_read")),
-                                  "waits": c["s_waitcnt"]})
-        if loops:
-            r = res.get(name, {})
-            out[name] = {"loops": loops, "scratch_bytes": r.get("private_segment_fixed_size"), "vgpr": r.get("vgpr_count"), "agpr": r.get("agpr_count"),
-                         "vgpr_spill": r.get("vgpr_spill_count"), "sgpr": r.get("sgpr_count"), "sgpr_spill": r.get("sgpr_spill_count")}
+    code, lines = {}, None
     for l in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(_Z\w+)>:$", l)
         if m:
-            flush()
-            name, lines = m.group(1), []
+            lines = code.setdefault(m.group(1), [])
             continue
-        if name is None:
+        if lines is None:
             continue
         m = re.match(r"^[0-9a-f]+ (<L\d+>:)$", l)
         if m:
@@ -114,7 +92,65 @@ def audit_object(obj, grep="", min_mfma=64):
         t = l.split("//")[0].strip()
         if t:
             lines.append(t)
-    flush()
+    return res, code
+
+
+def loops_of(lines, min_mfma):
+    """The loops (backward branch to a label) of one kernel that hold >= min_mfma matrix-core instructions, with their counts."""
+    labels = {t[1:-2]: i for i, t in enumerate(lines) if re.match(r"^<L\d+>:$", t)}
+    loops, seen = [], set()
+    for i, t in enumerate(lines):
+        m = re.match(r"s_c?branch\w*\s+(L\d+)", t)
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            lo = labels[m.group(1)]
+            c = Counter(x.split()[0] for x in lines[lo:i] if not x.startswith("<"))
+            n = sum(v for k, v in c.items() if k.startswith("v_mfma"))
+            if n >= min_mfma and (lo, n) not in seen:
+                seen.add((lo, n))
+                loops.append({"mfma": n, "valu": sum(v for k, v in c.items() if k.startswith("v_") and not k.startswith("v_mfma")),
+                              "v_readlane": c["v_readlane_b32"], "ds_read": sum(v for k, v in c.items() if k.startswith("ds_read")),
+                              "waits": c["s_waitcnt"]})
+    return loops
+
+
+def audit_object(obj, grep="", min_mfma=64):
+    """Round 5: the same audit over a BUILT object (neuralcodecs_amd/csrc/build/*.o), so a test can hold the shipped kernels to a
+    committed table.  Returns {kernel: {"loops": [{"mfma", "valu", "v_readlane", "ds_read", "waits"}, ...]}} for the loops with >= min_mfma
+    matrix-core instructions (static counts over all paths of a loop, like the source form)."""
+    res, code = read_object(obj)
+    out = {}
+    for name, lines in code.items():
+        if grep and not re.search(grep, name):
+            continue
+        loops = loops_of(lines, min_mfma)
+        if loops:
+            r = res.get(name, {})
+            out[name] = {"loops": loops, "scratch_bytes": r.get("private_segment_fixed_size"), "vgpr": r.get("vgpr_count"), "agpr": r.get("agpr_count"),
+                         "vgpr_spill": r.get("vgpr_spill_count"), "sgpr": r.get("sgpr_count"), "sgpr_spill": r.get("sgpr_spill_count")}
+    return out
+
+
+def diff_builds(dir_a, dir_b, grep="conv_mfma_kernel", min_mfma=48, objects=r"nc_conv_(k|in2|xv)\w*\.o$"):
+    """`--diff`: every kernel matching `grep` in the objects (names matching `objects`: the template's instantiation units) that the two
+    build directories share, side A against side B.  Returns
+    {kernel: None if disassembly and metadata are identical, else {"object", "only_in" | "meta": {key: [a, b]}, "loops": [a, b]}}."""
+    out = {}
+    for obj in sorted(set(os.listdir(dir_a)) & set(os.listdir(dir_b))):
+        if not re.match(objects, obj):
+            continue
+        (ma, ca), (mb, cb) = read_object(os.path.join(dir_a, obj)), read_object(os.path.join(dir_b, obj))
+        for name in sorted(set(ca) | set(cb)):
+            if not re.search(grep, name):
+                continue
+            if name not in ca or name not in cb:
+                out[name] = {"object": obj, "only_in": "A" if name in ca else "B"}
+            elif ca[name] == cb[name] and ma.get(name) == mb.get(name):
+                out[name] = None
+            else:
+                keys = sorted(set(ma.get(name, {})) | set(mb.get(name, {})))
+                out[name] = {"object": obj, "meta": {k: [ma.get(name, {}).get(k), mb.get(name, {}).get(k)] for k in keys
+                                                     if ma.get(name, {}).get(k) != mb.get(name, {}).get(k)},
+                             "loops": [loops_of(ca[name], min_mfma), loops_of(cb[name], min_mfma)]}
     return out
 
 
@@ -171,6 +207,13 @@ def hot_table(build_dir):
 
 
 def main():
+    if len(sys.argv) >= 4 and sys.argv[1] == "--diff":
+        d = diff_builds(sys.argv[2], sys.argv[3])
+        for k, v in d.items():
+            print(k, "identical" if v is None else v)
+        same = sum(v is None for v in d.values())
+        print(f"{len(d)} kernels, {same} identical, {len(d) - same} differ")
+        sys.exit(0 if d and same == len(d) else 1)
     if len(sys.argv) >= 2 and sys.argv[1] == "--table":
         import json
         tab = hot_table(os.path.join(ROOT, "neuralcodecs_amd", "csrc", "build"))
