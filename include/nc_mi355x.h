@@ -478,6 +478,15 @@ NC_API nc_status nc_op_vq_argmin(int device_index, const float* z_e, int32_t B, 
  * leaves LDS).  form 0: one launch per stage; form 1: the all-stages matrix-core kernel (D == 128 and N = 512 or 1024, else NC_EUNSUPPORTED). */
 NC_API nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, int32_t D, int64_t T, const float* codebooks,
                                   int32_t n_q, int32_t N, int32_t form, int64_t* codes, float* residual_out);
+/* One activation of a loaded Encodec handle's SEANet stacks, as the driver holds it between launches (a "tap").  decoder == 0: the encoder
+ * on x [B,channels,L] (no RMS normalisation); decoder != 0: the decoder on x [B,dimension,L].  The launches up to the tap are the ones
+ * nc_encodec_encode / nc_encodec_decode make for a group of B rows.  Taps in driver order -- encoder: first conv | per stage: shortcut s,
+ * branch h (k = 3), branch y (k = 1), down-conv | LSTM | last conv; decoder: first conv | LSTM | per stage: up-conv, s, h, y | last conv
+ * (*n_taps = 3 + 4 * n_ratios).  out [B,C_out,L_out]: the tap with its pending GroupNorm applied, trimmed as its consumer reads it, without
+ * the consumer's ELU; the LSTM tap is elu(x + lstm(x)).  stats [B][2] (nullable): (mean, rstd) of the tap's pending GroupNorm, written
+ * where *has_stats comes back 1.  out == NULL: only *C_out, *L_out and *n_taps (tap < 0: only *n_taps); nothing is launched. */
+NC_API nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* x, int32_t B, int64_t L, int32_t tap, float* out, float* stats,
+                                     int32_t* C_out, int64_t* L_out, int32_t* n_taps, int32_t* has_stats);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */
 NC_API nc_status nc_op_fold_weight_norm(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
 /* The HBM-bound SNAC kernels, one at a time (host pointers in and out, like nc_op_conv1d).

@@ -690,6 +690,33 @@ nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, i
     });
 }
 
+nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* x, int32_t B, int64_t L, int32_t tap, float* out, float* stats,
+                              int32_t* C_out, int64_t* L_out, int32_t* n_taps, int32_t* has_stats) {
+    return guard([&] {
+        EncodecModel& m = as<EncodecModel>(h);
+        if (n_taps) *n_taps = m.trace_taps();
+        if (tap < 0 && !out) return;                                   // the tap count alone
+        if (B <= 0 || L <= 0) fail(NC_EINVAL, "B and L must be positive");
+        int C = 0; int64_t Lt = 0;
+        m.trace_shape(decoder != 0, L, tap, &C, &Lt);
+        if (C_out) *C_out = C;
+        if (L_out) *L_out = Lt;
+        if (!out) return;                                              // sizes only: nothing is launched
+        if (!x) fail(NC_EINVAL, "x must not be null");
+        m.use_device();
+        OwnStreamScope own(m);
+        const size_t n_in = (size_t)B * (decoder ? m.cfg.dimension : m.cfg.channels) * L * 4, n_out = (size_t)B * C * Lt * 4;
+        m.ck_in.reserve(n_in);
+        const float* st = nullptr;
+        const float* y = nullptr;
+        encodec_host_call(m, [&] { h2d(m.ck_in.p, x, n_in, m.stream); }, [&] { y = m.trace_dev(decoder != 0, m.ck_in.as<float>(), B, L, tap, &st); });
+        d2h(out, y, n_out, m.stream);
+        if (has_stats) *has_stats = st ? 1 : 0;
+        if (stats && st) d2h(stats, st, (size_t)B * 2 * 4, m.stream);
+        NC_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
 // ---- op hooks over the HBM-bound SNAC kernels (nc_elem.hip, nc_snac_unit.hip) ----
 
 nc_status nc_op_dwconv1d(int device_index, int32_t B, int32_t C, int64_t T, int32_t K, int32_t pad, int32_t dil, const float* x,

@@ -15,6 +15,7 @@
 // the tail segment beside them on a side stream.
 // Arithmetic is the canonical arithmetic of DESIGN.md (same sequences as oracle/c/nc_ref_encodec.c).
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 
 #include "nc_gn.h"
@@ -513,6 +514,10 @@ EncodecModel::GnJob EncodecModel::gn_begin(const ConvLayer& conv, ConvIO& io, in
 const float* EncodecModel::gn_end(const GnJob& j, const float* raw, int N, int C, int64_t L, int64_t rs) {
     if (rs <= 0) rs = L;
     if (!j.on) return nullptr;
+    if (FILE* lf = launch_log()) {   // where the statistics of this conv launch come from (tests/test_encodec_layers_gpu.py)
+        std::fprintf(lf, "enc_gn %s\n", j.finished ? "epilogue_finished" : j.fused ? "epilogue_sums+final" : "block_pass+final");
+        std::fflush(lf);
+    }
     if (j.finished) return j.stats;
     const int64_t n = (int64_t)j.nrb * j.ncb;
     ProfScope ps(&prof, stream, NC_KC_NORM, 3.0 * N * C * (double)L, j.fused ? 16.0 * N * (double)n : 4.0 * N * C * (double)L);
@@ -578,6 +583,14 @@ static EncodecModel::Act make_act(const float* y, int C, int64_t len, int64_t rs
 }
 static EncodecModel::Act dense_act(const float* y, int C, int64_t len) { return make_act(y, C, len, len, 0); }
 
+// NC_LAUNCH_LOG: one "enc_form <kernel> ..." line per launch of a streaming kernel (the form the driver took, for tests/test_encodec_layers_gpu.py)
+static void log_enc_form(const char* kernel, int p, bool aligned) {
+    if (FILE* lf = launch_log()) {
+        std::fprintf(lf, "enc_form %s<%d> %s\n", kernel, p, aligned ? "aligned" : "unaligned");
+        std::fflush(lf);
+    }
+}
+
 // two operands one launch can read side by side: same shape and pitch, both or neither with a pending GroupNorm
 static bool same_geometry(const EncodecModel::Act& a, const EncodecModel::Act& b) {
     return b.C == a.C && b.L == a.L && b.rs == a.rs && (a.stats != nullptr) == (b.stats != nullptr);
@@ -625,6 +638,7 @@ bool EncodecModel::try_stream_down(SConv& L, const Act& a, const Act* b2, bool e
         if (!(s5 ? launch_down5(d, 4, stream) : s4 ? launch_down4(d, 4, stream) : launch_down2(d, 2, aligned, stream)))
             fail(NC_ESTATE, "internal: no streaming down-convolution instance");
     }
+    log_enc_form("down", L.stride, s2 ? aligned : true);
     out = make_act(y, L.Cout, pl.Lout, pl.Lout, 0, st, &L);
     return true;
 }
@@ -687,6 +701,7 @@ bool EncodecModel::try_stream_up(SConv& L, const Act& a, const Act* b2, bool elu
         ProfScope ps(&prof, stream, L.conv.kclass, L.conv.flops(N, T), 4.0 * N * (2.0 * a.C * (double)T + (double)L.Cout * Lfull));
         if (!launch_up2(d, L.conv.cfg.TM, S, aligned, stream)) fail(NC_ESTATE, "internal: no streaming up-convolution instance");
     }
+    log_enc_form("up", S, aligned);
     const int64_t pt = L.K - L.stride, right = pt / 2, left = pt - right;           // non-causal trim (SConvTranspose1d.cs:159-171)
     out = make_act(y, L.Cout, Lfull - left - right, Lfull, left, st, &L);
     return true;
@@ -769,6 +784,7 @@ bool EncodecModel::resblock_first_pass(ResBlock& r, const Act& x, int N, Act& s,
         ProfScope ps(&prof, stream, NC_KC_CONV_K1, 2.0 * C * (C + 1.5 * C) * (double)T * N, 4.0 * N * (double)T * (C + C + C / 2));
         if (!launch_res_a(a, C / 32, aligned, stream)) fail(NC_ESTATE, "internal: no first-pass kernel for C = %d", C);
     }
+    log_enc_form("res_a", C / 32, aligned);
     s = make_act(ys, C, T, T, 0, st_s, &r.sc);
     h = make_act(yb, C / 2, T, T, 0, st_b, &r.c1);
     return true;
@@ -781,10 +797,12 @@ void EncodecModel::resblock(ResBlock& r, const Act& x, int N, Act& s, Act& y) {
         s = sconv(r.sc, x, nullptr, false, N);
         h = sconv(r.c1, x, nullptr, true, N);
     }
+    tap(s); tap(h);
     y = sconv(r.c2, h, nullptr, true, N);
     // A row shorter than the k=3 pad takes SConv1d's small-input path (zero-extend, never trimmed: D9), so the block branch comes
     // out LONGER than the 1x1 shortcut and the reference's add() would broadcast.  Such degenerate segments are rejected.
     if (y.L != s.L) fail(NC_EINVAL, "segment too short: a residual block sees %lld samples", (long long)x.L);
+    tap(y);
 }
 
 // GroupNorm-apply of a view into a dense tensor (optionally x scale[b] / divided by scale[b])
@@ -794,6 +812,27 @@ float* EncodecModel::materialize(const Act& a, int N, const float* scale, int mo
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, view_of(a), scale, mode, y, N, a.C, a.L);
     NC_HIP(hipGetLastError());
     return y;
+}
+
+// SEANetEncoder.forward (SEANetEncoder.cs:37-148) on N rows
+EncodecModel::Act EncodecModel::encoder_stack(Act cur, int N) {
+    cur = sconv(enc_in, cur, nullptr, false, N);
+    tap(cur);
+    for (int i = 0; i < cfg.n_ratios; ++i) {
+        Act s, y;
+        resblock(enc_res[i], cur, N, s, y);
+        cur = sconv(enc_down[i], s, &y, true, N);
+        tap(cur);
+    }
+    const float* xl = materialize(cur, N, nullptr, 0);
+    // (the ELU in front of the last convolution is applied by the LSTM's output store: once per element instead of once per row tile
+    //  of the consumer's staging, and the consumer runs as a plain convolution)
+    const bool lstm_elu = lstm_applies_elu(enc_lstm);
+    const Act a = dense_act(lstm.run(enc_lstm, xl, N, cur.L, lstm_elu), cur.C, cur.L);
+    tap(a, true, lstm_elu);
+    Act e = sconv(enc_out, a, nullptr, !lstm_elu, N);
+    tap(e);
+    return e;
 }
 
 // EncodeFrame on N = clips of one segment length: x [N,channels,L] dense -> codes [N,n_q,T'] (+ scale [N], emb)
@@ -814,18 +853,7 @@ void EncodecModel::encode_batch(const float* x, int N, int64_t L, int64_t Tz, in
         }
         cur.p = materialize(cur, N, sc, 0);
     }
-    cur = sconv(enc_in, cur, nullptr, false, N);
-    for (int i = 0; i < cfg.n_ratios; ++i) {
-        Act s, y;
-        resblock(enc_res[i], cur, N, s, y);
-        cur = sconv(enc_down[i], s, &y, true, N);
-    }
-    const float* xl = materialize(cur, N, nullptr, 0);
-    // (the ELU in front of the last convolution is applied by the LSTM's output store: once per element instead of once per row tile
-    //  of the consumer's staging, and the consumer runs as a plain convolution)
-    const bool lstm_elu = lstm_applies_elu(enc_lstm);
-    const Act a = dense_act(lstm.run(enc_lstm, xl, N, cur.L, lstm_elu), cur.C, cur.L);
-    Act e = sconv(enc_out, a, nullptr, !lstm_elu, N);
+    Act e = encoder_stack(cur, N);
     if (e.L != Tz) fail(NC_ESTATE, "internal: encoder produced %lld frames, expected %lld", (long long)e.L, (long long)Tz);
     float* residual = materialize(e, N, nullptr, 0);
     const int D = cfg.dimension;
@@ -836,21 +864,98 @@ void EncodecModel::encode_batch(const float* x, int N, int64_t L, int64_t Tz, in
     if (prof.on) prof.end(stream);
 }
 
-// DecodeFrame on N clips: codes [N,n_q,T'] -> out [N,channels,Lout] dense (x scale[n] when given)
-float* EncodecModel::decode_batch(const int64_t* codes, int N, int nq, int64_t Tz, const float* scale, int64_t* Lout) {
-    float* emb = alloc((size_t)N * cfg.dimension * Tz);
-    launch_emb_sum(book_tab, codes, nq, N, Tz, emb, stream);
+// SEANetDecoder.forward (SEANetDecoder.cs:40-153) on N rows
+EncodecModel::Act EncodecModel::decoder_stack(const float* emb, int N, int64_t Tz) {
     Act cur = sconv(dec_in, dense_act(emb, cfg.dimension, Tz), nullptr, false, N);
+    tap(cur);
     const float* xl = materialize(cur, N, nullptr, 0);
     const bool lstm_elu = lstm_applies_elu(dec_lstm);
     Act s = dense_act(lstm.run(dec_lstm, xl, N, cur.L, lstm_elu), cur.C, cur.L), y;
+    tap(s, true, lstm_elu);
     bool dual = false;
     for (int i = 0; i < cfg.n_ratios; ++i) {
         Act u = sconvT(dec_up[i], s, dual ? &y : nullptr, !(i == 0 && lstm_elu), N);
+        tap(u);
         resblock(dec_res[i], u, N, s, y);
         dual = true;
     }
     Act o = sconv(dec_out, s, dual ? &y : nullptr, true, N);
+    tap(o);
+    return o;
+}
+
+// The test hook's tap (nc_model.h).  Shapes first, by the pad plans alone.
+void EncodecModel::trace_shape(bool decoder, int64_t L, int tap_i, int* C_out, int64_t* L_out) const {
+    if (L <= 0 || tap_i < 0 || tap_i >= trace_taps()) fail(NC_EINVAL, "tap %d of %d, rows of %lld", tap_i, trace_taps(), (long long)L);
+    int n = 0, C = 0;
+    bool done = false;
+    auto at = [&](int c, int64_t l) { if (!done && n++ == tap_i) { *C_out = c; *L_out = l; done = true; } };
+    auto block = [&](int c, int64_t l) {   // s, h, y of a residual block on [c, l]
+        const int64_t lh = plan_sconv(l, cfg.residual_kernel_size, 1, 1).Lout;
+        const int64_t ly = plan_sconv(lh, 1, 1, 1).Lout;
+        if (done) return;
+        at(c, plan_sconv(l, 1, 1, 1).Lout); at(c / cfg.compress, lh);
+        if (ly != l && !done) fail(NC_EINVAL, "segment too short: a residual block sees %lld samples", (long long)l);
+        at(c, ly);
+    };
+    const int nf = cfg.n_filters;
+    if (!decoder) {
+        C = nf; L = plan_sconv(L, cfg.kernel_size, 1, 1).Lout;
+        at(C, L);
+        for (int i = 0; i < cfg.n_ratios; ++i) {
+            const int r = cfg.ratios[cfg.n_ratios - 1 - i];
+            block(C, L);
+            C *= 2; L = plan_sconv(L, 2 * r, r, 1).Lout;
+            at(C, L);
+        }
+        at(C, L);
+        at(cfg.dimension, plan_sconv(L, cfg.last_kernel_size, 1, 1).Lout);
+    } else {
+        C = nf << cfg.n_ratios; L = plan_sconv(L, cfg.kernel_size, 1, 1).Lout;
+        at(C, L); at(C, L);
+        for (int i = 0; i < cfg.n_ratios; ++i) {
+            const int r = cfg.ratios[i];
+            C /= 2; L = L * r;                                   // (L - 1) r + 2r, trimmed by r
+            at(C, L);
+            block(C, L);
+        }
+        at(cfg.channels, plan_sconv(L, cfg.last_kernel_size, 1, 1).Lout);
+    }
+    if (!done) fail(NC_ESTATE, "internal: tap %d not reached", tap_i);
+}
+
+const float* EncodecModel::trace_dev(bool decoder, const float* x, int N, int64_t L, int tap_i, const float** stats) {
+    if (!loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
+    if (!x || N <= 0 || N > GN_MAX_SAMPLES || L <= 0 || L > ((int64_t)1 << 30)) fail(NC_EINVAL, "x, N and L must be given");
+    int C = 0; int64_t Lt = 0;
+    trace_shape(decoder, L, tap_i, &C, &Lt);
+    use_device();
+    check_async_errors();
+    pool_i = 0;
+    struct Off { Trace& t; ~Off() { t.want = -1; } } off{trace};
+    trace = Trace{};
+    trace.want = tap_i;
+    bool hit = false;
+    try {
+        if (decoder) decoder_stack(x, N, L);
+        else encoder_stack(dense_act(x, cfg.channels, L), N);
+    } catch (const TapReached&) { hit = true; }
+    trace.want = -1;
+    const Act& a = trace.act;
+    if (!hit || a.C != C || a.L != Lt) fail(NC_ESTATE, "internal: tap %d is [%d, %lld], planned [%d, %lld]", tap_i, a.C, (long long)a.L, C, (long long)Lt);
+    if (stats) *stats = a.stats;
+    if (trace.lstm && !trace.lstm_has_elu) {   // (NC_LSTM_NO_ELU: the consumer applies the ELU while staging; the tap is defined with it)
+        Plan pl; pl.left = 0; pl.right = 0; pl.Lz = a.L; pl.Lp = a.L; pl.Lout = a.L;
+        return pad_act(a, nullptr, true, N, pl);
+    }
+    return materialize(a, N, nullptr, 0);
+}
+
+// DecodeFrame on N clips: codes [N,n_q,T'] -> out [N,channels,Lout] dense (x scale[n] when given)
+float* EncodecModel::decode_batch(const int64_t* codes, int N, int nq, int64_t Tz, const float* scale, int64_t* Lout) {
+    float* emb = alloc((size_t)N * cfg.dimension * Tz);
+    launch_emb_sum(book_tab, codes, nq, N, Tz, emb, stream);
+    Act o = decoder_stack(emb, N, Tz);
     *Lout = o.L;
     return materialize(o, N, scale, 1);
 }

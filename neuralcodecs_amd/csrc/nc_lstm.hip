@@ -2,6 +2,7 @@
 // the per-device ticket that serialises the persistent sections of different handles, and the launch sequence (layers in sequence, or
 // layer-pipelined over two streams).  Arithmetic is the canonical arithmetic of DESIGN.md (same sequences as oracle/c/nc_ref_encodec.c).
 #include <algorithm>
+#include <cstdio>
 #include <mutex>
 
 #include "nc_math.h"
@@ -632,6 +633,12 @@ static float* run_persistent(LstmRuntime& r, Lstm& l, const float* x, int N, int
         static bool fake = env_flag("NC_LSTM_FAKE_TIMEOUT");
         if (fake) { fake = false; *reinterpret_cast<volatile unsigned*>(r.tmo_host) = 1; }
     }
+    if (FILE* lf = launch_log()) {   // the form of the call, for tests/test_encodec_layers_gpu.py
+        static const bool no_htile = env_flag("NC_LSTM_NO_HTILE");
+        std::fprintf(lf, "lstm seq C=%d UBW=%d htile=%d piped=%d chunks=%d tiles=%d layers=%d T=%lld\n", c.C, c.UBW, no_htile ? 0 : 1, c.piped ? 1 : 0, c.nch(),
+                     c.n_tiles, c.nl, (long long)T);
+        std::fflush(lf);
+    }
     if (c.piped) run_piped(r, c, l);
     else
         for (int li = 0; li < c.nl; ++li) {
@@ -645,6 +652,10 @@ static float* run_persistent(LstmRuntime& r, Lstm& l, const float* x, int N, int
 static float* run_stepwise(EncodecModel& m, Lstm& l, const float* x, int N, int64_t T, bool elu_out) {
     const int C = l.C, nl = (int)l.layers.size();
     hipStream_t stream = m.stream;
+    if (FILE* lf = launch_log()) {
+        std::fprintf(lf, "lstm step C=%d layers=%d T=%lld\n", C, nl, (long long)T);
+        std::fflush(lf);
+    }
     const float* in = x;
     float* out = nullptr;
     for (int li = 0; li < nl; ++li) {

@@ -315,6 +315,16 @@ struct EncodecModel : Codec {
     void encode_dev(const float* pcm, int B, int64_t T, int64_t* codes, float* scales, float* emb);
     void decode_dev(const int64_t* codes, const float* scales, int B, int64_t T, int nq, float* pcm);
     float* alloc(size_t n_floats);   // the next buffer of the pool, grown to n_floats
+    // Test hook (nc_op_encodec_trace).  A tap is every activation view the driver holds between launches, numbered in the order the
+    // driver produces them: encoder = first conv | per stage: shortcut s, branch h, branch y, down-conv | LSTM | last conv; decoder =
+    // first conv | LSTM | per stage: up-conv, s, h, y | last conv.  The LSTM tap is elu(x + lstm(x)).
+    int trace_taps() const { return 3 + 4 * cfg.n_ratios; }
+    // channels and length of tap `tap` for rows of L samples (encoder) or frames (decoder): host arithmetic on the pad plans; raises what the stack raises
+    void trace_shape(bool decoder, int64_t L, int tap, int* C_out, int64_t* L_out) const;
+    // Runs the encoder stack (no RMS normalisation) or the decoder stack on the dense device tensor x [N, channels | dimension, L] up to
+    // tap `tap` -- the launches encode_batch / decode_batch make -- and returns the tap as a dense device tensor [N, C, L_tap]: pending
+    // GroupNorm applied, trimmed, no ELU.  *stats: the tap's [N][2] (mean, rstd) on the device, null where no GroupNorm is pending.
+    const float* trace_dev(bool decoder, const float* x, int N, int64_t L, int tap, const float** stats);
 
   private:
     void load_sconv(const Blob& b, const std::string& key, SConv& L, int Cin, int Cout, int K, int stride, bool transposed);
@@ -344,6 +354,15 @@ struct EncodecModel : Codec {
     char* ola_stage(const std::vector<const float*>& fp, const std::vector<int64_t>& flen);
     void encode_batch(const float* x, int N, int64_t L, int64_t Tz, int64_t* codes, float* scale_out, float* emb_out);
     float* decode_batch(const int64_t* codes, int N, int nq, int64_t Tz, const float* scale, int64_t* Lout);
+    Act encoder_stack(Act cur, int N);                        // SEANetEncoder.forward on an activation view -> the last conv's pending view
+    Act decoder_stack(const float* emb, int N, int64_t Tz);   // SEANetDecoder.forward on dense emb [N,dimension,Tz]
+    // the tap of trace_dev: with no trace running (want < 0, every production call) tap() is one compare
+    struct TapReached {};
+    struct Trace { int want = -1, n = 0; bool lstm = false, lstm_has_elu = false; Act act; } trace;
+    void tap(const Act& a, bool lstm = false, bool lstm_has_elu = false) {
+        if (trace.want < 0) return;
+        if (trace.n++ == trace.want) { trace.act = a; trace.lstm = lstm; trace.lstm_has_elu = lstm_has_elu; throw TapReached{}; }
+    }
 };
 
 }  // namespace nc

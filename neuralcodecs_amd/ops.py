@@ -65,6 +65,27 @@ def euclid_rvq(residual, codebooks, form=1, device_index=0):
     return codes, out
 
 
+def encodec_trace_taps(model):
+    """Number of taps of either stack of a loaded Encodec model (3 + 4 * len(ratios))."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().nc_op_encodec_trace(model._h, 0, None, 0, 0, -1, None, None, None, None, C.byref(n), None))
+    return n.value
+
+
+def encodec_trace(model, x, tap, decoder=False):
+    """Tap `tap` of the SEANet encoder on x [B,channels,L] (no RMS normalisation) or, decoder=True, of the decoder on x [B,dimension,L], by
+    the launches the model itself makes: (tap [B,C,L'] with its pending GroupNorm applied and no ELU, stats [B,2] = (mean, rstd) of that
+    GroupNorm or None).  Tap order: see nc_op_encodec_trace in include/nc_mi355x.h."""
+    x = np.ascontiguousarray(x, np.float32)
+    B, _, L = x.shape
+    Co, Lo, hs = C.c_int32(), C.c_int64(), C.c_int32()
+    f = _lib.lib().nc_op_encodec_trace
+    _lib.check(f(model._h, int(bool(decoder)), None, B, L, int(tap), None, None, C.byref(Co), C.byref(Lo), None, None))
+    out = np.empty((B, Co.value, Lo.value), np.float32); st = np.empty((B, 2), np.float32)
+    _lib.check(f(model._h, int(bool(decoder)), x.ctypes.data, B, L, int(tap), out.ctypes.data, st.ctypes.data, None, None, None, C.byref(hs)))
+    return out, (st if hs.value else None)
+
+
 def fold_weight_norm(v, g):
     v = np.ascontiguousarray(v, np.float32); g = np.ascontiguousarray(g, np.float32).reshape(-1)
     w = np.empty_like(v)

@@ -39,12 +39,27 @@ typedef struct {
     int kernel_size, last_kernel_size, residual_kernel_size, group_norm, causal, normalize, codebook_size, n_q_total;
 } ref_encodec_config;
 
+#define REF_MAX_TAPS (3 + 4 * 8)
+typedef struct { float* v; int C; int64_t L; int has_stats; float* stats; float* raw; int64_t raw_L; } ref_tap;   /* raw [B,C,raw_L]: the conv output the statistics were taken on */
 typedef struct {
     ref_encodec_config cfg;
     uint8_t* blob_copy;
     ref_blob blob;
     int bad;
+    /* ref_encodec_trace: the activations between the layers of the last traced run, in the order the stacks produce them */
+    int tracing, n_taps, last_has_stats;
+    float* last_stats;          /* [B][2] (mean, rstd) of the GroupNorm the last sconv / sconvT applied */
+    float* last_raw;            /* and that layer's output before it [B,C,last_raw_L] (untrimmed behind a transposed convolution) */
+    int64_t last_raw_L;
+    ref_tap taps[REF_MAX_TAPS];
 } ref_encodec;
+
+static void taps_free(ref_encodec* m) {
+    for (int i = 0; i < m->n_taps; i++) { free(m->taps[i].v); free(m->taps[i].stats); free(m->taps[i].raw); }
+    m->n_taps = 0;
+    free(m->last_stats); m->last_stats = NULL;
+    free(m->last_raw); m->last_raw = NULL;
+}
 
 REF_API ref_encodec* ref_encodec_create(const ref_encodec_config* cfg, const uint8_t* blob, int64_t len) {
     ref_encodec* m = (ref_encodec*)calloc(1, sizeof(ref_encodec));
@@ -56,6 +71,7 @@ REF_API ref_encodec* ref_encodec_create(const ref_encodec_config* cfg, const uin
 }
 REF_API void ref_encodec_destroy(ref_encodec* m) {
     if (!m) return;
+    taps_free(m);
     free(m->blob.t); free(m->blob_copy); free(m);
 }
 
@@ -141,6 +157,7 @@ static void gn_sums(const float* y, int C, int64_t T, int sub, double* s1_out, d
     *s1_out = p1[0]; *s2_out = p2[0];
 }
 
+static float* gn_stats_sink = NULL;   /* ref_encodec_trace: [B][2] (mean, rstd) of the next ref_group_norm1 call */
 /* GroupNorm(1,C) over x [B,C,T] (NormConv1d.cs:155); `sub` selects the canonical block view (gn_sums) */
 REF_API void ref_group_norm1(const float* x, int64_t B, int C, int64_t T, int sub, const float* gamma, const float* beta, float* y) {
 #pragma omp parallel for schedule(static)
@@ -153,6 +170,7 @@ REF_API void ref_group_norm1(const float* x, int64_t B, int C, int64_t T, int su
         if (var < 0.0) var = 0.0;
         const float r = (float)(1.0 / sqrt(var + 1e-5));
         const float muf = (float)mu;
+        if (gn_stats_sink) { gn_stats_sink[2 * b] = muf; gn_stats_sink[2 * b + 1] = r; }
         for (int c = 0; c < C; c++)
             for (int64_t t = 0; t < T; t++) {
                 const int64_t o = (b * C + c) * T + t;
@@ -163,6 +181,33 @@ REF_API void ref_group_norm1(const float* x, int64_t B, int C, int64_t T, int su
 
 static inline float eluf(float x) { return x > 0.0f ? x : ref_expf(x) - 1.0f; }
 static inline float sigmoidf(float x) { return 1.0f / (1.0f + ref_expf(-x)); }
+
+/* ref_encodec_trace: keep v [B,C,L] as the next tap (lstm: the tap is elu(v); conv: with the statistics of the GroupNorm just applied) */
+static void tap(ref_encodec* m, const float* v, int64_t B, int C, int64_t L, int lstm) {
+    if (!m->tracing || m->n_taps >= REF_MAX_TAPS) return;
+    ref_tap* t = &m->taps[m->n_taps++];
+    t->C = C; t->L = L;
+    t->v = (float*)malloc(sizeof(float) * B * C * L);
+    for (int64_t i = 0; i < B * C * L; i++) t->v[i] = lstm ? eluf(v[i]) : v[i];
+    t->has_stats = !lstm && m->last_has_stats;
+    t->stats = NULL; t->raw = NULL; t->raw_L = 0;
+    if (t->has_stats) {
+        t->stats = (float*)malloc(sizeof(float) * 2 * B); memcpy(t->stats, m->last_stats, sizeof(float) * 2 * B);
+        t->raw = m->last_raw; t->raw_L = m->last_raw_L; m->last_raw = NULL;
+    }
+}
+/* GroupNorm of a conv output inside sconv / sconvT, its statistics kept for the tap */
+static void conv_group_norm(ref_encodec* m, float* y, int64_t B, int C, int64_t T, int sub, const float* g, const float* b) {
+    gn_stats_sink = m->tracing ? m->last_stats : NULL;
+    if (m->tracing) {
+        free(m->last_raw);
+        m->last_raw = (float*)malloc(sizeof(float) * B * C * T); memcpy(m->last_raw, y, sizeof(float) * B * C * T);
+        m->last_raw_L = T;
+    }
+    ref_group_norm1(y, B, C, T, sub, g, b, y);
+    gn_stats_sink = NULL;
+    m->last_has_stats = 1;
+}
 
 /* ---- SConv1d / SConvTranspose1d ----------------------------------------------------------------------- */
 typedef struct { int64_t left, right, Lz, Lout; } pad_plan;   /* Lz = length after the small-input zero pad (D9) */
@@ -185,6 +230,7 @@ static pad_plan plan_sconv(int64_t L, int k, int stride, int dil, int causal) {
 static float* sconv(ref_encodec* m, const char* key, const float* x, int64_t B, int Cin, int64_t L, int k_expect, int stride, int dil,
                     int* Cout, int64_t* Lout) {
     int d0, d1, k, owned;
+    m->last_has_stats = 0;
     const float* w = get_weight(m, key, &d0, &d1, &k, &owned);
     char nm[320];
     snprintf(nm, sizeof nm, "%s.conv.bias", key);
@@ -207,7 +253,7 @@ static float* sconv(ref_encodec* m, const char* key, const float* x, int64_t B, 
     if (m->cfg.group_norm) {
         snprintf(nm, sizeof nm, "%s.norm.weight", key); const float* g = getf(m, nm, d0);
         snprintf(nm, sizeof nm, "%s.norm.bias", key); const float* b = getf(m, nm, d0);
-        if (g && b) ref_group_norm1(y, B, d0, p.Lout, 1, g, b, y);
+        if (g && b) conv_group_norm(m, y, B, d0, p.Lout, 1, g, b);
     }
     *Cout = d0; *Lout = p.Lout;
     return y;
@@ -215,6 +261,7 @@ static float* sconv(ref_encodec* m, const char* key, const float* x, int64_t B, 
 
 static float* sconvT(ref_encodec* m, const char* key, const float* x, int64_t B, int Cin, int64_t L, int stride, int* Cout, int64_t* Lout) {
     int d0, d1, k, owned;
+    m->last_has_stats = 0;
     const float* w = get_weight(m, key, &d0, &d1, &k, &owned);
     char nm[320];
     snprintf(nm, sizeof nm, "%s.conv.bias", key);
@@ -227,7 +274,7 @@ static float* sconvT(ref_encodec* m, const char* key, const float* x, int64_t B,
     if (m->cfg.group_norm) {
         snprintf(nm, sizeof nm, "%s.norm.weight", key); const float* g = getf(m, nm, d1);
         snprintf(nm, sizeof nm, "%s.norm.bias", key); const float* b = getf(m, nm, d1);
-        if (g && b) ref_group_norm1(y, B, d1, Lfull, gn_sub_for(k, stride, d1), g, b, y);
+        if (g && b) conv_group_norm(m, y, B, d1, Lfull, gn_sub_for(k, stride, d1), g, b);
     }
     const int64_t pt = k - stride;
     int64_t right, left;
@@ -254,17 +301,20 @@ static float* resblock(ref_encodec* m, const char* key, float* x, int64_t B, int
     int Co; int64_t Lo;
     snprintf(nm, sizeof nm, "%s.shortcut", key);
     float* s = sconv(m, nm, x, B, C, L, 1, 1, 1, &Co, &Lo);
+    tap(m, s, B, Co, Lo, 0);
     float* a = elu_new(x, B * C * L);
     snprintf(nm, sizeof nm, "%s.block.1", key);
     int Ch; int64_t Lh;
     float* h = sconv(m, nm, a, B, C, L, m->cfg.residual_kernel_size, 1, 1, &Ch, &Lh);
     free(a);
+    tap(m, h, B, Ch, Lh, 0);
     a = elu_new(h, B * Ch * Lh);
     free(h);
     snprintf(nm, sizeof nm, "%s.block.3", key);
     float* y = sconv(m, nm, a, B, Ch, Lh, 1, 1, 1, &Co, &Lo);
     free(a);
     if (Lo != L || Co != C) { m->bad = 1; free(s); free(x); return y; }   /* degenerate: block branch longer than the shortcut (D9) */
+    tap(m, y, B, Co, Lo, 0);
     for (int64_t i = 0; i < B * C * L; i++) y[i] = s[i] + y[i];
     free(s); free(x);
     return y;
@@ -353,6 +403,49 @@ REF_API int64_t ref_encodec_decoded_length(const ref_encodec* m, int64_t Tz) {
     return plan_sconv(L, c->last_kernel_size, 1, 1, c->causal).Lout;
 }
 
+/* SEANetEncoder.forward on x [B,C,L] (frees x) -> [B,dimension,T']; *C and *L are updated */
+static float* encoder_stack(ref_encodec* m, float* x, int64_t B, int* C_io, int64_t* L_io) {
+    const ref_encodec_config* c = &m->cfg;
+    char nm[320];
+    int C = *C_io;
+    int64_t Lc = *L_io;
+    float* y = sconv(m, "encoder.layers.0", x, B, C, Lc, c->kernel_size, 1, 1, &C, &Lc);
+    free(x); x = y;
+    tap(m, x, B, C, Lc, 0);
+    int n = 1;
+    for (int i = c->n_ratios - 1; i >= 0 && !m->bad; i--) {
+        const int r = c->ratios[i];
+        snprintf(nm, sizeof nm, "encoder.layers.%d", n);
+        x = resblock(m, nm, x, B, C, Lc);
+        if (m->bad) break;
+        float* a = elu_new(x, B * C * Lc);
+        free(x);
+        snprintf(nm, sizeof nm, "encoder.layers.%d", n + 2);
+        int Co; int64_t Lo;
+        x = sconv(m, nm, a, B, C, Lc, 2 * r, r, 1, &Co, &Lo);
+        free(a);
+        C = Co; Lc = Lo;
+        tap(m, x, B, C, Lc, 0);
+        n += 3;
+    }
+    if (m->bad) { *C_io = C; *L_io = Lc; return x; }
+    snprintf(nm, sizeof nm, "encoder.layers.%d", n);
+    x = slstm(m, nm, x, B, C, Lc);
+    tap(m, x, B, C, Lc, 1);
+    {
+        float* a = elu_new(x, B * C * Lc);
+        free(x);
+        snprintf(nm, sizeof nm, "encoder.layers.%d", n + 2);
+        int Co; int64_t Lo;
+        x = sconv(m, nm, a, B, C, Lc, c->last_kernel_size, 1, 1, &Co, &Lo);
+        free(a);
+        C = Co; Lc = Lo;
+    }
+    tap(m, x, B, C, Lc, 0);
+    *C_io = C; *L_io = Lc;
+    return x;
+}
+
 /* Encodec.EncodeFrame: x [B,C,L] -> codes [B,n_q,T'] int64, scale [B] (normalize) , emb nullable [B,dim,T'] */
 REF_API int ref_encodec_encode_frame(ref_encodec* m, const float* x_in, int64_t B, int64_t L, int n_q, int64_t* codes, float* scale_out,
                                      float* emb_out) {
@@ -385,33 +478,8 @@ REF_API int ref_encodec_encode_frame(ref_encodec* m, const float* x_in, int64_t 
         }
     }
     int64_t Lc = L;
-    float* y = sconv(m, "encoder.layers.0", x, B, C, Lc, c->kernel_size, 1, 1, &C, &Lc);
-    free(x); x = y;
-    int n = 1;
-    for (int i = c->n_ratios - 1; i >= 0 && !m->bad; i--) {
-        const int r = c->ratios[i];
-        snprintf(nm, sizeof nm, "encoder.layers.%d", n);
-        x = resblock(m, nm, x, B, C, Lc);
-        float* a = elu_new(x, B * C * Lc);
-        free(x);
-        snprintf(nm, sizeof nm, "encoder.layers.%d", n + 2);
-        int Co; int64_t Lo;
-        x = sconv(m, nm, a, B, C, Lc, 2 * r, r, 1, &Co, &Lo);
-        free(a);
-        C = Co; Lc = Lo;
-        n += 3;
-    }
-    snprintf(nm, sizeof nm, "encoder.layers.%d", n);
-    x = slstm(m, nm, x, B, C, Lc);
-    {
-        float* a = elu_new(x, B * C * Lc);
-        free(x);
-        snprintf(nm, sizeof nm, "encoder.layers.%d", n + 2);
-        int Co; int64_t Lo;
-        x = sconv(m, nm, a, B, C, Lc, c->last_kernel_size, 1, 1, &Co, &Lo);
-        free(a);
-        C = Co; Lc = Lo;
-    }
+    x = encoder_stack(m, x, B, &C, &Lc);
+    if (m->bad) { free(x); return -1; }
     const int64_t Tz = Lc;
     const int D = C;
     if (emb_out) memcpy(emb_out, x, sizeof(float) * B * D * Tz);
@@ -436,6 +504,43 @@ REF_API int ref_encodec_encode_frame(ref_encodec* m, const float* x_in, int64_t 
     return m->bad ? -1 : (int)Tz;
 }
 
+/* SEANetDecoder.forward on x [B,dimension,T'] (frees x) -> [B,channels,L]; *C and *L are updated */
+static float* decoder_stack(ref_encodec* m, float* x, int64_t B, int* C_io, int64_t* L_io) {
+    const ref_encodec_config* c = &m->cfg;
+    char nm[320];
+    int C = *C_io; int64_t L = *L_io;
+    float* y = sconv(m, "decoder.layers.0", x, B, C, L, c->kernel_size, 1, 1, &C, &L);
+    free(x); x = y;
+    tap(m, x, B, C, L, 0);
+    x = slstm(m, "decoder.layers.1", x, B, C, L);
+    tap(m, x, B, C, L, 1);
+    int n = 2;
+    for (int i = 0; i < c->n_ratios && !m->bad; i++) {
+        const int r = c->ratios[i];
+        float* a = elu_new(x, B * C * L);
+        free(x);
+        snprintf(nm, sizeof nm, "decoder.layers.%d", n + 1);
+        int Co; int64_t Lo;
+        x = sconvT(m, nm, a, B, C, L, r, &Co, &Lo);
+        free(a);
+        C = Co; L = Lo;
+        tap(m, x, B, C, L, 0);
+        snprintf(nm, sizeof nm, "decoder.layers.%d", n + 2);
+        x = resblock(m, nm, x, B, C, L);
+        n += 3;
+    }
+    if (m->bad) { *C_io = C; *L_io = L; return x; }
+    float* a = elu_new(x, B * C * L);
+    free(x);
+    snprintf(nm, sizeof nm, "decoder.layers.%d", n + 1);
+    int Co; int64_t Lo;
+    x = sconv(m, nm, a, B, C, L, c->last_kernel_size, 1, 1, &Co, &Lo);
+    free(a);
+    tap(m, x, B, Co, Lo, 0);
+    *C_io = Co; *L_io = Lo;
+    return x;
+}
+
 /* Encodec.DecodeFrame: codes [B,n_q,T'] -> out [B,channels,Lout] (x scale[b] when scale != NULL) */
 REF_API int ref_encodec_decode_frame(ref_encodec* m, const int64_t* codes, int64_t B, int n_q, int64_t Tz, const float* scale, float* out,
                                      float* emb_out) {
@@ -456,34 +561,51 @@ REF_API int ref_encodec_decode_frame(ref_encodec* m, const int64_t* codes, int64
                 }
     }
     if (emb_out) memcpy(emb_out, x, sizeof(float) * B * D * Tz);
-    int C = D; int64_t L = Tz;
-    float* y = sconv(m, "decoder.layers.0", x, B, C, L, c->kernel_size, 1, 1, &C, &L);
-    free(x); x = y;
-    x = slstm(m, "decoder.layers.1", x, B, C, L);
-    int n = 2;
-    for (int i = 0; i < c->n_ratios && !m->bad; i++) {
-        const int r = c->ratios[i];
-        float* a = elu_new(x, B * C * L);
-        free(x);
-        snprintf(nm, sizeof nm, "decoder.layers.%d", n + 1);
-        int Co; int64_t Lo;
-        x = sconvT(m, nm, a, B, C, L, r, &Co, &Lo);
-        free(a);
-        C = Co; L = Lo;
-        snprintf(nm, sizeof nm, "decoder.layers.%d", n + 2);
-        x = resblock(m, nm, x, B, C, L);
-        n += 3;
-    }
-    float* a = elu_new(x, B * C * L);
-    free(x);
-    snprintf(nm, sizeof nm, "decoder.layers.%d", n + 1);
-    int Co; int64_t Lo;
-    x = sconv(m, nm, a, B, C, L, c->last_kernel_size, 1, 1, &Co, &Lo);
-    free(a);
+    int Co = D; int64_t Lo = Tz;
+    x = decoder_stack(m, x, B, &Co, &Lo);
+    if (m->bad) { free(x); return -1; }
     for (int64_t b = 0; b < B; b++)
         for (int64_t i = 0; i < Co * Lo; i++) out[b * Co * Lo + i] = scale ? x[b * Co * Lo + i] * scale[b] : x[b * Co * Lo + i];
     free(x);
     return m->bad ? -1 : (int)Lo;
+}
+
+/* The activations between the layers of one stack.  decoder == 0: SEANetEncoder on x [B,channels,L] (no RMS normalisation); else SEANetDecoder
+ * on x [B,dimension,L].  Taps in the order the stacks produce them -- encoder: first conv | per stage: shortcut s, branch h, branch y,
+ * down-conv | elu(x + lstm(x)) | last conv; decoder: first conv | elu(x + lstm(x)) | per stage: up-conv, s, h, y | last conv -- each after its
+ * GroupNorm and before the next ELU.  Returns the number of taps kept (read them with ref_encodec_trace_get), -1 where the stack fails. */
+REF_API int ref_encodec_trace(ref_encodec* m, int decoder, const float* x_in, int64_t B, int64_t L) {
+    const ref_encodec_config* c = &m->cfg;
+    taps_free(m);
+    m->bad = 0;
+    m->tracing = 1;
+    m->last_stats = (float*)calloc(2 * B, sizeof(float));
+    int C = decoder ? c->dimension : c->channels;
+    float* x = (float*)malloc(sizeof(float) * B * C * L);
+    memcpy(x, x_in, sizeof(float) * B * C * L);
+    int64_t Lc = L;
+    x = decoder ? decoder_stack(m, x, B, &C, &Lc) : encoder_stack(m, x, B, &C, &Lc);
+    free(x);
+    m->tracing = 0;
+    return m->bad ? -1 : m->n_taps;
+}
+/* shape of tap i (out == NULL) or its values [B,C,L] and, where it has them, the [B][2] (mean, rstd) of its GroupNorm; returns has_stats, -1: no such tap */
+REF_API int ref_encodec_trace_get(const ref_encodec* m, int i, int64_t B, int* C, int64_t* L, float* out, float* stats) {
+    if (i < 0 || i >= m->n_taps) return -1;
+    const ref_tap* t = &m->taps[i];
+    if (C) *C = t->C;
+    if (L) *L = t->L;
+    if (out) memcpy(out, t->v, sizeof(float) * B * t->C * t->L);
+    if (stats && t->has_stats) memcpy(stats, t->stats, sizeof(float) * 2 * B);
+    return t->has_stats;
+}
+
+/* the conv output [B,C,*L] the statistics of tap i were taken on (out == NULL: its length alone); -1: the tap has none */
+REF_API int ref_encodec_trace_raw(const ref_encodec* m, int i, int64_t B, int64_t* L, float* out) {
+    if (i < 0 || i >= m->n_taps || !m->taps[i].raw) return -1;
+    if (L) *L = m->taps[i].raw_L;
+    if (out) memcpy(out, m->taps[i].raw, sizeof(float) * B * m->taps[i].C * m->taps[i].raw_L);
+    return 0;
 }
 
 /* DSP.LinearOverlapAdd: `rows` independent rows; frame f holds rows x lens[f] samples at frames[offs[f]..] */

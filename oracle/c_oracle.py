@@ -91,6 +91,9 @@ def lib():
             getattr(L, f).argtypes = [C.c_void_p, C.c_int64]
         L.ref_encodec_encode_frame.argtypes = [C.c_void_p, f32p, C.c_int64, C.c_int64, C.c_int, i64p, C.c_void_p, C.c_void_p]
         L.ref_encodec_decode_frame.argtypes = [C.c_void_p, i64p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, f32p, C.c_void_p]
+        L.ref_encodec_trace.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int64, C.c_int64]
+        L.ref_encodec_trace_get.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+        L.ref_encodec_trace_raw.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
         L.ref_linear_overlap_add.argtypes = [f32p, i64p, i64p, C.c_int, C.c_int64, C.c_int64, f32p, C.c_int64]
         L.ref_group_norm1.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, C.c_int, f32p, f32p, f32p]
         _lib = L
@@ -400,6 +403,31 @@ class RefEncodec:
         if lib().ref_encodec_decode_frame(self._h, codes, B, nq, Tz, _opt(sc), out, None) < 0:
             raise RuntimeError("ref_encodec_decode_frame failed")
         return out
+
+    def trace(self, x, decoder=False):
+        """Every activation between the layers of the SEANet encoder on x [B,channels,L] (no RMS normalisation) or, decoder=True, of the decoder
+        on x [B,dimension,L]: a list of (tap [B,C,L'], stats [B,2] = (mean, rstd) of its GroupNorm or None, raw = the conv output those
+        statistics were taken on -- untrimmed behind a transposed convolution -- or None), each tap after its GroupNorm and before the next ELU;
+        the LSTM tap is elu(x + lstm(x)).  Order: see ref_encodec_trace in oracle/c/nc_ref_encodec.c."""
+        x = np.ascontiguousarray(x, np.float32)
+        B, _, L = x.shape
+        n = lib().ref_encodec_trace(self._h, int(bool(decoder)), x, B, L)
+        if n < 0:
+            raise RuntimeError("ref_encodec_trace failed (a residual block sees too few samples, or missing tensors)")
+        taps = []
+        for i in range(n):
+            Cc, Lt = C.c_int(), C.c_int64()
+            lib().ref_encodec_trace_get(self._h, i, B, C.byref(Cc), C.byref(Lt), None, None)
+            v = np.empty((B, Cc.value, Lt.value), np.float32); st = np.empty((B, 2), np.float32)
+            has = lib().ref_encodec_trace_get(self._h, i, B, None, None, v.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p))
+            raw = None
+            if has == 1:
+                Lr = C.c_int64()
+                lib().ref_encodec_trace_raw(self._h, i, B, C.byref(Lr), None)
+                raw = np.empty((B, Cc.value, Lr.value), np.float32)
+                lib().ref_encodec_trace_raw(self._h, i, B, None, raw.ctypes.data_as(C.c_void_p))
+            taps.append((v, st if has == 1 else None, raw))
+        return taps
 
     def decode(self, frames):
         if len(frames) == 0:

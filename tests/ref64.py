@@ -171,6 +171,12 @@ def aten_tol(f, M, *args, **kw):
     return want, M * err, err
 
 
+def aten_errors(f, *args, **kw):
+    """The two references of aten_tol with the whole error array: (binary64 answer, |ATen's binary32 answer - binary64| per element)."""
+    want = f(*args, dtype=torch.float64, **kw)
+    return want, np.abs(f(*args, dtype=torch.float32, **kw).astype(np.float64) - want)
+
+
 # ------------------------------------------------------------------------------------------------------------- quantizers
 def vq_distances(z, codebook, kind="dac"):
     """Squared distances of every frame of z [B,D,T] to every row of codebook [N,D] in binary64 -> (dist [B,T,N], argmin [B,T], top-2 gap
@@ -192,3 +198,89 @@ def vq_distances(z, codebook, kind="dac"):
     part = np.partition(dist, 1, axis=-1)
     gap = part[:, 1] - part[:, 0]
     return dist.reshape(B, T, -1), idx.reshape(B, T), gap.reshape(B, T), bound.reshape(B, T, -1)
+
+
+# ------------------------------------------------------------------------------------------------------------- Encodec (SEANet) layers
+# Written from the definitions of the layers (SConv1d / SConvTranspose1d of the EnCodec paper's SEANet with the small-input path as the
+# port has it, torch.nn.GroupNorm, torch.nn.LSTM); every function takes `dtype` so that aten_tol can run it in binary32.
+def sconv_pad_plan(L, k, stride, causal):
+    """SConv1d's padding for rows of L samples -> (left, right, zero_ext).  padding_total = k - stride; extra right padding so that the last
+    window is full: n = (L - k + padding_total) / stride + 1, ideal = (ceil(n) - 1) * stride + (k - padding_total), extra = ideal - L;
+    causal: all of padding_total on the left, else right = padding_total // 2 and left the rest; `extra` goes to the right.  A row not
+    longer than the larger of the two pads cannot be reflected: it is first extended by zeros on the right to max_pad + 1 samples, and that
+    extension is NOT trimmed afterwards (deviation D9 of DESIGN.md: the port keeps it, the output is longer)."""
+    pt = k - stride
+    n = (L - k + pt) / stride + 1
+    extra = (int(np.ceil(n)) - 1) * stride + (k - pt) - L
+    if causal:
+        left, right = pt, extra
+    else:
+        right = pt // 2
+        left, right = pt - right, right + extra
+    mx = max(left, right)
+    return left, right, (mx - L + 1 if L <= mx else 0)
+
+
+def sconv_padded(x, k, stride, causal):
+    """The padded rows SConv1d convolves: zero extension (small rows), then reflect padding (left, right)."""
+    left, right, zext = sconv_pad_plan(x.shape[-1], k, stride, causal)
+    if zext:
+        x = F.pad(x, (0, zext))
+    return F.pad(x, (left, right), mode="reflect") if left or right else x
+
+
+def two_pass_stats(y, eps=1e-5):
+    """(mean, 1 / sqrt(var + eps)) over all but the first axis of y, two passes in binary64 -> [B,2]; also E[x^2] / var per row."""
+    y = np.asarray(y, np.float64).reshape(y.shape[0], -1)
+    mu = y.mean(axis=1)
+    var = ((y - mu[:, None]) ** 2).mean(axis=1)
+    with np.errstate(divide="ignore"):
+        ratio = (y ** 2).mean(axis=1) / var
+    return np.stack([mu, 1.0 / np.sqrt(var + eps)], axis=1), ratio
+
+
+def _seanet_in(x, x2, elu_in, dtype):
+    v = _t(x, dtype)
+    if x2 is not None:
+        v = v + _t(x2, dtype)
+    return F.elu(v) if elu_in else v
+
+
+def seanet_conv(x, w, b, stride=1, causal=False, gn=None, elu_in=False, x2=None, dtype=torch.float64):
+    """[ELU](x [+ x2]) -> SConv1d pad -> conv1d(w [Cout,Cin,K], b) -> [GroupNorm(1, Cout), eps 1e-5, affine gn = (gamma, beta)]."""
+    v = sconv_padded(_seanet_in(x, x2, elu_in, dtype), w.shape[2], stride, causal)
+    y = F.conv1d(v, _t(w, dtype), _t(b, dtype), stride=stride)
+    if gn is not None:
+        y = F.group_norm(y, 1, _t(gn[0], dtype), _t(gn[1], dtype), 1e-5)
+    return y.numpy()
+
+
+def seanet_conv_transpose(x, w, b, stride, causal=False, gn=None, elu_in=False, x2=None, dtype=torch.float64):
+    """[ELU](x [+ x2]) -> conv_transpose1d(w [Cin,Cout,K], b) -> [GroupNorm(1, Cout) over the UNTRIMMED output] -> trim padding_total =
+    K - stride samples: all on the right when causal, else right = padding_total // 2 and the rest on the left."""
+    y = F.conv_transpose1d(_seanet_in(x, x2, elu_in, dtype), _t(w, dtype), _t(b, dtype), stride=stride)
+    if gn is not None:
+        y = F.group_norm(y, 1, _t(gn[0], dtype), _t(gn[1], dtype), 1e-5)
+    pt = w.shape[2] - stride
+    right = pt if causal else pt // 2
+    left = pt - right
+    return y[..., left:y.shape[-1] - right].contiguous().numpy()
+
+
+def slstm_elu(x, layers, dtype=torch.float64):
+    """elu(x + LSTM(x)) on x [B,C,T]: torch.nn.LSTM over the time axis, zero initial state; layers = [(w_ih, w_hh, b_ih, b_hh), ...]."""
+    C = x.shape[1]
+    lstm = torch.nn.LSTM(C, C, num_layers=len(layers)).to(dtype)
+    with torch.no_grad():
+        for i, (wih, whh, bih, bhh) in enumerate(layers):
+            getattr(lstm, f"weight_ih_l{i}").copy_(_t(wih, dtype)); getattr(lstm, f"weight_hh_l{i}").copy_(_t(whh, dtype))
+            getattr(lstm, f"bias_ih_l{i}").copy_(_t(bih, dtype)); getattr(lstm, f"bias_hh_l{i}").copy_(_t(bhh, dtype))
+        v = _t(x, dtype).permute(2, 0, 1)
+        y, _ = lstm(v)
+        return F.elu(y + v).permute(1, 2, 0).contiguous().numpy()
+
+
+def rms_scale(x):
+    """Encodec's per-clip scale: sqrt(mean(mono^2)) + 1e-8 with mono the channel mean of x [B,C,T], binary64 -> [B]."""
+    mono = np.asarray(x, np.float64).mean(axis=1)
+    return np.sqrt((mono ** 2).mean(axis=1)) + 1e-8
