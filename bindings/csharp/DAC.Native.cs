@@ -164,6 +164,43 @@ public sealed unsafe class DACNative : INeuralCodec
         return codes;
     }
 
+    /// <summary>Clips of unequal lengths in one call: pcmPacked holds clip b behind clip b-1 (lengths[b] samples each); returns the packed
+    /// codes, clip b as [nQ, frames[b]] row-major.  Clip b's codes are those of Encode on that clip alone, bit for bit.</summary>
+    public long[] EncodeRagged(float[] pcmPacked, long[] lengths, int nQ, out long[] frames)
+    {
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        ArgumentNullException.ThrowIfNull(lengths);
+        frames = new long[lengths.Length];
+        int rows = nQ <= 0 || nQ > _config.NumCodebooks ? _config.NumCodebooks : nQ;
+        fixed (long* pl = lengths) fixed (long* pf = frames)
+            NcMi355x.Check(NcMi355x.nc_dac_ragged_query(_h, lengths.Length, pl, pf, null));
+        long total = 0;
+        foreach (long f in frames) total += rows * f;
+        var codes = new long[total];
+        fixed (float* p = pcmPacked) fixed (long* pl = lengths) fixed (long* pc = codes)
+            NcMi355x.Check(NcMi355x.nc_dac_encode_ragged(_h, p, lengths.Length, pl, 0, nQ, pc));
+        return codes;
+    }
+
+    /// <summary>FromCodes then Decode of clips of unequal lengths in one call: codesPacked as EncodeRagged returns it; the packed PCM holds
+    /// decodedLens[b] samples per clip.</summary>
+    public float[] DecodeRagged(long[] codesPacked, long[] frames, int nQ, out long[] decodedLens)
+    {
+        ArgumentNullException.ThrowIfNull(codesPacked);
+        ArgumentNullException.ThrowIfNull(frames);
+        var lens = new long[frames.Length];
+        decodedLens = new long[frames.Length];
+        for (int b = 0; b < frames.Length; ++b) lens[b] = (frames[b] - 1) * _hopLength + 1;   // any length with frames[b] frames
+        fixed (long* pl = lens) fixed (long* pd = decodedLens)
+            NcMi355x.Check(NcMi355x.nc_dac_ragged_query(_h, frames.Length, pl, null, pd));
+        long total = 0;
+        foreach (long n in decodedLens) total += n;
+        var pcm = new float[total];
+        fixed (long* pc = codesPacked) fixed (long* pf = frames) fixed (float* pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_dac_decode_codes_ragged(_h, pc, frames.Length, pf, nQ, pp));
+        return pcm;
+    }
+
     public void Dispose()                                                           // Models/DAC.cs:329-338
     {
         if (_h != IntPtr.Zero) { NcMi355x.nc_codec_destroy(_h); _h = IntPtr.Zero; }

@@ -159,6 +159,38 @@ public sealed unsafe class SNACNative : INeuralCodec
         return result;
     }
 
+    /// <summary>Clips of unequal lengths in one call: pcmPacked holds clip b behind clip b-1; returns the packed codes, the levels of a clip
+    /// side by side (codesPerClip[b] values), clip after clip.  Clip b's codes are those of Encode(float[]) on that clip alone.</summary>
+    public long[] EncodeRagged(float[] pcmPacked, long[] lengths, out long[] frames, out long[] codesPerClip)
+    {
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        ArgumentNullException.ThrowIfNull(lengths);
+        frames = new long[lengths.Length];
+        codesPerClip = new long[lengths.Length];
+        fixed (long* pl = lengths) fixed (long* pf = frames) fixed (long* pn = codesPerClip)
+            NcMi355x.Check(NcMi355x.nc_snac_ragged_query(_h, lengths.Length, pl, pf, pn, null));
+        long total = 0;
+        foreach (long n in codesPerClip) total += n;
+        var codes = new long[total];
+        fixed (float* p = pcmPacked) fixed (long* pl = lengths) fixed (long* pc = codes)
+            NcMi355x.Check(NcMi355x.nc_snac_encode_ragged(_h, p, lengths.Length, pl, pc));
+        return codes;
+    }
+
+    /// <summary>Decode of clips of unequal lengths in one call: frames[b] * hop samples per clip.  noise: every clip's B = 1 noise block, clip
+    /// after clip; null draws clip b from seed + b.</summary>
+    public float[] DecodeRagged(long[] codesPacked, long[] frames, float[]? noise = null, ulong seed = 0)
+    {
+        ArgumentNullException.ThrowIfNull(codesPacked);
+        ArgumentNullException.ThrowIfNull(frames);
+        long total = 0;
+        foreach (long f in frames) total += f * _hopLength;
+        var pcm = new float[total];
+        fixed (long* pc = codesPacked) fixed (long* pf = frames) fixed (float* pn = noise) fixed (float* pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_snac_decode_ragged(_h, pc, frames.Length, pf, pn, seed, pp));
+        return pcm;
+    }
+
     public void Dispose()
     {
         if (_h != IntPtr.Zero) { NcMi355x.nc_codec_destroy(_h); _h = IntPtr.Zero; }

@@ -255,8 +255,84 @@ typedef struct nc_chunk_plan {
 } nc_chunk_plan;
 NC_API nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t B, int64_t frames, nc_chunk_plan* out);
 
+/* --------------------------------------------------------------------------------- ragged batches
+ * One call on B clips of UNEQUAL lengths (dataset tokenisation, Dia voice prompts, decoding generated code matrices).  Clip b's output
+ * equals, bit for bit, the uniform call on that clip alone (B = 1); zero-padding the clips to the longest one would not (every layer pads
+ * with zeros at its own edge, so a short clip inside a longer row sees biases and Snake outputs leak back into its last frames).
+ * Layout: with the halos of the direction (halo_left / halo_right as nc_codec_chunk_plan reports them), a kept width C (a multiple of
+ * align) and W = C + halo_left + halo_right,
+ *   - a clip of F >= W frames is covered by windows of exactly W frames starting at min(j * C, F - W): the first is left-aligned and the
+ *     last right-aligned to the clip, so both outer edges are true clip edges; every frame is kept by exactly one window and keeps clear
+ *     of every interior window edge by the halo;
+ *   - clips of F < W frames are not cut: clips of equal F form one group, a group is a batch of one-window clips of width F;
+ *   - windows of all long clips run through the uniform launch sequences in batches of at most max_windows rows (as do the groups), so
+ *     the activation arena is bounded by max_windows * W whatever B and the clip lengths.
+ * Rows are gathered and kept columns scattered by table-driven kernels, one launch per tensor and batch.  Packed layouts: clip b's data
+ * follows clip b-1's with no gap; lengths[] / frames[] are HOST arrays in both forms.  The *_dev forms take device pointers for the packed
+ * tensors and enqueue on the handle's stream; the plain forms take host pointers, are synchronous, and stage the whole packed tensors on the
+ * device.  NC_EINVAL for B <= 0, a length <= 0 or a null pointer; whatever status the uniform call on any one clip would return is returned
+ * for the whole batch; every refusal is decided before anything is launched.
+ * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair, nc_snac_encode_tensor, the group calls, and Encodec
+ * (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context, so no window of a clip stands for the clip). */
+typedef struct nc_ragged_plan {
+    int64_t window_frames;     /* W */
+    int64_t kept_frames;       /* C */
+    int64_t halo_left, halo_right;
+    int64_t n_windows;         /* windows of the clips with F >= W */
+    int64_t n_window_batches;  /* launch batches they run in */
+    int64_t n_exact_groups;    /* distinct F among the clips with F < W */
+    int64_t n_rows;            /* n_windows + clips with F < W: entries of the window list */
+    int64_t n_batches;         /* all launch batches (a group of more than max_windows clips is split) */
+    int64_t arena_bytes;       /* activation arena: max_windows rows of W frames */
+    int64_t total_frames;      /* sum of F_b */
+    int64_t total_codes;       /* int64 codes of all clips with every codebook (DAC: n_codebooks * F_b; SNAC: sum_i F_b / vq_strides[i]) */
+    int64_t total_samples;     /* decoded samples of all clips */
+} nc_ragged_plan;
+/* one row of a launch batch: frames [start, start + width) of `clip`, of which [keep_start, keep_start + keep_frames) are kept */
+typedef struct nc_ragged_window {
+    int32_t clip, batch;
+    int64_t start, width;
+    int64_t keep_start, keep_frames;
+} nc_ragged_window;
+/* The planner on a config alone (host functions: no handle, no device).  decode != 0: decode.  kept_frames / max_windows: 0 = the
+ * defaults of nc_codec_set_ragged_window.  windows (nullable) receives the first `cap` rows in launch order. */
+NC_API nc_status nc_dac_ragged_windows(const nc_dac_config* cfg, int32_t decode, int32_t B, const int64_t* frames, int64_t kept_frames,
+                                       int32_t max_windows, nc_ragged_plan* out, nc_ragged_window* windows, int64_t cap);
+NC_API nc_status nc_snac_ragged_windows(const nc_snac_config* cfg, int32_t decode, int32_t B, const int64_t* frames, int64_t kept_frames,
+                                        int32_t max_windows, nc_ragged_plan* out, nc_ragged_window* windows, int64_t cap);
+/* Per-handle kept width C (rounded up to align) and rows per launch batch; 0 selects the default, the best measured pair
+ * (profiles/ragged_bench.json): 128 frames for DAC, 256 for SNAC, 128 rows. */
+NC_API nc_status nc_codec_set_ragged_window(nc_codec* h, int64_t kept_frames, int32_t max_windows);
+/* what a ragged call on these frame counts would do under the handle's setting */
+NC_API nc_status nc_codec_ragged_plan(const nc_codec* h, int32_t decode, int32_t B, const int64_t* frames, nc_ragged_plan* out);
+
+/* frames F_b and decoded samples of every clip (outputs nullable) */
+NC_API nc_status nc_dac_ragged_query(const nc_codec* h, int32_t B, const int64_t* lengths, int64_t* frames, int64_t* decoded_lens);
+/* pcm_packed [sum lengths] -> codes_packed: clip b as [n_q, F_b] row-major, clip after clip (sample_rate / n_q as nc_dac_encode) */
+NC_API nc_status nc_dac_encode_ragged(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int32_t sample_rate,
+                                      int32_t n_q, int64_t* codes_packed);
+NC_API nc_status nc_dac_encode_ragged_dev(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int32_t sample_rate,
+                                          int32_t n_q, int64_t* codes_packed);
+/* FromCodes then Decode per window: codes_packed as above -> pcm_packed, clip b yields decoded_lens[b] samples */
+NC_API nc_status nc_dac_decode_codes_ragged(nc_codec* h, const int64_t* codes_packed, int32_t B, const int64_t* frames, int32_t n_q,
+                                            float* pcm_packed);
+NC_API nc_status nc_dac_decode_codes_ragged_dev(nc_codec* h, const int64_t* codes_packed, int32_t B, const int64_t* frames, int32_t n_q,
+                                                float* pcm_packed);
+/* frames F_b (Preprocess pads), codes per clip and decoded samples of every clip (outputs nullable) */
+NC_API nc_status nc_snac_ragged_query(const nc_codec* h, int32_t B, const int64_t* lengths, int64_t* frames, int64_t* codes_per_clip,
+                                      int64_t* decoded_lens);
+/* codes_packed: the levels of a clip side by side as in nc_snac_encode (codes_per_clip[b] values), clip after clip */
+NC_API nc_status nc_snac_encode_ragged(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int64_t* codes_packed);
+NC_API nc_status nc_snac_encode_ragged_dev(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int64_t* codes_packed);
+/* noise: every clip's B = 1 noise block (nc_snac_noise_len(1, F_b) floats), clip after clip; NULL: clip b is drawn exactly as
+ * nc_snac_decode(B = 1, seed + b) draws it */
+NC_API nc_status nc_snac_decode_ragged(nc_codec* h, const int64_t* codes_packed, int32_t B, const int64_t* frames, const float* noise,
+                                       uint64_t seed, float* pcm_packed);
+NC_API nc_status nc_snac_decode_ragged_dev(nc_codec* h, const int64_t* codes_packed, int32_t B, const int64_t* frames, const float* noise,
+                                           uint64_t seed, float* pcm_packed);
+
 /* -------------------------------------------------------------------------------------- Encodec
- * replaces: new Encodec(EncodecConfig)             NeuralCodecs.Torch/Models/Encodec.cs:46-90
+ * replaces: new Encodec(EncodecConfig)            NeuralCodecs.Torch/Models/Encodec.cs:46-90
  * Only channels / dimension / norm / causal reach SEANet in the reference (Encodec.cs:57-68, deviation D11); the other SEANet
  * fields are its hard defaults (SEANetEncoder.cs:37-56) and are carried here so reduced-width test models can be built. */
 typedef struct {

@@ -67,6 +67,17 @@ class NcChunkPlan(C.Structure):
                 ("arena_bytes", C.c_int64)]
 
 
+class NcRaggedPlan(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("window_frames", "kept_frames", "halo_left", "halo_right", "n_windows", "n_window_batches",
+                                         "n_exact_groups", "n_rows", "n_batches", "arena_bytes", "total_frames", "total_codes",
+                                         "total_samples")]
+
+
+class NcRaggedWindow(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("batch", C.c_int32), ("start", C.c_int64), ("width", C.c_int64), ("keep_start", C.c_int64),
+                ("keep_frames", C.c_int64)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
 
 _lib = None
@@ -118,6 +129,22 @@ SYMBOLS = [
     ("nc_snac_halo", C.c_int, [C.POINTER(NcSnacConfig), C.POINTER(NcHalo)]),
     ("nc_codec_set_chunk_frames", C.c_int, [_P, C.c_int64]),
     ("nc_codec_chunk_plan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(NcChunkPlan)]),
+    ("nc_dac_ragged_windows", C.c_int, [C.POINTER(NcDacConfig), C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(NcRaggedPlan), _P,
+                                        C.c_int64]),
+    ("nc_snac_ragged_windows", C.c_int, [C.POINTER(NcSnacConfig), C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(NcRaggedPlan), _P,
+                                         C.c_int64]),
+    ("nc_codec_set_ragged_window", C.c_int, [_P, C.c_int64, C.c_int32]),
+    ("nc_codec_ragged_plan", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(NcRaggedPlan)]),
+    ("nc_dac_ragged_query", C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    ("nc_dac_encode_ragged", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    ("nc_dac_encode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    ("nc_dac_decode_codes_ragged", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("nc_dac_decode_codes_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("nc_snac_ragged_query", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_snac_encode_ragged", C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    ("nc_snac_encode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    ("nc_snac_decode_ragged", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint64, _P]),
+    ("nc_snac_decode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint64, _P]),
     ("nc_encodec_create", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int, C.POINTER(_P)]),
     ("nc_encodec_set_bandwidth", C.c_int, [_P, C.c_float]),
     ("nc_encodec_query", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32,
@@ -238,6 +265,32 @@ def check(status: int) -> None:
     raise NcError(f"status {status}: {msg}")
 
 
+def i64_array(values):
+    """A host int64 array for the lengths[] / frames[] arguments of the ragged calls."""
+    v = [int(x) for x in values]
+    return (C.c_int64 * len(v))(*v)
+
+
+def ragged_windows(fn, c_cfg, frames, decode: bool = False, kept_frames: int = 0, max_windows: int = 0):
+    """nc_{dac,snac}_ragged_windows: (plan dict, list of window dicts in launch order) from a config alone -- no device."""
+    f = i64_array(frames)
+    p = NcRaggedPlan()
+    check(fn(C.byref(c_cfg), 1 if decode else 0, len(f), f, int(kept_frames), int(max_windows), C.byref(p), None, 0))
+    rows = (NcRaggedWindow * max(1, int(p.n_rows)))()
+    check(fn(C.byref(c_cfg), 1 if decode else 0, len(f), f, int(kept_frames), int(max_windows), C.byref(p), rows, int(p.n_rows)))
+    plan = {k: int(getattr(p, k)) for k, _ in NcRaggedPlan._fields_}
+    return plan, [{k: int(getattr(rows[i], k)) for k, _ in NcRaggedWindow._fields_} for i in range(int(p.n_rows))]
+
+
+def split_packed(flat, sizes):
+    """Views of a packed 1-D array or tensor, one per clip."""
+    out, o = [], 0
+    for n in sizes:
+        out.append(flat[o:o + n])
+        o += n
+    return out
+
+
 class ProfileMixin:
     """HIP-event kernel-class profile of a codec handle (nc_codec_profile_*): the numbers bench.py's `roofline` objects come from."""
 
@@ -255,6 +308,17 @@ class ProfileMixin:
         p = NcChunkPlan()
         check(lib().nc_codec_chunk_plan(self._h, 1 if decode else 0, int(B), int(frames), C.byref(p)))
         return {k: int(getattr(p, k)) for k, _ in NcChunkPlan._fields_}
+
+    def set_ragged_window(self, kept_frames: int = 0, max_windows: int = 0) -> None:
+        """nc_codec_set_ragged_window: kept frames per window and rows per launch batch of the ragged calls (0 = default)."""
+        check(lib().nc_codec_set_ragged_window(self._h, int(kept_frames), int(max_windows)))
+
+    def ragged_plan(self, frames, decode: bool = False) -> dict:
+        """nc_codec_ragged_plan: what a ragged call on clips of these frame counts would do under the handle's setting."""
+        f = i64_array(frames)
+        p = NcRaggedPlan()
+        check(lib().nc_codec_ragged_plan(self._h, 1 if decode else 0, len(f), f, C.byref(p)))
+        return {k: int(getattr(p, k)) for k, _ in NcRaggedPlan._fields_}
 
     def profile_enable(self, on: bool = True):
         check(lib().nc_codec_profile_enable(self._h, 1 if on else 0))

@@ -163,10 +163,16 @@ ChunkPlan DacModel::chunk_plan(ChunkKind kind, int B, int64_t Tz) const {
     const bool fits = chunk_frames != 0 || oneshot_fits(cfg.encoder_rates, cfg.n_encoder_rates, cfg.encoder_dim, cfg.decoder_rates,
                                                         cfg.n_decoder_rates, cfg.decoder_dim, kind, Tz);
     ChunkPlan P = make_plan(chunk_frames, h, kind, Tz, fits);
-    // 3 rotating activation buffers of B x max(C * L) floats over the widest window
-    const int64_t W = P.n_chunks > 1 ? max_window(P, Tz) : Tz;
+    P.arena_bytes = arena_bytes(cfg, kind, B, P.n_chunks > 1 ? max_window(P, Tz) : Tz);
+    return P;
+}
+
+// 3 rotating activation buffers of B x max(C * L) floats over the widest window
+int64_t DacModel::arena_bytes(const nc_dac_config& cfg, ChunkKind kind, int64_t B, int64_t W) {
     int64_t maxel = 0;
     if (kind == CK_ENCODE) {
+        int64_t hop = 1;
+        for (int i = 0; i < cfg.n_encoder_rates; ++i) hop *= cfg.encoder_rates[i];
         int c = cfg.encoder_dim;
         int64_t L = W * hop;
         maxel = (int64_t)c * pitch16(L);
@@ -176,8 +182,7 @@ ChunkPlan DacModel::chunk_plan(ChunkKind kind, int B, int64_t Tz) const {
         maxel = (int64_t)cfg.decoder_dim * pitch16(L);
         for (int i = 0; i < cfg.n_decoder_rates; ++i) { L *= cfg.decoder_rates[i]; maxel = std::max(maxel, (int64_t)(cfg.decoder_dim >> (i + 1)) * pitch16(L)); }
     }
-    P.arena_bytes = 3 * (int64_t)B * maxel * 4;
-    return P;
+    return 3 * B * maxel * 4;
 }
 
 void DacModel::encode(bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents, int64_t* codes_tq) {
@@ -282,9 +287,15 @@ ChunkPlan SnacModel::chunk_plan(ChunkKind kind, int B, int64_t frames_in) const 
     const bool fits = chunk_frames != 0 || oneshot_fits(cfg.encoder_rates, cfg.n_encoder_rates, cfg.encoder_dim, cfg.decoder_rates,
                                                         cfg.n_decoder_rates, cfg.decoder_dim, kind, Tz);
     ChunkPlan P = make_plan(chunk_frames, h, kind, Tz, fits);
-    const int64_t W = P.n_chunks > 1 ? max_window(P, Tz) : Tz;
+    P.arena_bytes = arena_bytes(cfg, kind, B, P.n_chunks > 1 ? max_window(P, Tz) : Tz);
+    return P;
+}
+
+int64_t SnacModel::arena_bytes(const nc_snac_config& cfg, ChunkKind kind, int64_t B, int64_t W) {
     int64_t maxel = 0;   // reserve_act: the widest tensor of either direction
     if (kind != CK_FROM_CODES) {
+        int64_t hop = 1;
+        for (int i = 0; i < cfg.n_encoder_rates; ++i) hop *= cfg.encoder_rates[i];
         int c = cfg.encoder_dim;
         int64_t L = W * hop;
         maxel = (int64_t)c * L;
@@ -293,8 +304,7 @@ ChunkPlan SnacModel::chunk_plan(ChunkKind kind, int B, int64_t frames_in) const 
         maxel = std::max(maxel, (int64_t)cfg.decoder_dim * Ld);
         for (int i = 0; i < cfg.n_decoder_rates; ++i) { Ld = up_len(Ld, cfg.decoder_rates[i]); maxel = std::max(maxel, (int64_t)(cfg.decoder_dim >> (i + 1)) * Ld); }
     }
-    P.arena_bytes = 3 * (int64_t)B * maxel * 4;
-    return P;
+    return 3 * B * maxel * 4;
 }
 
 void SnacModel::copy_levels(int64_t* dst, bool dst_host, int64_t Td, int64_t d0, const int64_t* src, bool src_host, int64_t Ts, int64_t s0, int64_t n, int B) {

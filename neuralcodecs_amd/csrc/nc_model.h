@@ -88,6 +88,19 @@ struct Codec {
     // They are the staging buffers of every host-pointer call too: a clip that is not cut is one window.
     int64_t chunk_frames = 0;
     DevBuf ck_in, ck_codes, ck_a, ck_b, ck_out, ck_noise, ck_noise_full;
+    // nc_ragged.hip: kept width C and rows per launch batch of the ragged calls (0 = default), the descriptor tables of one call (pinned
+    // host image, device copy, the event behind the copy), the packed tensors of a host-pointer call and the drawn noise of all clips
+    int64_t ragged_kept = 0;
+    int32_t ragged_max_windows = 0;
+    struct RaggedTables {
+        DevBuf dev;
+        void* pin = nullptr;
+        size_t pin_cap = 0;
+        hipEvent_t ev = nullptr;
+        bool ev_used = false;
+        ~RaggedTables();
+    } rg_tab;
+    DevBuf rg_in, rg_out, rg_noise;
     // rows x width bytes between two pitched arrays on `stream`; either side may be a host pointer (then a 2-D memcpy), device to
     // device is the copy kernel of nc_util.hip.  All sizes are multiples of 4 bytes.
     void copy2d(void* dst, bool dst_host, size_t dpitch, const void* src, bool src_host, size_t spitch, size_t width, size_t rows);
@@ -165,6 +178,8 @@ struct DacModel : Codec {
     // launch sequence on the caller's own arrays.  encode: codes / z / latents or, with codes_tq, Dia's [B, T', n_q] matrix of all
     // codebooks; decode: from z or, with codes_tq, from such a matrix.
     ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
+    // activation arena of the launch sequence `kind` on B rows of W frames (3 rotating buffers of the widest tensor)
+    static int64_t arena_bytes(const nc_dac_config& cfg, ChunkKind kind, int64_t B, int64_t W);
     void encode(bool host, const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents, int64_t* codes_tq);
     void decode(bool host, const float* z, const int64_t* codes_tq, int n_q, int B, int64_t frames, float* pcm);
     void from_codes(bool host, const int64_t* codes, int B, int n_q, int64_t frames, float* z);
@@ -235,6 +250,7 @@ struct SnacModel : Codec {
     void decode_dev(const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);
     // the operations of the C ABI (nc_chunk.hip), as DacModel's; encode is the padded form
     ChunkPlan chunk_plan(ChunkKind kind, int B, int64_t frames) const;
+    static int64_t arena_bytes(const nc_snac_config& cfg, ChunkKind kind, int64_t B, int64_t W);
     void encode(bool host, const float* pcm, int B, int64_t T, int64_t* codes, float* z, float* zq);
     void from_codes(bool host, const int64_t* codes, int B, int64_t frames, float* zq);
     void decode(bool host, const int64_t* codes, int B, int64_t frames, const float* noise, uint64_t seed, float* pcm);

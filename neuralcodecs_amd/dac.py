@@ -52,6 +52,11 @@ def dac_halo(config: DACConfig) -> dict:
     return {k: int(getattr(h, k)) for k, _ in _lib.NcHalo._fields_}
 
 
+def dac_ragged_windows(config: DACConfig, frames, decode: bool = False, kept_frames: int = 0, max_windows: int = 0):
+    """nc_dac_ragged_windows: the window layout of a ragged call on clips of these frame counts (no device needed)."""
+    return _lib.ragged_windows(_lib.lib().nc_dac_ragged_windows, _c_config(config), frames, decode, kept_frames, max_windows)
+
+
 class DAC(_lib.ProfileMixin):
     def __init__(self, config: Optional[DACConfig] = None, device_index: int = 0):
         if config is None:
@@ -205,6 +210,57 @@ class DAC(_lib.ProfileMixin):
         z = np.empty((B, self.latent_dim, Tz), np.float32)
         _lib.check(_lib.lib().nc_dac_from_codes(self._h, c.ctypes.data, B, nq, Tz, z.ctypes.data))
         return z
+
+    # ---- ragged batches (clips of unequal lengths in one call) ------------------------------------
+    @staticmethod
+    def _pack(clips, dtype: str):
+        """list of arrays / tensors -> (one packed 1-D buffer, is_torch)"""
+        if clips is None or len(clips) == 0:
+            raise ValueError("the list of clips must not be empty")
+        if _is_torch(clips[0]):
+            import torch
+            return torch.cat([c.reshape(-1).to(getattr(torch, dtype)) for c in clips]).contiguous(), True
+        return np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=dtype).reshape(-1) for c in clips])), False
+
+    def encode_ragged(self, clips, n_quantizers: Optional[int] = None):
+        """nc_dac_encode_ragged[_dev]: 1-D clips of any lengths -> list of codes [n_q, F_b]; clip b's codes are those of encode() on
+        that clip alone, bit for bit."""
+        flat, dev = self._pack(clips, "float32")
+        B, nq = len(clips), self._nq(n_quantizers)
+        lens = [int(c.shape[-1]) if c.ndim else 0 for c in clips]
+        if any(c.ndim != 1 for c in clips):
+            raise ValueError("every clip must be 1-D")
+        sizes = [nq * self.frames(t) for t in lens]
+        if dev:
+            import torch
+            codes = torch.empty(max(1, sum(sizes)), dtype=torch.int64, device=flat.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_dac_encode_ragged_dev(self._h, flat.data_ptr(), B, _lib.i64_array(lens), 0, nq, codes.data_ptr()))
+        else:
+            codes = np.empty(max(1, sum(sizes)), np.int64)
+            _lib.check(_lib.lib().nc_dac_encode_ragged(self._h, flat.ctypes.data, B, _lib.i64_array(lens), 0, nq, codes.ctypes.data))
+        return [c.reshape(nq, -1) for c in _lib.split_packed(codes, sizes)]
+
+    def decode_codes_ragged(self, codes):
+        """nc_dac_decode_codes_ragged[_dev]: list of codes [n_q, F_b] -> list of 1-D pcm (FromCodes then Decode), each the
+        decode(from_codes()) of that clip alone, bit for bit."""
+        if codes is None or len(codes) == 0:
+            raise ValueError("the list of codes must not be empty")
+        if any(c.ndim != 2 or c.shape[0] != codes[0].shape[0] for c in codes):
+            raise ValueError("every clip's codes must be [n_q, F] with one n_q")
+        flat, dev = self._pack(codes, "int64")
+        B, nq = len(codes), int(codes[0].shape[0])
+        frames = [int(c.shape[1]) for c in codes]
+        sizes = [self.decoded_length(f) for f in frames]
+        if dev:
+            import torch
+            pcm = torch.empty(max(1, sum(sizes)), dtype=torch.float32, device=flat.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_dac_decode_codes_ragged_dev(self._h, flat.data_ptr(), B, _lib.i64_array(frames), nq, pcm.data_ptr()))
+        else:
+            pcm = np.empty(max(1, sum(sizes)), np.float32)
+            _lib.check(_lib.lib().nc_dac_decode_codes_ragged(self._h, flat.ctypes.data, B, _lib.i64_array(frames), nq, pcm.ctypes.data))
+        return _lib.split_packed(pcm, sizes)
 
     # ---- Dia <-> DAC glue (SURVEY 8f N3) -----------------------------------------------------------
     def decode_code_matrix(self, audio_codes):

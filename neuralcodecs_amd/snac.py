@@ -56,6 +56,11 @@ def snac_halo(config: SNACConfig) -> dict:
     return {k: int(getattr(h, k)) for k, _ in _lib.NcHalo._fields_}
 
 
+def snac_ragged_windows(config: SNACConfig, frames, decode: bool = False, kept_frames: int = 0, max_windows: int = 0):
+    """nc_snac_ragged_windows: the window layout of a ragged call on clips of these frame counts (no device needed)."""
+    return _lib.ragged_windows(_lib.lib().nc_snac_ragged_windows, _c_config(config), frames, decode, kept_frames, max_windows)
+
+
 class SNAC(_lib.ProfileMixin):
     def __init__(self, config: Optional[SNACConfig] = None, device_index: int = 0):
         if config is None:
@@ -266,6 +271,77 @@ class SNAC(_lib.ProfileMixin):
         _lib.check(_lib.lib().nc_snac_decode(self._h, flat.ctypes.data, B, frames, nz.ctypes.data if nz is not None else None, seed,
                                              out.ctypes.data))
         return out
+
+    # ---- ragged batches (clips of unequal lengths in one call) ------------------------------------
+    @staticmethod
+    def _pack(parts, dtype: str):
+        """flat list of arrays / tensors -> (one packed 1-D buffer, is_torch)"""
+        if _is_torch(parts[0]):
+            import torch
+            return torch.cat([p.reshape(-1).to(getattr(torch, dtype)) for p in parts]).contiguous(), True
+        return np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dtype).reshape(-1) for p in parts])), False
+
+    def encode_ragged(self, clips):
+        """nc_snac_encode_ragged[_dev]: 1-D clips of any lengths -> per clip the list of its code levels (1-D, coarse first); clip
+        b's codes are those of encode() on that clip alone, bit for bit."""
+        if clips is None or len(clips) == 0:
+            raise ValueError("the list of clips must not be empty")
+        if any(c.ndim != 1 for c in clips):
+            raise ValueError("every clip must be 1-D")
+        flat, dev = self._pack(clips, "float32")
+        B = len(clips)
+        lens = _lib.i64_array(int(c.shape[0]) for c in clips)
+        frames, per_clip = (C.c_int64 * B)(), (C.c_int64 * B)()
+        _lib.check(_lib.lib().nc_snac_ragged_query(self._h, B, lens, frames, per_clip, None))
+        if dev:
+            import torch
+            codes = torch.empty(sum(per_clip), dtype=torch.int64, device=flat.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_snac_encode_ragged_dev(self._h, flat.data_ptr(), B, lens, codes.data_ptr()))
+        else:
+            codes = np.empty(sum(per_clip), np.int64)
+            _lib.check(_lib.lib().nc_snac_encode_ragged(self._h, flat.ctypes.data, B, lens, codes.ctypes.data))
+        return [_lib.split_packed(c, [f // s for s in self.config.vq_strides]) for c, f in zip(_lib.split_packed(codes, list(per_clip)), frames)]
+
+    def decode_ragged(self, codes, noise=None, seed: int = 0):
+        """nc_snac_decode_ragged[_dev]: per clip the list of its code levels -> list of 1-D pcm.  noise: per clip the list of its
+        B = 1 NoiseBlock inputs (noise_shapes(1, F_b)); None: clip b is drawn as decode(B = 1, seed = seed + b) draws it."""
+        if codes is None or len(codes) == 0:
+            raise ValueError("the list of codes must not be empty")
+        for c in codes:
+            self._flat_codes(c)
+        B = len(codes)
+        frames = [int(c[-1].shape[-1]) * self.config.vq_strides[-1] for c in codes]
+        for c, f in zip(codes, frames):
+            if [int(np.prod(lv.shape)) * s for lv, s in zip(c, self.config.vq_strides)] != [f] * len(c):
+                raise ValueError("code level widths do not match one frame count")
+        flat, dev = self._pack([lv for c in codes for lv in c], "int64")
+        sizes = []
+        for f in frames:
+            L = f
+            for s in self.config.decoder_rates:
+                L = (L - 1) * s - 2 * (-(-s // 2)) + 2 * s + (s % 2)
+            sizes.append(L)
+        nz = None
+        if noise is not None and self.config.noise:
+            if len(noise) != B or any([int(np.prod(n.shape)) for n in nb] != [int(np.prod(sh)) for sh in self.noise_shapes(1, f)]
+                                      for nb, f in zip(noise, frames)):
+                raise ValueError("noise must hold every clip's B = 1 noise blocks")
+            nz, _ = self._pack([n for nb in noise for n in nb], "float32")
+            if dev:
+                nz = nz.to(flat.device)
+        fr = _lib.i64_array(frames)
+        if dev:
+            import torch
+            pcm = torch.empty(sum(sizes), dtype=torch.float32, device=flat.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_snac_decode_ragged_dev(self._h, flat.data_ptr(), B, fr, nz.data_ptr() if nz is not None else None,
+                                                            seed & 0xFFFFFFFFFFFFFFFF, pcm.data_ptr()))
+        else:
+            pcm = np.empty(sum(sizes), np.float32)
+            _lib.check(_lib.lib().nc_snac_decode_ragged(self._h, flat.ctypes.data, B, fr, nz.ctypes.data if nz is not None else None,
+                                                        seed & 0xFFFFFFFFFFFFFFFF, pcm.ctypes.data))
+        return _lib.split_packed(pcm, sizes)
 
     def decode_array(self, codes: Sequence, noise=None, seed: int = 0) -> np.ndarray:
         """SNAC.Decode(List<float[]>) (SNAC.cs:173-192)."""
