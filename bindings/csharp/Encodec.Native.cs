@@ -157,6 +157,43 @@ public sealed unsafe class EncodecNative : INeuralCodec
         return pcm;
     }
 
+    /// <summary>Clips of unequal lengths in one call (whole files): pcmPacked holds clip b, [Channels, lengths[b]], behind clip b-1.
+    /// Returns the packed codes -- clip b's part is the codes buffer of EncodeHost(B = 1) on that clip, its frames [nQ, T'_f] end to
+    /// end -- with nFrames[b] segments and codeFrames[b] code frames per clip, and the packed scales (nFrames[b] floats per clip).
+    /// The segments of all clips run pooled in uniform batches; every clip's result is that of Encode on it alone, bit for bit.</summary>
+    public long[] EncodeRagged(float[] pcmPacked, long[] lengths, out int[] nFrames, out long[] codeFrames, out float[] scalesPacked)
+    {
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        ArgumentNullException.ThrowIfNull(lengths);
+        nFrames = new int[lengths.Length];
+        codeFrames = new long[lengths.Length];
+        int nf, nQ;
+        long dec;
+        NcMi355x.Check(NcMi355x.nc_encodec_query(_h, 1, &nf, &nQ, null, 0, &dec));                    // n_q of the bandwidth in force
+        fixed (long* pl = lengths, pc = codeFrames) fixed (int* pn = nFrames)
+            NcMi355x.Check(NcMi355x.nc_encodec_ragged_query(_h, lengths.Length, pl, pn, pc, null));
+        var codes = new long[Math.Max(1, nQ * codeFrames.Sum())];
+        scalesPacked = new float[Math.Max(1, nFrames.Sum())];
+        fixed (float* p = pcmPacked, ps = scalesPacked) fixed (long* pl = lengths, pc = codes)
+            NcMi355x.Check(NcMi355x.nc_encodec_encode_ragged(_h, p, lengths.Length, pl, pc, ps, null));
+        return codes;
+    }
+
+    /// <summary>Decode of clips of unequal lengths in one call: codesPacked / scalesPacked as EncodeRagged returns them, lengths the
+    /// clips' sample counts; the packed PCM holds clip b as [Channels, decodedLens[b]].</summary>
+    public float[] DecodeRagged(long[] codesPacked, float[]? scalesPacked, long[] lengths, int nQ, out long[] decodedLens)
+    {
+        ArgumentNullException.ThrowIfNull(codesPacked);
+        ArgumentNullException.ThrowIfNull(lengths);
+        decodedLens = new long[lengths.Length];
+        fixed (long* pl = lengths, pd = decodedLens)
+            NcMi355x.Check(NcMi355x.nc_encodec_ragged_query(_h, lengths.Length, pl, null, null, pd));
+        var pcm = new float[Math.Max(1, Channels * decodedLens.Sum())];
+        fixed (long* pc = codesPacked, pl = lengths) fixed (float* ps = scalesPacked, pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_encodec_decode_ragged(_h, pc, Normalize ? ps : null, lengths.Length, pl, nQ, pp));
+        return pcm;
+    }
+
     // ---- the reference's members, signature for signature ---------------------------------------------------------------------------
     public Tensor Decode(List<EncodedFrame> encodedFrames)                          // Models/Encodec.cs:213-235
     {

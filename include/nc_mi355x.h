@@ -272,8 +272,10 @@ NC_API nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t 
  * tensors and enqueue on the handle's stream; the plain forms take host pointers, are synchronous, and stage the whole packed tensors on the
  * device.  NC_EINVAL for B <= 0, a length <= 0 or a null pointer; whatever status the uniform call on any one clip would return is returned
  * for the whole batch; every refusal is decided before anything is launched.
- * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair, nc_snac_encode_tensor, the group calls, and Encodec
- * (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context, so no window of a clip stands for the clip). */
+ * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair, nc_snac_encode_tensor and the group calls.
+ * Encodec clips are never cut into windows (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context, so no window
+ * of a clip stands for the clip): nc_codec_set_ragged_window / nc_codec_ragged_plan return NC_EUNSUPPORTED for Encodec handles.  Encodec
+ * has ragged calls of its own that pool the SEGMENTS of all clips, nc_encodec_*_ragged below ("Encodec ragged batches"). */
 typedef struct nc_ragged_plan {
     int64_t window_frames;     /* W */
     int64_t kept_frames;       /* C */
@@ -385,6 +387,62 @@ NC_API nc_status nc_encodec_encode_dev(nc_codec* h, const float* pcm, int32_t B,
 NC_API nc_status nc_encodec_decode(nc_codec* h, const int64_t* codes, const float* scales, int32_t B, int64_t T, int32_t n_q, float* pcm);
 NC_API nc_status nc_encodec_decode_dev(nc_codec* h, const int64_t* codes, const float* scales, int32_t B, int64_t T, int32_t n_q,
                                        float* pcm);
+
+/* ----------------------------------------------------------------------- Encodec ragged batches
+ * One call on B clips of UNEQUAL lengths (whole files: Examples/Program.cs:293-322, EncodecCompressor).  The reference cuts every clip
+ * into segments, and a segment depends on nothing outside itself (GroupNorm(1,C), the RMS scale, the LSTM state and the RVQ are all per
+ * sample), so the segments of ALL clips are rows of uniform batches: nothing is recomputed and no halo is needed.  Clip b's output equals,
+ * bit for bit, the one-clip call (B = 1) on that clip.
+ *   - a row is one (clip, segment) pair of the clip's segment list; its key is the segment's sample count for Encode and its code-frame
+ *     count for Decode;
+ *   - rows of equal key, from any clips, run through the unchanged launch sequences in batches of at most max_rows rows (keys in
+ *     descending order, rows of a key segment-major then by clip: for equal lengths this is the uniform call's grouping);
+ *   - models without segmentation (segment_length == 0: the 24 kHz preset) have one row per clip whose key is the clip's own length, so
+ *     only clips of EQUAL length share a batch -- the LSTM runs over the whole clip and no part of it stands for the clip;
+ *   - the activation arena is bounded by max_rows rows of one segment (without segmentation: of the longest clip), whatever B is.
+ * Packed layouts, clip after clip with no gap: clip b's PCM is [channels, lengths[b]] (Decode: [channels, decoded_lens[b]]); its codes
+ * are exactly the `codes` buffer of nc_encodec_encode(B = 1) on that clip (its frames [n_q, T'_f] end to end), its scales its
+ * n_frames[b] floats, its emb (nullable test hook) its frames [dimension, T'_f] end to end.  lengths[] is a HOST array of clip lengths
+ * in samples in both forms and both directions.  The *_dev forms take device pointers for the packed tensors and enqueue on the handle's
+ * stream; the plain forms take host pointers and are synchronous.  NC_EINVAL for B <= 0, a null pointer or a length <= 0; whatever the
+ * one-clip call would answer for any clip (a clip too short for the residual blocks, for instance) is the answer for the whole batch, names
+ * the clip index, and is decided before anything is launched. */
+typedef struct nc_encodec_ragged_plan {
+    int64_t n_rows;             /* (clip, segment) pairs */
+    int64_t n_keys;             /* distinct keys */
+    int64_t n_batches;          /* launch batches: sum over the keys of ceil(rows of the key / max_rows) */
+    int64_t max_rows;           /* rows per launch batch in force */
+    int64_t total_code_frames;  /* sum of T'_f over all rows */
+    int64_t total_codes;        /* int64 values of codes_packed: n_q * total_code_frames (n_q from the config's / handle's bandwidth) */
+    int64_t total_scales;       /* floats of scales_packed: n_rows */
+    int64_t total_samples;      /* floats per channel of the decoded pcm_packed: sum of decoded_lens[b] */
+} nc_encodec_ragged_plan;
+/* one row: segment `segment` of clip `clip` is row `row` of launch batch `batch`; it starts `offset` samples into the clip, holds
+ * `length` samples (decode != 0: the samples its frame decodes to) and `frames` code frames */
+typedef struct nc_encodec_ragged_row {
+    int32_t clip, segment, batch, row;
+    int64_t offset, length, frames;
+} nc_encodec_ragged_row;
+/* The planner on a config alone (host function: no handle, no device).  decode != 0: decode.  max_rows: 0 = the default, at most 4096.
+ * rows (nullable) receives the first `cap` rows in launch order. */
+NC_API nc_status nc_encodec_ragged_rows(const nc_encodec_config* cfg, int32_t decode, int32_t B, const int64_t* lengths, int32_t max_rows,
+                                        nc_encodec_ragged_plan* out, nc_encodec_ragged_row* rows, int64_t cap);
+/* Per-handle rows per launch batch; 0 selects the default, the best measured value (profiles/encodec_ragged_bench.json) */
+NC_API nc_status nc_encodec_set_ragged_rows(nc_codec* h, int32_t max_rows);
+/* what a ragged call on these clip lengths would do under the handle's setting and bandwidth (rows nullable, as above) */
+NC_API nc_status nc_encodec_ragged_rows_of(const nc_codec* h, int32_t decode, int32_t B, const int64_t* lengths, nc_encodec_ragged_plan* out,
+                                           nc_encodec_ragged_row* rows, int64_t cap);
+/* per clip (outputs nullable): segments, code frames summed over them, decoded samples -- the sums of nc_encodec_query on every clip */
+NC_API nc_status nc_encodec_ragged_query(const nc_codec* h, int32_t B, const int64_t* lengths, int32_t* n_frames, int64_t* code_frames,
+                                         int64_t* decoded_lens);
+NC_API nc_status nc_encodec_encode_ragged(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int64_t* codes_packed,
+                                          float* scales_packed, float* emb_packed);
+NC_API nc_status nc_encodec_encode_ragged_dev(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, int64_t* codes_packed,
+                                              float* scales_packed, float* emb_packed);
+NC_API nc_status nc_encodec_decode_ragged(nc_codec* h, const int64_t* codes_packed, const float* scales_packed, int32_t B,
+                                          const int64_t* lengths, int32_t n_q, float* pcm_packed);
+NC_API nc_status nc_encodec_decode_ragged_dev(nc_codec* h, const int64_t* codes_packed, const float* scales_packed, int32_t B,
+                                              const int64_t* lengths, int32_t n_q, float* pcm_packed);
 
 /* ------------------------------------------------------------------------------- code containers
  * Device-side bit packing of code tensors: the wire layout of the reference's BitPacker / BitUnpacker

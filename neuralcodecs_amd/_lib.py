@@ -78,6 +78,16 @@ class NcRaggedWindow(C.Structure):
                 ("keep_frames", C.c_int64)]
 
 
+class NcEncodecRaggedPlan(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_rows", "n_keys", "n_batches", "max_rows", "total_code_frames", "total_codes", "total_scales",
+                                         "total_samples")]
+
+
+class NcEncodecRaggedRow(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("segment", C.c_int32), ("batch", C.c_int32), ("row", C.c_int32), ("offset", C.c_int64),
+                ("length", C.c_int64), ("frames", C.c_int64)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
 
 _lib = None
@@ -154,6 +164,15 @@ SYMBOLS = [
     ("nc_encodec_encode_dev", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("nc_encodec_decode", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P]),
     ("nc_encodec_decode_dev", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P]),
+    ("nc_encodec_ragged_rows", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(NcEncodecRaggedPlan), _P,
+                                         C.c_int64]),
+    ("nc_encodec_set_ragged_rows", C.c_int, [_P, C.c_int32]),
+    ("nc_encodec_ragged_rows_of", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(NcEncodecRaggedPlan), _P, C.c_int64]),
+    ("nc_encodec_ragged_query", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_encodec_encode_ragged", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_encodec_encode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_encodec_decode_ragged", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("nc_encodec_decode_ragged_dev", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P]),
     ("nc_packed_bytes", C.c_int64, [C.c_int64, C.c_int32]),
     ("nc_pack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     ("nc_unpack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),

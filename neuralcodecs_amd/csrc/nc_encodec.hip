@@ -463,9 +463,10 @@ void EncodecModel::check_async_errors() {
 
 // ---- launch helpers --------------------------------------------------------------------------------
 float* EncodecModel::alloc(size_t n_floats) {
-    if (pool_i == pool.size()) pool.emplace_back(new DevBuf());
-    pool[pool_i]->reserve(n_floats * sizeof(float));
-    return pool[pool_i++]->as<float>();
+    const size_t idx = pool_i++ * (size_t)pool_lanes + (size_t)pool_lane;
+    while (pool.size() <= idx) pool.emplace_back(new DevBuf());
+    pool[idx]->reserve(n_floats * sizeof(float));
+    return pool[idx]->as<float>();
 }
 
 static ActView view_of(const EncodecModel::Act& a) {
@@ -966,20 +967,31 @@ float* EncodecModel::decode_batch(const int64_t* codes, int N, int nq, int64_t T
 template <class Body>
 void EncodecModel::for_each_group(const std::vector<Seg>& segs, int B, int64_t Seg::*key, Body&& body) {
     static const bool no_overlap = env_flag("NC_ENCODEC_NO_OVERLAP");
-    hipStream_t const main_stream = stream;
-    struct Restore {   // behind every group, and on an exception
-        EncodecModel& m;
-        hipStream_t s;
-        void operator()() const { m.stream = s; m.on_side_group = false; m.cur_group = 0; }
-        ~Restore() { (*this)(); }
-    } restore{*this, main_stream};
-    int n_groups = 0;
-    bool side_used[2] = {false, false};
-    NC_HIP(hipEventRecord(ev_fork, main_stream));
+    std::vector<std::pair<size_t, int>> runs;   // (first segment, segments) of every group
+    std::vector<int> lanes;
     for (size_t f = 0; f < segs.size();) {
         size_t g = f + 1;
         while (g < segs.size() && segs[g].*key == segs[f].*key && (int64_t)(g - f + 1) * B <= 4096) ++g;
-        const int side = (n_groups > 0 && !no_overlap) ? (n_groups - 1) % 2 : -1;   // groups after the first: side streams
+        lanes.push_back((!runs.empty() && !no_overlap) ? 1 + (int)((runs.size() - 1) % 2) : 0);   // groups after the first: side streams
+        runs.emplace_back(f, (int)(g - f));
+        f = g;
+    }
+    run_batches(lanes, false, [&](size_t i) { body(runs[i].first, runs[i].second); });
+}
+
+// The independent batches of one call (the segment groups of a uniform call, the pooled batches of a ragged one), each on its lane.
+void EncodecModel::run_batches(const std::vector<int>& lanes, bool lane_pools, const std::function<void(size_t)>& body) {
+    hipStream_t const main_stream = stream;
+    struct Restore {   // behind every batch, and on an exception
+        EncodecModel& m;
+        hipStream_t s;
+        void operator()() const { m.stream = s; m.on_side_group = false; m.cur_group = 0; m.pool_lane = 0; }
+        ~Restore() { (*this)(); }
+    } restore{*this, main_stream};
+    bool side_used[2] = {false, false};
+    NC_HIP(hipEventRecord(ev_fork, main_stream));
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const int side = lanes[i] - 1;
         on_side_group = side >= 0;
         cur_group = side + 1;
         if (side >= 0) {
@@ -987,10 +999,9 @@ void EncodecModel::for_each_group(const std::vector<Seg>& segs, int B, int64_t S
             if (!side_used[side]) NC_HIP(hipStreamWaitEvent(stream, ev_fork, 0));
             side_used[side] = true;
         }
-        ++n_groups;
-        body(f, (int)(g - f));
+        if (lane_pools) { pool_lane = cur_group; pool_i = 0; }
+        body(i);
         restore();
-        f = g;
     }
     for (int i = 0; i < 2; ++i)
         if (side_used[i]) {

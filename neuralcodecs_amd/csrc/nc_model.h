@@ -1,5 +1,6 @@
 // Engine objects behind the opaque nc_codec handle.
 #pragma once
+#include <functional>
 #include <memory>
 
 #include "nc_common.h"
@@ -297,6 +298,10 @@ struct EncodecModel : Codec {
 
     std::vector<std::unique_ptr<DevBuf>> pool;   // per-call intermediates, same allocation order every call (grow-only)
     size_t pool_i = 0;
+    // A ragged call runs many batches per stream: it splits the pool into one lane per stream (pool_lanes = 3, buffer i of lane l is
+    // pool[3 i + l]) and every batch starts over at the head of its lane, so the arena is bounded by the largest batch.  Batches of one
+    // lane are ordered by their stream.  Every other call runs with one lane: pool[pool_i], as ever.
+    int pool_lanes = 1, pool_lane = 0;
     LstmRuntime lstm{*this};                     // timeout word, ticket, second stream and events of the LSTM launches (nc_lstm.hip)
     // segment groups of one call are independent until the overlap-add: the first runs on the handle's stream, the others on side
     // streams (forked / joined with events), so the short tail segment of a clip hides behind the full-length batch
@@ -330,7 +335,14 @@ struct EncodecModel : Codec {
     }
     void encode_dev(const float* pcm, int B, int64_t T, int64_t* codes, float* scales, float* emb);
     void decode_dev(const int64_t* codes, const float* scales, int B, int64_t T, int nq, float* pcm);
-    float* alloc(size_t n_floats);   // the next buffer of the pool, grown to n_floats
+    // Ragged batches (nc_encodec_ragged.hip): the segments of B clips of unequal lengths pooled into uniform batches of at most
+    // ragged_rows rows (0 = default).  Device pointers, async on `stream`; lengths is a host array of clip lengths in samples.
+    int32_t ragged_rows = 0;
+    static constexpr int RAGGED_MAX_ROWS = 4096;   // = GN_MAX_SAMPLES: one arrival counter per row of a batch
+    DevBuf rg_frames;               // decoded frames of all batches of a ragged decode, alive until its one overlap-add launch
+    void encode_ragged_dev(const float* pcm, int B, const int64_t* lengths, int64_t* codes, float* scales, float* emb);
+    void decode_ragged_dev(const int64_t* codes, const float* scales, int B, const int64_t* lengths, int nq, float* pcm);
+    float* alloc(size_t n_floats);   // the next buffer of the pool (of the running batch's lane), grown to n_floats
     // Test hook (nc_op_encodec_trace).  A tap is every activation view the driver holds between launches, numbered in the order the
     // driver produces them: encoder = first conv | per stage: shortcut s, branch h, branch y, down-conv | LSTM | last conv; decoder =
     // first conv | LSTM | per stage: up-conv, s, h, y | last conv.  The LSTM tap is elu(x + lstm(x)).
@@ -348,6 +360,7 @@ struct EncodecModel : Codec {
     float* pad_act(const Act& a, const Act* b2, bool elu, int N, const Plan& pl);
     struct GnJob { bool on = false, fused = false, finished = false; int sub = 1, nrb = 0, ncb = 0; double* part = nullptr; float* stats = nullptr; };
     static constexpr int GN_MAX_SAMPLES = 4096;   // rows of a segment group (encode_dev caps a group at 4096)
+    static_assert(RAGGED_MAX_ROWS == GN_MAX_SAMPLES, "a ragged batch is a segment group");
     DevBuf gn_counters;                           // [3 groups][2][GN_MAX_SAMPLES] arrival counters of the in-launch GroupNorm finish (zero between launches; the second set: the
                                                   // branch output of the fused first pass of a residual block, two outputs finishing in one launch)
     int cur_group = 0;
@@ -366,6 +379,9 @@ struct EncodecModel : Codec {
     // body(first, G) per group of consecutive segments with equal `key` (at most 4096 rows): the first on the handle's stream, the others on side streams
     template <class Body>
     void for_each_group(const std::vector<Seg>& segs, int B, int64_t Seg::*key, Body&& body);
+    // body(i) per independent batch i, on lane lanes[i]: 0 = the handle's stream, 1 / 2 = the side streams (forked from and joined to the
+    // handle's stream with events; each lane has its own set of gn_counters).  lane_pools: every batch allocates from the head of its lane.
+    void run_batches(const std::vector<int>& lanes, bool lane_pools, const std::function<void(size_t)>& body);
     void ola_tables(const std::vector<int64_t>& flen, int64_t stride, int64_t total);
     char* ola_stage(const std::vector<const float*>& fp, const std::vector<int64_t>& flen);
     void encode_batch(const float* x, int N, int64_t L, int64_t Tz, int64_t* codes, float* scale_out, float* emb_out);

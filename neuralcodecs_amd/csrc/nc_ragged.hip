@@ -20,12 +20,11 @@
 #include <map>
 
 #include "nc_guard.h"
+#include "nc_ragged.h"
 
 namespace nc {
 
 namespace {
-
-struct RgSeg { int64_t src, dst, n, fill; };   // elements
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
 // Memory-bound, no LDS, no atomics.  blockIdx.y = descriptor, blockIdx.x strides over its run.  The destination side is written with
@@ -186,35 +185,13 @@ void snac_plan_report(const nc_snac_config& c, bool decode, int B, const int64_t
     report(P, SnacModel::arena_bytes(c, decode ? CK_DECODE : CK_ENCODE, P.maxw, P.W), codes, samples, out, windows, cap);
 }
 
-// ---- the tables of one call --------------------------------------------------------------------------------------------------------
-// Every descriptor of every launch of the call is written (and bounds-checked against the tensors it addresses) before anything is
-// launched; upload() then makes one pinned image and one asynchronous copy of them.
-struct Tables {
-    struct Launch { size_t first, count; int64_t longest; };
-    std::vector<RgSeg> segs;
-    std::vector<Launch> launches;
-    size_t open_at = 0;
-    int64_t src_elems = 0, dst_elems = 0, longest = 0;
+// ---- the tables of one call (nc_ragged.h) ------------------------------------------------------------------------------------------
+using Tables = RgTables;
 
-    void begin(int64_t src_n, int64_t dst_n) { open_at = segs.size(); src_elems = src_n; dst_elems = dst_n; longest = 0; }
-    void add(int64_t src, int64_t dst, int64_t n, int64_t fill = 0) {
-        if (n < 0 || fill < 0 || src < 0 || dst < 0 || src + n > src_elems || dst + n + fill > dst_elems)
-            fail(NC_ESTATE, "internal: ragged descriptor [%lld + %lld] -> [%lld + %lld] leaves its tensors (%lld, %lld elements)", (long long)src,
-                 (long long)n, (long long)dst, (long long)(n + fill), (long long)src_elems, (long long)dst_elems);
-        if (n + fill == 0) return;
-        segs.push_back({src, dst, n, fill});
-        longest = std::max(longest, n + fill);
-    }
-    size_t end() {   // -> index of the launch
-        launches.push_back({open_at, segs.size() - open_at, longest});
-        return launches.size() - 1;
-    }
-};
-
-void upload(Codec& m, const Tables& t) {
+const char* upload(Codec& m, const Tables& t) {
     Codec::RaggedTables& r = m.rg_tab;
-    const size_t bytes = t.segs.size() * sizeof(RgSeg);
-    if (!bytes) return;
+    const size_t seg_bytes = t.segs.size() * sizeof(RgSeg), bytes = seg_bytes + t.extra.size();
+    if (!bytes) return nullptr;
     if (!r.ev) NC_HIP(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
     if (r.ev_used) NC_HIP(hipEventSynchronize(r.ev));   // the previous call's copy has read the pinned image
     if (bytes > r.pin_cap) {
@@ -224,11 +201,13 @@ void upload(Codec& m, const Tables& t) {
         NC_HIP(hipHostMalloc(&r.pin, want, hipHostMallocDefault));
         r.pin_cap = want;
     }
-    std::memcpy(r.pin, t.segs.data(), bytes);
+    if (seg_bytes) std::memcpy(r.pin, t.segs.data(), seg_bytes);
+    if (!t.extra.empty()) std::memcpy(static_cast<char*>(r.pin) + seg_bytes, t.extra.data(), t.extra.size());
     r.dev.reserve(bytes);
     NC_HIP(hipMemcpyAsync(r.dev.p, r.pin, bytes, hipMemcpyHostToDevice, m.stream));
     NC_HIP(hipEventRecord(r.ev, m.stream));
     r.ev_used = true;
+    return t.extra.empty() ? nullptr : r.dev.as<char>() + seg_bytes;
 }
 
 template <class T>
@@ -534,6 +513,10 @@ void host_call(Codec& m, F&& f) {
 
 }  // namespace
 
+const char* rg_upload(Codec& m, const RgTables& t) { return upload(m, t); }
+void rg_copy_f32(Codec& m, const RgTables& t, size_t which, const float* src, float* dst) { launch<float>(m, t, which, ragged_gather_f32, src, dst); }
+void rg_copy_i64(Codec& m, const RgTables& t, size_t which, const int64_t* src, int64_t* dst) { launch<int64_t>(m, t, which, ragged_gather_i64, src, dst); }
+
 Codec::RaggedTables::~RaggedTables() {
     if (ev) (void)hipEventDestroy(ev);
     if (pin) (void)hipHostFree(pin);
@@ -565,7 +548,7 @@ nc_status nc_snac_ragged_windows(const nc_snac_config* cfg, int32_t decode, int3
 nc_status nc_codec_set_ragged_window(nc_codec* h, int64_t kept_frames, int32_t max_windows) {
     return guard([&] {
         Codec& c = codec_of(h);
-        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles have no ragged calls: 48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context");
+        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles are not cut into windows (48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context): their ragged calls pool segments, see nc_encodec_set_ragged_rows");
         if (kept_frames < 0 || max_windows < 0) fail(NC_EINVAL, "kept_frames and max_windows must not be negative (0 = default)");
         c.ragged_kept = kept_frames;
         c.ragged_max_windows = max_windows;
@@ -575,7 +558,7 @@ nc_status nc_codec_set_ragged_window(nc_codec* h, int64_t kept_frames, int32_t m
 nc_status nc_codec_ragged_plan(const nc_codec* h, int32_t decode, int32_t B, const int64_t* frames, nc_ragged_plan* out) {
     return guard([&] {
         Codec& c = codec_of(h);
-        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles have no ragged calls");
+        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles have no window plan: see nc_encodec_ragged_rows");
         if (h->kind == DacModel::kKind) dac_plan_report(as<DacModel>(h).cfg, decode != 0, B, frames, c.ragged_kept, c.ragged_max_windows, out, nullptr, 0);
         else snac_plan_report(as<SnacModel>(h).cfg, decode != 0, B, frames, c.ragged_kept, c.ragged_max_windows, out, nullptr, 0);
     });

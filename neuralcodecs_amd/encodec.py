@@ -39,6 +39,46 @@ class EncodedFrame:
     scale: Optional[object] = None
 
 
+def _c_config(config: EncodecConfig) -> "_lib.NcEncodecConfig":
+    """nc_encodec_config of an EncodecConfig (the derived fields as Encodec.cs:70-84 computes them)."""
+    hop = config.hop_length
+    frame_rate = int(math.ceil(config.sampling_rate / float(hop)))
+    seg = None if config.segment_seconds is None else int(config.segment_seconds * config.sampling_rate)
+    stride = None if seg is None else max(1, int((1 - config.overlap) * seg))
+    c = _lib.NcEncodecConfig()
+    c.sample_rate, c.channels, c.dimension, c.n_filters = config.sampling_rate, config.channels, config.dimension, config.n_filters
+    c.n_ratios = len(config.ratios)
+    for i, r in enumerate(config.ratios):
+        c.ratios[i] = r
+    c.lstm_layers, c.compress, c.kernel_size = config.lstm_layers, config.compress, config.kernel_size
+    c.last_kernel_size, c.residual_kernel_size = config.last_kernel_size, config.residual_kernel_size
+    c.time_group_norm = int(config.norm == "time_group_norm")
+    c.causal, c.normalize = int(config.causal), int(config.normalize)
+    c.segment_length, c.segment_stride = seg or 0, stride or 0
+    c.codebook_size, c.frame_rate, c.bandwidth = config.codebook_size, frame_rate, config.bandwidth
+    c.n_codebooks = int(1000 * max(config.target_bandwidths) / (math.ceil(config.sampling_rate / hop) * 10))
+    return c
+
+
+def _ragged_rows(call, lengths, decode: bool):
+    """(plan dict, list of row dicts in launch order) of one of the two planner entry points; call(n, lens, plan, rows, cap)"""
+    lens = _lib.i64_array(lengths)
+    p = _lib.NcEncodecRaggedPlan()
+    _lib.check(call(len(lens), lens, C.byref(p), None, 0))
+    rows = (_lib.NcEncodecRaggedRow * max(1, int(p.n_rows)))()
+    _lib.check(call(len(lens), lens, C.byref(p), rows, int(p.n_rows)))
+    plan = {k: int(getattr(p, k)) for k, _ in _lib.NcEncodecRaggedPlan._fields_}
+    return plan, [{k: int(getattr(rows[i], k)) for k, _ in _lib.NcEncodecRaggedRow._fields_} for i in range(int(p.n_rows))]
+
+
+def encodec_ragged_rows(config: EncodecConfig, lengths, decode: bool = False, max_rows: int = 0):
+    """nc_encodec_ragged_rows: how a ragged call on clips of these lengths (samples) pools their segments into batches -- from a
+    config alone, no device needed."""
+    c = _c_config(config)
+    return _ragged_rows(lambda n, lens, p, rows, cap: _lib.lib().nc_encodec_ragged_rows(C.byref(c), 1 if decode else 0, n, lens, int(max_rows), p, rows, cap),
+                        lengths, decode)
+
+
 class Encodec(_lib.ProfileMixin):
     def __init__(self, config: Optional[EncodecConfig] = None, device_index: int = 0):
         if config is None:
@@ -53,17 +93,7 @@ class Encodec(_lib.ProfileMixin):
         self.num_codebooks = int(1000 * max(config.target_bandwidths) / (math.ceil(config.sampling_rate / hop) * 10))   # Encodec.cs:70-71
         self.segment_length = None if config.segment_seconds is None else int(config.segment_seconds * config.sampling_rate)
         self.segment_stride = None if self.segment_length is None else max(1, int((1 - config.overlap) * self.segment_length))
-        c = _lib.NcEncodecConfig()
-        c.sample_rate, c.channels, c.dimension, c.n_filters = config.sampling_rate, config.channels, config.dimension, config.n_filters
-        c.n_ratios = len(config.ratios)
-        for i, r in enumerate(config.ratios):
-            c.ratios[i] = r
-        c.lstm_layers, c.compress, c.kernel_size = config.lstm_layers, config.compress, config.kernel_size
-        c.last_kernel_size, c.residual_kernel_size = config.last_kernel_size, config.residual_kernel_size
-        c.time_group_norm = int(config.norm == "time_group_norm")
-        c.causal, c.normalize = int(config.causal), int(config.normalize)
-        c.segment_length, c.segment_stride = self.segment_length or 0, self.segment_stride or 0
-        c.codebook_size, c.n_codebooks, c.frame_rate, c.bandwidth = config.codebook_size, self.num_codebooks, self.frame_rate, config.bandwidth
+        c = _c_config(config)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().nc_encodec_create(C.byref(c), device_index, C.byref(self._h)))
 
@@ -242,3 +272,111 @@ class Encodec(_lib.ProfileMixin):
     def forward(self, x):
         frames = self.encode(x)
         return self.decode(frames, x.shape[-1])[..., : x.shape[-1]]                                    # Encodec.cs:290
+
+    # ---- ragged batches (clips of unequal lengths in one call) ------------------------------------
+    def set_ragged_rows(self, max_rows: int = 0) -> None:
+        """nc_encodec_set_ragged_rows: rows (segments) per launch batch of the ragged calls (0 = default, at most 4096)."""
+        _lib.check(_lib.lib().nc_encodec_set_ragged_rows(self._h, int(max_rows)))
+
+    def ragged_rows(self, lengths, decode: bool = False):
+        """nc_encodec_ragged_rows_of: (plan, rows) of a ragged call on clips of these lengths under the handle's setting and bandwidth."""
+        return _ragged_rows(lambda n, lens, p, rows, cap: _lib.lib().nc_encodec_ragged_rows_of(self._h, 1 if decode else 0, n, lens, p, rows, cap),
+                            lengths, decode)
+
+    def ragged_query(self, lengths):
+        """nc_encodec_ragged_query: per clip (segments, code frames summed over them, decoded samples)."""
+        lens = _lib.i64_array(lengths)
+        n = max(1, len(lens))
+        nf, fr, dl = (C.c_int32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+        _lib.check(_lib.lib().nc_encodec_ragged_query(self._h, len(lens), lens, nf, fr, dl))
+        return [int(nf[i]) for i in range(len(lens))], [int(fr[i]) for i in range(len(lens))], [int(dl[i]) for i in range(len(lens))]
+
+    def encode_ragged(self, clips, return_emb: bool = False):
+        """nc_encodec_encode_ragged[_dev]: a list of [C, T_b] arrays / device tensors -> per clip the List[EncodedFrame] (leading batch
+        of 1) that encode(clip[None]) returns, bit for bit; the segments of all clips run pooled in uniform batches."""
+        if clips is None or len(clips) == 0:
+            raise ValueError("the list of clips must not be empty")
+        for c in clips:
+            if c is None or c.ndim != 2 or c.shape[0] != self.config.channels:
+                raise ValueError(f"every clip must be [{self.config.channels}, T]")
+        B, D = len(clips), self.config.dimension
+        lens = [int(c.shape[1]) for c in clips]
+        larr = _lib.i64_array(lens)
+        nfs, frs, _ = self.ragged_query(lens)
+        nq = self.query(1)[1]
+        n_codes, n_sc, n_emb = nq * sum(frs), sum(nfs), D * sum(frs)
+        if _is_torch(clips[0]):
+            import torch
+            flat = torch.cat([c.reshape(-1).to(torch.float32) for c in clips]).contiguous()
+            codes = torch.empty((max(1, n_codes),), dtype=torch.int64, device=flat.device)
+            scales = torch.empty((max(1, n_sc),), dtype=torch.float32, device=flat.device)
+            emb = torch.empty((max(1, n_emb),), dtype=torch.float32, device=flat.device) if return_emb else None
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_encodec_encode_ragged_dev(self._h, flat.data_ptr(), B, larr, codes.data_ptr(), scales.data_ptr(),
+                                                               emb.data_ptr() if emb is not None else None))
+        else:
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1) for c in clips]))
+            codes = np.empty((max(1, n_codes),), np.int64)
+            scales = np.empty((max(1, n_sc),), np.float32)
+            emb = np.empty((max(1, n_emb),), np.float32) if return_emb else None
+            _lib.check(_lib.lib().nc_encodec_encode_ragged(self._h, flat.ctypes.data, B, larr, codes.ctypes.data, scales.ctypes.data,
+                                                           emb.ctypes.data if emb is not None else None))
+        out, embs, o, osc, oe = [], [], 0, 0, 0
+        for T in lens:
+            frames, es = [], []
+            for f, Tf in enumerate(self.query(T)[2]):
+                frames.append(EncodedFrame(codes[o:o + nq * Tf].reshape(1, nq, Tf), scales[osc + f:osc + f + 1].reshape(1, 1) if self.config.normalize else None))
+                o += nq * Tf
+                if return_emb:
+                    es.append(emb[oe:oe + D * Tf].reshape(1, D, Tf))
+                    oe += D * Tf
+            osc += len(frames)
+            out.append(frames)
+            embs.append(es)
+        return (out, embs) if return_emb else out
+
+    def decode_ragged(self, frame_lists, lengths=None):
+        """nc_encodec_decode_ragged[_dev]: per clip a List[EncodedFrame] with a leading batch of 1 -> a list of [C, Ld_b], each the
+        decode() of that clip alone, bit for bit.  lengths: the clips' sample counts (default: inferred from the frames as decode() does)."""
+        if frame_lists is None or len(frame_lists) == 0:
+            raise ValueError("the list of clips must not be empty")
+        for fl in frame_lists:
+            if fl is None or len(fl) == 0:
+                raise ValueError("No frames provided to decode")
+            if self.segment_length is None and len(fl) != 1:
+                raise ValueError("Expected single frame when no segmentation is used")
+            for f in fl:
+                if f.codes is None or f.codes.ndim != 3 or f.codes.shape[0] != 1:
+                    raise ValueError("Invalid frame codes in Encodec Decode: every frame must be [1, n_q, T']")
+        B, nq = len(frame_lists), int(frame_lists[0][0].codes.shape[1])
+        if any(int(f.codes.shape[1]) != nq for fl in frame_lists for f in fl):
+            raise ValueError("every frame must carry the same number of codebooks")
+        lens = [int(t) for t in lengths] if lengths is not None else [self._infer_length(fl) for fl in frame_lists]
+        if len(lens) != B:
+            raise ValueError("one length per clip")
+        for b, (fl, T) in enumerate(zip(frame_lists, lens)):
+            nf, _, want, _ = self.query(T)
+            if nf != len(fl) or [int(f.codes.shape[-1]) for f in fl] != want:
+                raise ValueError(f"clip {b}: frames do not match the segment layout of a {T}-sample clip: expected {want}")
+        larr = _lib.i64_array(lens)
+        _, _, dls = self.ragged_query(lens)
+        Cn = self.config.channels
+        if _is_torch(frame_lists[0][0].codes):
+            import torch
+            codes = torch.cat([f.codes.reshape(-1).to(torch.int64) for fl in frame_lists for f in fl]).contiguous()
+            scales = None
+            if self.config.normalize:
+                scales = torch.cat([f.scale.reshape(-1).to(torch.float32) for fl in frame_lists for f in fl]).contiguous()
+            out = torch.empty((max(1, Cn * sum(dls)),), dtype=torch.float32, device=codes.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_encodec_decode_ragged_dev(self._h, codes.data_ptr(), scales.data_ptr() if scales is not None else None,
+                                                               B, larr, nq, out.data_ptr()))
+        else:
+            codes = np.ascontiguousarray(np.concatenate([np.asarray(f.codes, np.int64).reshape(-1) for fl in frame_lists for f in fl]))
+            scales = None
+            if self.config.normalize:
+                scales = np.ascontiguousarray(np.concatenate([np.asarray(f.scale, np.float32).reshape(-1) for fl in frame_lists for f in fl]))
+            out = np.empty((max(1, Cn * sum(dls)),), np.float32)
+            _lib.check(_lib.lib().nc_encodec_decode_ragged(self._h, codes.ctypes.data, scales.ctypes.data if scales is not None else None,
+                                                           B, larr, nq, out.ctypes.data))
+        return [p.reshape(Cn, -1) for p in _lib.split_packed(out, [Cn * d for d in dls])]
