@@ -83,12 +83,36 @@ public sealed unsafe class DACNative : INeuralCodec
         return z;
     }
 
+    /// <summary>latents [B,cLat,T'] -> (zQ [B,latent,T'], projected [B,nQ*codebookDim,T'], codes [B,nQ,T']) with
+    /// nQ = min(NumCodebooks, cLat / CodebookDim); Modules/DAC/ResidualVectorQuantizer.cs:243-300 on host arrays.</summary>
+    public (float[] z, float[] projected, long[] codes, int nQ) FromLatentsHost(float[] latents, int B, int cLat, long frames)
+    {
+        ArgumentNullException.ThrowIfNull(latents);
+        int nq = Math.Max(1, Math.Min(_config.NumCodebooks, cLat / _config.CodebookDim));   // (cLat < CodebookDim: NC_EINVAL -> ArgumentException)
+        var z = new float[(long)B * _latentDim * frames];
+        var proj = new float[(long)B * nq * _config.CodebookDim * frames];
+        var codes = new long[(long)B * nq * frames];
+        fixed (float* pl = latents, pz = z, pp = proj) fixed (long* pc = codes)
+            NcMi355x.Check(NcMi355x.nc_dac_from_latents(_h, pl, B, cLat, frames, pz, pp, pc));
+        return (z, proj, codes, nq);
+    }
+
     // ---- the reference's members, signature for signature ---------------------------------------------------------------------------
     public Tensor FromCodes(Tensor codes)                                           // Models/DAC.cs:101-106: codes [B,nQ,T'] int64
     {
         int B = (int)codes.shape[0], nQ = (int)codes.shape[1];
         long frames = codes.shape[2];
         return NcTensor.From(FromCodesHost(NcTensor.Longs(codes), B, nQ, frames), B, _latentDim, frames);
+    }
+
+    /// <summary>The quantizer's FromLatents (the reference reaches it as Quantizer.FromLatents): latents [B,C,T'] float32.</summary>
+    public (Tensor zQ, Tensor projected, Tensor codes) FromLatents(Tensor latents)  // Modules/DAC/ResidualVectorQuantizer.cs:243-300
+    {
+        int B = (int)latents.shape[0], cLat = (int)latents.shape[1];
+        long frames = latents.shape[2];
+        var (z, proj, codes, nq) = FromLatentsHost(NcTensor.Floats(latents), B, cLat, frames);
+        return (NcTensor.From(z, B, _latentDim, frames), NcTensor.From(proj, B, (long)nq * _config.CodebookDim, frames),
+                NcTensor.From(codes, B, nq, frames));
     }
 
     public (Tensor z, Tensor codes, Tensor latents, Tensor commitmentLoss, Tensor codebookLoss)

@@ -132,7 +132,28 @@ NC_API nc_status nc_dac_decode_dev(nc_codec* h, const float* z, int32_t B, int64
 NC_API nc_status nc_dac_from_codes(nc_codec* h, const int64_t* codes, int32_t B, int32_t n_q, int64_t frames, float* z);
 NC_API nc_status nc_dac_from_codes_dev(nc_codec* h, const int64_t* codes, int32_t B, int32_t n_q, int64_t frames, float* z);
 
-/* replaces: Dia.Decode(Tensor audioCodes[T, n_q])  Models/Dia.cs:973-981  (FromCodes(codes.unsqueeze(0).transpose(1, 2)) -> Decode) and
+/* replaces: ResidualVectorQuantizer.FromLatents(Tensor latents[B,C_lat,T']) -> (zQ, projected, codes)
+ *           Modules/DAC/ResidualVectorQuantizer.cs:243-300 over VectorQuantizer.DecodeLatents (VectorQuantizer.cs:99-125)
+ * The way back in for the continuous `latents` that nc_dac_encode hands out: every codebook slice of D = codebook_dim channels is
+ * looked up in its codebook (nearest code on the un-normalised vectors; lowest index on ties, a NaN distance wins, the first one --
+ * the rules of the encoder's quantizer, so latents taken from nc_dac_encode return its codes unchanged), the raw codebook rows are
+ * out-projected and summed as nc_dac_from_codes sums them (z is bit-identical to nc_dac_from_codes on the returned codes).
+ *   latents    [B,C_lat,T'] float32; n_q = min(n_codebooks, C_lat / D) codebooks are used (those whose cumulative dimension fits);
+ *              channels beyond n_q*D are ignored, the row stride stays C_lat
+ *   z          [B,latent,T'] float32       (nullable)
+ *   projected  [B,n_q*D,T'] float32        (nullable; the raw codebook rows, the reference's cat(projected))
+ *   codes      [B,n_q,T'] int64            (nullable)
+ * NC_EINVAL, before anything is launched: latents NULL; all three outputs NULL; B <= 0; frames <= 0; frames > 2^30; C_lat < D (the
+ * reference would return a one-element zero tensor there, which no caller can use: a deliberate deviation).  NC_ESTATE without weights.
+ * The operation is pointwise in time (no halo) and addresses batch and frame offsets in 64 bits, so no size is refused; the
+ * out-projection of rows too long for one convolution launch is cut as nc_dac_from_codes cuts it (nc_codec_set_chunk_frames applies).
+ * Clips of unequal lengths need no entry point of their own: packed end to end along T' they are one B = 1 call. */
+NC_API nc_status nc_dac_from_latents(nc_codec* h, const float* latents, int32_t B, int32_t C_lat, int64_t frames, float* z,
+                                     float* projected, int64_t* codes);
+NC_API nc_status nc_dac_from_latents_dev(nc_codec* h, const float* latents, int32_t B, int32_t C_lat, int64_t frames, float* z,
+                                         float* projected, int64_t* codes);
+
+/* replaces: Dia.Decode(Tensor audioCodes[T, n_q])  Models/Dia.cs:973-981 (FromCodes(codes.unsqueeze(0).transpose(1, 2)) -> Decode) and
  *           AudioUtils.Decode(DAC, codes)           Modules/Dia/AudioUtils.cs:189-199, batched: codes_tq int64 [B, T', n_q] (Dia's layout)
  *           -> pcm [B, 1, L] (L as for nc_dac_decode).  The transpose to DAC's [B, n_q, T'] is a device kernel.
  * replaces: Dia.Encode(Tensor audio[1, T])          Models/Dia.cs:989-1002 (Encode -> squeeze(0).transpose(0, 1)), batched:

@@ -243,6 +243,41 @@ nc_status nc_dac_from_codes(nc_codec* h, const int64_t* codes, int32_t B, int32_
     });
 }
 
+nc_status nc_dac_from_latents_dev(nc_codec* h, const float* latents, int32_t B, int32_t C_lat, int64_t frames, float* z, float* projected,
+                                  int64_t* codes) {
+    return guard([&] { as<DacModel>(h).from_latents_dev(latents, B, C_lat, frames, z, projected, codes); });
+}
+
+// one upload, the device-pointer sequence on the staged arrays (which refuses what is to be refused before anything is queued), one
+// download per output asked for
+nc_status nc_dac_from_latents(nc_codec* h, const float* latents, int32_t B, int32_t C_lat, int64_t frames, float* z, float* projected,
+                              int64_t* codes) {
+    return guard([&] {
+        DacModel& m = as<DacModel>(h);
+        const int D = m.cfg.codebook_dim;
+        if (!latents) fail(NC_EINVAL, "latents must not be null");
+        if (!z && !projected && !codes) fail(NC_EINVAL, "z, projected and codes are all null: nothing to compute");
+        if (B <= 0 || frames <= 0 || frames > ((int64_t)1 << 30)) fail(NC_EINVAL, "B and frames must be positive (at most 2^30 frames)");
+        if (C_lat < D) fail(NC_EINVAL, "latents of %d channels hold no codebook of dimension %d", C_lat, D);
+        if (!m.loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
+        on_own_stream(m, [&] {
+            const int n_q = std::min(m.cfg.n_codebooks, C_lat / D);
+            const size_t n_in = (size_t)B * C_lat * frames * 4, n_z = (size_t)B * m.latent * frames * 4, n_pj = (size_t)B * n_q * D * frames * 4,
+                         n_codes = (size_t)B * n_q * frames * 8;
+            m.ck_in.reserve(n_in);
+            if (z) m.ck_a.reserve(n_z);
+            if (projected) m.ck_b.reserve(n_pj);
+            if (codes) m.ck_codes.reserve(n_codes);
+            h2d(m.ck_in.p, latents, n_in, m.stream);
+            m.from_latents_dev(m.ck_in.as<float>(), B, C_lat, frames, z ? m.ck_a.as<float>() : nullptr, projected ? m.ck_b.as<float>() : nullptr,
+                               codes ? m.ck_codes.as<int64_t>() : nullptr);
+            if (z) d2h(z, m.ck_a.p, n_z, m.stream);
+            if (projected) d2h(projected, m.ck_b.p, n_pj, m.stream);
+            if (codes) d2h(codes, m.ck_codes.p, n_codes, m.stream);
+        });
+    });
+}
+
 nc_status nc_dac_decode_code_matrix_dev(nc_codec* h, const int64_t* codes_tq, int32_t B, int64_t frames, int32_t n_q, float* pcm) {
     return guard([&] { as<DacModel>(h).decode(false, nullptr, codes_tq, n_q, B, frames, pcm); });
 }

@@ -172,6 +172,9 @@ struct DacModel : Codec {
     void encode_dev(const float* pcm, int B, int64_t T, int sample_rate, int n_q, int64_t* codes, float* z, float* latents);
     void decode_dev(const float* z, int B, int64_t frames, float* pcm);
     void from_codes_dev(const int64_t* codes, int B, int n_q, int64_t frames, float* z);
+    // nc_dac_latents.hip: latents [B,C_lat,frames] -> z [B,latent,frames], projected [B,n_q*D,frames], codes [B,n_q,frames] with
+    // n_q = min(n_codebooks, C_lat / D); any output may be null, not all three
+    void from_latents_dev(const float* latents, int B, int C_lat, int64_t frames, float* z, float* projected, int64_t* codes);
     void decode_code_matrix_dev(const int64_t* codes_tq, int B, int64_t frames, int n_q, float* pcm);
     void encode_code_matrix_dev(const float* pcm, int B, int64_t T, int sample_rate, int64_t* codes_tq);
     // The operations of the C ABI (nc_chunk.hip), async on `stream`.  `host`: the caller's arrays are host pointers.  Each plans the

@@ -9,6 +9,7 @@ Same members, argument meaning and error behaviour as NeuralCodecs.Torch/Models/
     encode_array(float[]) -> float[] (the zQ latents, D12)                                            DAC.cs:205-224
     decode(z) / decode_array(float[])                                                                 DAC.cs:231-253
     from_codes(codes)                                                                                 DAC.cs:101-106
+    from_latents(latents) -> (z_q, projected, codes)                  Modules/DAC/ResidualVectorQuantizer.cs:243-300
     forward(audio) -> dict                                                                            DAC.cs:288-303
     dispose()                                                                                         DAC.cs:329-338
 
@@ -210,6 +211,33 @@ class DAC(_lib.ProfileMixin):
         z = np.empty((B, self.latent_dim, Tz), np.float32)
         _lib.check(_lib.lib().nc_dac_from_codes(self._h, c.ctypes.data, B, nq, Tz, z.ctypes.data))
         return z
+
+    def from_latents(self, latents):
+        """ResidualVectorQuantizer.FromLatents (Modules/DAC/ResidualVectorQuantizer.cs:243-300): latents [B, C, T'] (the `latents` of
+        encode(), or any continuous vectors in that space) -> (z_q [B, latent, T'], projected [B, n_q*D, T'], codes [B, n_q, T']) with
+        n_q = min(n_codebooks, C // D).  Clips of unequal lengths: concatenate them along T' into one B = 1 call."""
+        if latents is None:
+            raise ValueError("latents must not be null")
+        if latents.ndim != 3:
+            raise ValueError("latents must be [B,C,T']")
+        B, Cl, Tz = (int(v) for v in latents.shape)
+        D = self.config.codebook_dim
+        nq = max(1, min(self.config.n_codebooks, Cl // D))          # (Cl < D: the engine refuses before it writes anything)
+        if _is_torch(latents):
+            import torch
+            x = latents.contiguous().to(torch.float32)
+            z = torch.empty((B, self.latent_dim, Tz), dtype=torch.float32, device=x.device)
+            proj = torch.empty((B, nq * D, Tz), dtype=torch.float32, device=x.device)
+            codes = torch.empty((B, nq, Tz), dtype=torch.int64, device=x.device)
+            self._bind_torch_stream()
+            _lib.check(_lib.lib().nc_dac_from_latents_dev(self._h, x.data_ptr(), B, Cl, Tz, z.data_ptr(), proj.data_ptr(), codes.data_ptr()))
+            return z, proj, codes
+        x = np.ascontiguousarray(latents, dtype=np.float32)
+        z = np.empty((B, self.latent_dim, Tz), np.float32)
+        proj = np.empty((B, nq * D, Tz), np.float32)
+        codes = np.empty((B, nq, Tz), np.int64)
+        _lib.check(_lib.lib().nc_dac_from_latents(self._h, x.ctypes.data, B, Cl, Tz, z.ctypes.data, proj.ctypes.data, codes.ctypes.data))
+        return z, proj, codes
 
     # ---- ragged batches (clips of unequal lengths in one call) ------------------------------------
     @staticmethod
