@@ -633,6 +633,26 @@ NC_API nc_status nc_op_vq_argmin(int device_index, const float* z_e, int32_t B, 
  * leaves LDS).  form 0: one launch per stage; form 1: the all-stages matrix-core kernel (D == 128 and N = 512 or 1024, else NC_EUNSUPPORTED). */
 NC_API nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, int32_t D, int64_t T, const float* codebooks,
                                   int32_t n_q, int32_t N, int32_t form, int64_t* codes, float* residual_out);
+/* The DAC quantizer (ResidualVectorQuantizer.cs:54-103 over VectorQuantizer.cs:67-125) on residual [B,L,T] through the routine the DAC
+ * model's encode calls, on stage images built by the loader's routines from FOLDED dense weights: w_in [n_q,D,L], b_in [n_q,D] (nullable),
+ * codebooks [n_q,N,D], w_out [n_q,L,D], b_out [n_q,L] (nullable) -> codes [B,n_q,T], zq [B,L,T], latents [B,n_q*D,T].  form 0: the launches
+ * per stage (skinny in-projection, argmin, 1x1 convolution with the zq += q ; residual -= q epilogue); form 1: all stages in one launch,
+ * NC_EUNSUPPORTED with nothing built or launched where that kernel has no instance (it wants D == 8, L in {256, 512, 768, 1024},
+ * N % 64 == 0, N <= 1024).  form overrides NC_DAC_RVQ_STAGEWISE.  n_q <= 0: NC_EINVAL.  On an error the outputs are untouched. */
+NC_API nc_status nc_op_dac_rvq(int device_index, const float* residual, int32_t B, int32_t L, int64_t T, int32_t n_q, int32_t N, int32_t D,
+                               const float* w_in, const float* b_in, const float* codebooks, const float* w_out, const float* b_out,
+                               int32_t form, int64_t* codes, float* zq, float* latents);
+/* SNAC's quantizer update (ResidualVectorQuantizer.cs of SNAC: repeat_interleave of the stage's output at stride s): with q [rows,T/s],
+ * zq [rows,T] = (first ? 0 : zq) + repeat(q, s) and, residual [rows,T] not null, residual -= repeat(q, s); both in place.  T % s == 0. */
+NC_API nc_status nc_op_rvq_update(int device_index, const float* q, float* zq, float* residual, int64_t rows, int64_t T, int32_t s,
+                                  int32_t first);
+/* Code gather (VectorQuantizer.cs:135-142: Embedding + transpose): out[b,d,t] = codebook[code(b,t)][d] with code(b,t) =
+ * codes[codes_offset + b * codes_bstride + t], codes a flat buffer of which the words up to codes_offset + (B-1) * codes_bstride + T are
+ * read (SNAC keeps the levels of a clip side by side: codes_bstride > T).  A code outside [0, N) is CLAMPED to 0 or N - 1: that is the
+ * engine's behaviour where the reference's Embedding would throw.  out points at [B,D,T] inside a buffer with out_guard floats in front
+ * of it and out_guard behind; the whole buffer travels to the device and back, so a write outside [B,D,T] shows in the guards. */
+NC_API nc_status nc_op_vq_gather(int device_index, const float* codebook, int32_t N, int32_t D, const int64_t* codes, int64_t codes_offset,
+                                 int64_t codes_bstride, int32_t B, int64_t T, float* out, int64_t out_guard);
 /* One activation of a loaded Encodec handle's SEANet stacks, as the driver holds it between launches (a "tap").  decoder == 0: the encoder
  * on x [B,channels,L] (no RMS normalisation); decoder != 0: the decoder on x [B,dimension,L].  The launches up to the tap are the ones
  * nc_encodec_encode / nc_encodec_decode make for a group of B rows.  Taps in driver order -- encoder: first conv | per stage: shortcut s,

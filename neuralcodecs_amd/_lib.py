@@ -213,6 +213,10 @@ SYMBOLS = [
                                  C.c_int32, C.POINTER(C.c_double)]),
     ("nc_op_vq_argmin", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P]),
     ("nc_op_euclid_rvq", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("nc_op_dac_rvq", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
+                                _P, _P, _P]),
+    ("nc_op_rvq_update", C.c_int, [C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    ("nc_op_vq_gather", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _P, C.c_int64]),
     ("nc_op_encodec_trace", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nc_op_fold_weight_norm", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),

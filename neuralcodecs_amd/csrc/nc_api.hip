@@ -725,6 +725,75 @@ nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, i
     });
 }
 
+nc_status nc_op_dac_rvq(int device_index, const float* residual, int32_t B, int32_t L, int64_t T, int32_t n_q, int32_t N, int32_t D,
+                        const float* w_in, const float* b_in, const float* codebooks, const float* w_out, const float* b_out, int32_t form,
+                        int64_t* codes, float* zq, float* latents) {
+    return guard([&] {
+        if (!residual || !w_in || !codebooks || !w_out || !codes || !zq || !latents) fail(NC_EINVAL, "null argument");
+        if (B <= 0 || L <= 0 || T <= 0 || T > ((int64_t)1 << 30) || n_q <= 0 || n_q > 64 || N <= 0 || D <= 0 || form < 0 || form > 1 ||
+            D > (1 << 20) || L > (1 << 20) || (int64_t)B * std::max<int64_t>(L, (int64_t)n_q * D) > ((int64_t)1 << 31) / T)
+            fail(NC_EINVAL, "bad arguments");
+        if (form == 1 && !dac_rvq_fused_admits(n_q, L, D, N))   // before anything is built or launched
+            fail(NC_EUNSUPPORTED, "no one-launch DAC quantizer for latent %d, codebook %d x %d", L, N, D);
+        op_set_device(device_index);
+        DacRvq rvq;
+        for (int i = 0; i < n_q; ++i)
+            rvq.add_stage(w_in + (size_t)i * D * L, b_in ? b_in + (size_t)i * D : nullptr, w_out + (size_t)i * L * D,
+                          b_out ? b_out + (size_t)i * L : nullptr, codebooks + (size_t)i * N * D, L, D, N);
+        rvq.upload_stages();
+        const size_t nr = (size_t)B * L * T, nl = (size_t)B * n_q * D * T, nc = (size_t)B * n_q * T;
+        DevBuf dr, dz, dl, dc, ds;
+        op_upload(dr, residual, nr);
+        dz.reserve(nr * 4); dl.reserve(nl * 4); dc.reserve(nc * 8); ds.reserve((size_t)B * D * T * 4);
+        NC_HIP(hipMemset(dz.p, 0xFF, nr * 4));   // what a form leaves unwritten comes back as NaN / -1
+        NC_HIP(hipMemset(dl.p, 0xFF, nl * 4));
+        NC_HIP(hipMemset(dc.p, 0xFF, nc * 8));
+        rvq.quantize(form, n_q, L, D, N, dr.as<float>(), B, T, dc.as<int64_t>(), dz.as<float>(), dl.as<float>(), ds.as<float>(), nullptr, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(codes, dc.p, nc * 8, hipMemcpyDeviceToHost));
+        NC_HIP(hipMemcpy(zq, dz.p, nr * 4, hipMemcpyDeviceToHost));
+        NC_HIP(hipMemcpy(latents, dl.p, nl * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_rvq_update(int device_index, const float* q, float* zq, float* residual, int64_t rows, int64_t T, int32_t s, int32_t first) {
+    return guard([&] {
+        if (!q || !zq) fail(NC_EINVAL, "null argument");
+        if (rows <= 0 || T <= 0 || s <= 0 || T % s != 0 || rows > ((int64_t)1 << 31) / T) fail(NC_EINVAL, "bad update shape");
+        op_set_device(device_index);
+        const size_t n = (size_t)rows * T;
+        DevBuf dq, dz, dr;
+        op_upload(dq, q, n / s); op_upload(dz, zq, n);
+        float* r = residual ? op_upload(dr, residual, n) : nullptr;
+        launch_rvq_update(dq.as<float>(), dz.as<float>(), r, rows, T, s, first != 0, nullptr, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(zq, dz.p, n * 4, hipMemcpyDeviceToHost));
+        if (residual) NC_HIP(hipMemcpy(residual, dr.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+nc_status nc_op_vq_gather(int device_index, const float* codebook, int32_t N, int32_t D, const int64_t* codes, int64_t codes_offset,
+                          int64_t codes_bstride, int32_t B, int64_t T, float* out, int64_t out_guard) {
+    return guard([&] {
+        if (!codebook || !codes || !out) fail(NC_EINVAL, "null argument");
+        if (N <= 0 || D <= 0 || B <= 0 || T <= 0 || T > ((int64_t)1 << 30) || codes_offset < 0 || codes_bstride < T || out_guard < 0 ||
+            codes_bstride > ((int64_t)1 << 31) / B || (int64_t)B * D > ((int64_t)1 << 31) / T)
+            fail(NC_EINVAL, "bad gather shape");
+        op_set_device(device_index);
+        Codebook cb;
+        cb.build(codebook, N, D);
+        const size_t n_codes = (size_t)codes_offset + (size_t)(B - 1) * codes_bstride + T;   // the words the B rows of T codes span
+        const size_t n_out = (size_t)B * D * T + 2 * (size_t)out_guard;
+        DevBuf dc, dout;
+        dc.reserve(n_codes * 8);
+        NC_HIP(hipMemcpy(dc.p, codes, n_codes * 8, hipMemcpyHostToDevice));
+        op_upload(dout, out - out_guard, n_out);
+        launch_vq_gather(cb, dc.as<int64_t>() + codes_offset, codes_bstride, B, T, dout.as<float>() + out_guard, nullptr, nullptr);
+        NC_HIP(hipDeviceSynchronize());
+        NC_HIP(hipMemcpy(out - out_guard, dout.p, n_out * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* x, int32_t B, int64_t L, int32_t tap, float* out, float* stats,
                               int32_t* C_out, int64_t* L_out, int32_t* n_taps, int32_t* has_stats) {
     return guard([&] {

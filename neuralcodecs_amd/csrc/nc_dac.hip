@@ -10,6 +10,7 @@
 // so no activation makes an HBM round trip of its own.
 #include <cstdlib>
 #include <cstring>
+#include <tuple>
 
 #include "nc_model.h"
 
@@ -60,9 +61,8 @@ static void load_alpha(const Blob& b, const std::string& name, int C, DevBuf& ds
     upload(dst, static_cast<const float*>(t.data), C);
 }
 
-// weight_v / weight_g / bias -> folded dense weight -> packed device image
-static void load_wn_conv(const Blob& b, const std::string& prefix, ConvLayer& L, int Cin, int Cout, int K, int stride, int pad,
-                         int dil, bool transposed, int kclass) {
+// weight_v / weight_g / bias -> folded dense weight in w; returns the bias (null: the layer has none)
+static const float* fold_wn_conv(const Blob& b, const std::string& prefix, int Cin, int Cout, int K, bool transposed, std::vector<float>& w) {
     const BlobTensor& v = b.get(prefix + ".weight_v");
     const BlobTensor& g = b.get(prefix + ".weight_g");
     const BlobTensor* bias = b.find(prefix + ".bias");
@@ -71,10 +71,83 @@ static void load_wn_conv(const Blob& b, const std::string& prefix, ConvLayer& L,
         fail(NC_EINVAL, "%s.weight_v has the wrong shape", prefix.c_str());
     if (g.numel() != d0) fail(NC_EINVAL, "%s.weight_g: expected %lld elements (one per dim-0 slice)", prefix.c_str(), (long long)d0);
     if (bias && bias->numel() != Cout) fail(NC_EINVAL, "%s.bias has the wrong length", prefix.c_str());
-    std::vector<float> w((size_t)v.numel());
+    w.resize((size_t)v.numel());
     fold_weight_norm_dac(static_cast<const float*>(v.data), static_cast<const float*>(g.data), d0, d1 * K, w.data());
+    return bias ? static_cast<const float*>(bias->data) : nullptr;
+}
+
+// folded dense weight -> packed device image
+static void load_wn_conv(const Blob& b, const std::string& prefix, ConvLayer& L, int Cin, int Cout, int K, int stride, int pad,
+                         int dil, bool transposed, int kclass) {
+    std::vector<float> w;
+    const float* bias = fold_wn_conv(b, prefix, Cin, Cout, K, transposed, w);
     L.kclass = kclass;
-    L.build(w.data(), bias ? static_cast<const float*>(bias->data) : nullptr, Cin, Cout, K, stride, pad, dil, 0, transposed);
+    L.build(w.data(), bias, Cin, Cout, K, stride, pad, dil, 0, transposed);
+}
+
+// ---- the quantizer's stages -------------------------------------------------------------------------------------------------------
+void DacRvq::clear_stages() {
+    in_proj.clear(); out_proj.clear(); codebooks.clear(); rvq_dense.clear(); stage_tab.clear();
+}
+
+void DacRvq::add_stage(const float* w_in, const float* b_in, const float* w_out, const float* b_out, const float* codebook, int L, int D, int N) {
+    in_proj.emplace_back(new ConvLayer());
+    out_proj.emplace_back(new ConvLayer());
+    codebooks.emplace_back(new Codebook());
+    in_proj.back()->kclass = NC_KC_CONV_K1;
+    in_proj.back()->build(w_in, b_in, L, D, 1, 1, 0, 1, 0, false);
+    out_proj.back()->kclass = NC_KC_CONV_K1;
+    out_proj.back()->build(w_out, b_out, D, L, 1, 1, 0, 1, 0, false);
+    codebooks.back()->build(codebook, N, D);
+    // dense projection weights for the stage-fused quantizer (same folded values as the packed images)
+    auto dense = [&](const float* w, const float* bias, size_t nw, size_t nb) {
+        rvq_dense.emplace_back(new DevBuf());
+        upload(*rvq_dense.back(), w, nw);
+        const float* w_dev = rvq_dense.back()->as<float>();
+        std::vector<float> bz(nb, 0.0f);
+        if (bias) std::memcpy(bz.data(), bias, nb * sizeof(float));
+        rvq_dense.emplace_back(new DevBuf());
+        upload(*rvq_dense.back(), bz.data(), bz.size());
+        return std::make_pair(w_dev, (const float*)rvq_dense.back()->as<float>());
+    };
+    std::vector<float> wt((size_t)D * L);                                   // [D][L] -> [L][D]
+    for (int d = 0; d < D; ++d)
+        for (int c = 0; c < L; ++c) wt[(size_t)c * D + d] = w_in[(size_t)d * L + c];
+    RvqStage t{};
+    std::tie(t.w_inT, t.b_in) = dense(wt.data(), b_in, wt.size(), (size_t)D);
+    std::tie(t.w_out, t.b_out) = dense(w_out, b_out, (size_t)L * D, (size_t)L);   // [L][D]
+    t.cbT = codebooks.back()->cbT.as<float>();
+    t.c2 = codebooks.back()->c2.as<float>();
+    t.cb = codebooks.back()->cb.as<float>();
+    stage_tab.push_back(t);
+}
+
+void DacRvq::upload_stages() {
+    rvq_stages.reserve(stage_tab.size() * sizeof(RvqStage));
+    NC_HIP(hipMemcpy(rvq_stages.p, stage_tab.data(), stage_tab.size() * sizeof(RvqStage), hipMemcpyHostToDevice));
+}
+
+void DacRvq::quantize(int form, int nq, int L, int D, int N, float* residual, int B, int64_t Tz, int64_t* codes, float* zq_d, float* lat_d,
+                      float* st, hipStream_t stream, Profiler* prof) {
+    static const bool stagewise = env_present("NC_DAC_RVQ_STAGEWISE");
+    if (form < 0 ? !stagewise : form == 1) {
+        if (launch_dac_rvq_fused(rvq_stages.as<RvqStage>(), nq, L, D, N, residual, B, Tz, codes, zq_d, lat_d, stream, prof)) return;
+        if (form == 1) fail(NC_EUNSUPPORTED, "no one-launch DAC quantizer for latent %d, codebook %d x %d, %d stages", L, N, D, nq);
+    }
+    NC_HIP(hipMemsetAsync(zq_d, 0, (size_t)B * L * Tz * 4, stream));
+    for (int i = 0; i < nq; ++i) {
+        ConvIO pi{};  // in_proj 1x1: residual -> z_e, stored as channel slice i of `latents`
+        pi.x = residual; pi.x_bstride = (int64_t)L * Tz; pi.x_cstride = Tz; pi.x_len = (int32_t)Tz; pi.Tin = Tz;
+        pi.y = lat_d + (int64_t)i * D * Tz; pi.y_bstride = (int64_t)nq * D * Tz; pi.y_cstride = Tz;
+        launch_conv(*in_proj[i], pi, B, stream, prof);
+        launch_vq_argmin(*codebooks[i], lat_d + (int64_t)i * D * Tz, (int64_t)nq * D * Tz, B, Tz, codes + (int64_t)i * Tz,
+                         (int64_t)nq * Tz, st, stream, prof);
+        ConvIO po{};  // out_proj 1x1 with fused zq += q ; residual -= q
+        po.x = st; po.x_bstride = (int64_t)D * Tz; po.x_cstride = Tz; po.x_len = (int32_t)Tz; po.Tin = Tz;
+        po.y = zq_d; po.y_bstride = (int64_t)L * Tz; po.y_cstride = Tz;
+        po.rvq_zq = zq_d; po.rvq_res = residual; po.epi = EPI_RVQ;
+        launch_conv(*out_proj[i], po, B, stream, prof);
+    }
 }
 
 DacModel::DacModel(const nc_dac_config& c) : cfg(c) {
@@ -124,57 +197,19 @@ void DacModel::load(const Blob& b) {
     snprintf(nm, sizeof nm, "encoder.block.%d", cfg.n_encoder_rates + 2);
     load_wn_conv(b, nm, enc_out, d, latent, 3, 1, 1, 1, false, NC_KC_CONV_MISC);
 
-    in_proj.clear(); out_proj.clear(); codebooks.clear();
+    clear_stages();
     for (int i = 0; i < cfg.n_codebooks; ++i) {
         snprintf(nm, sizeof nm, "quantizer.quantizers.%d", i);
         const std::string p = nm;
-        in_proj.emplace_back(new ConvLayer());
-        out_proj.emplace_back(new ConvLayer());
-        codebooks.emplace_back(new Codebook());
-        load_wn_conv(b, p + ".in_proj", *in_proj.back(), latent, cfg.codebook_dim, 1, 1, 0, 1, false, NC_KC_CONV_K1);
-        load_wn_conv(b, p + ".out_proj", *out_proj.back(), cfg.codebook_dim, latent, 1, 1, 0, 1, false, NC_KC_CONV_K1);
+        std::vector<float> w_in, w_out;
+        const float* b_in = fold_wn_conv(b, p + ".in_proj", latent, cfg.codebook_dim, 1, false, w_in);
+        const float* b_out = fold_wn_conv(b, p + ".out_proj", cfg.codebook_dim, latent, 1, false, w_out);
         const BlobTensor& cb = b.get(p + ".codebook.weight");
         if (cb.dims.size() != 2 || cb.dims[0] != cfg.codebook_size || cb.dims[1] != cfg.codebook_dim)
             fail(NC_EINVAL, "%s.codebook.weight has the wrong shape", p.c_str());
-        codebooks.back()->build(static_cast<const float*>(cb.data), cfg.codebook_size, cfg.codebook_dim);
+        add_stage(w_in.data(), b_in, w_out.data(), b_out, static_cast<const float*>(cb.data), latent, cfg.codebook_dim, cfg.codebook_size);
     }
-    {   // dense projection weights of every stage for the stage-fused quantizer (same folded values as the packed images)
-        const int D = cfg.codebook_dim;
-        rvq_dense.clear();
-        std::vector<RvqStage> tab((size_t)cfg.n_codebooks);
-        auto dense = [&](const std::string& prefix, int64_t d0, int64_t inner, bool transpose, const float** w_dev, const float** b_dev, int64_t nb) {
-            const BlobTensor& v = b.get(prefix + ".weight_v");
-            const BlobTensor& g = b.get(prefix + ".weight_g");
-            const BlobTensor* bias = b.find(prefix + ".bias");
-            std::vector<float> w((size_t)(d0 * inner)), wt;
-            fold_weight_norm_dac(static_cast<const float*>(v.data), static_cast<const float*>(g.data), d0, inner, w.data());
-            if (transpose) {
-                wt.resize(w.size());
-                for (int64_t r = 0; r < d0; ++r)
-                    for (int64_t c = 0; c < inner; ++c) wt[(size_t)(c * d0 + r)] = w[(size_t)(r * inner + c)];
-            }
-            rvq_dense.emplace_back(new DevBuf());
-            upload(*rvq_dense.back(), transpose ? wt.data() : w.data(), w.size());
-            *w_dev = rvq_dense.back()->as<float>();
-            std::vector<float> bz((size_t)nb, 0.0f);
-            if (bias) std::memcpy(bz.data(), bias->data, (size_t)nb * sizeof(float));
-            rvq_dense.emplace_back(new DevBuf());
-            upload(*rvq_dense.back(), bz.data(), bz.size());
-            *b_dev = rvq_dense.back()->as<float>();
-        };
-        for (int i = 0; i < cfg.n_codebooks; ++i) {
-            snprintf(nm, sizeof nm, "quantizer.quantizers.%d", i);
-            const std::string p = nm;
-            RvqStage& t = tab[(size_t)i];
-            dense(p + ".in_proj", D, latent, true, &t.w_inT, &t.b_in, D);          // [D][latent] -> [latent][D]
-            dense(p + ".out_proj", latent, D, false, &t.w_out, &t.b_out, latent);  // [latent][D]
-            t.cbT = codebooks[(size_t)i]->cbT.as<float>();
-            t.c2 = codebooks[(size_t)i]->c2.as<float>();
-            t.cb = codebooks[(size_t)i]->cb.as<float>();
-        }
-        rvq_stages.reserve(tab.size() * sizeof(RvqStage));
-        NC_HIP(hipMemcpy(rvq_stages.p, tab.data(), tab.size() * sizeof(RvqStage), hipMemcpyHostToDevice));
-    }
+    upload_stages();
 
     int ch = cfg.decoder_dim;
     load_wn_conv(b, "decoder.model.0", dec_in, latent, ch, 7, 1, 3, 1, false, NC_KC_CONV_MISC);
@@ -324,21 +359,7 @@ void DacModel::encode_dev(const float* pcm, int B, int64_t T, int sample_rate, i
     // ---- residual vector quantizer (ResidualVectorQuantizer.cs:54-103)
     float* zq_d = z ? z : zq.as<float>();
     float* lat_d = latents ? latents : lat.as<float>();
-    if (launch_dac_rvq_fused(rvq_stages.as<RvqStage>(), nq, latent, D, cfg.codebook_size, residual, B, Tz, codes, zq_d, lat_d, stream, &prof)) return;
-    NC_HIP(hipMemsetAsync(zq_d, 0, (size_t)B * latent * Tz * 4, stream));
-    for (int i = 0; i < nq; ++i) {
-        ConvIO pi{};  // in_proj 1x1: residual -> z_e, stored as channel slice i of `latents`
-        pi.x = residual; pi.x_bstride = (int64_t)latent * Tz; pi.x_cstride = Tz; pi.x_len = (int32_t)Tz; pi.Tin = Tz;
-        pi.y = lat_d + (int64_t)i * D * Tz; pi.y_bstride = (int64_t)nq * D * Tz; pi.y_cstride = Tz;
-        launch_conv(*in_proj[i], pi, B, stream, &prof);
-        launch_vq_argmin(*codebooks[i], lat_d + (int64_t)i * D * Tz, (int64_t)nq * D * Tz, B, Tz, codes + (int64_t)i * Tz,
-                         (int64_t)nq * Tz, st.as<float>(), stream, &prof);
-        ConvIO po{};  // out_proj 1x1 with fused zq += q ; residual -= q
-        po.x = st.as<float>(); po.x_bstride = (int64_t)D * Tz; po.x_cstride = Tz; po.x_len = (int32_t)Tz; po.Tin = Tz;
-        po.y = zq_d; po.y_bstride = (int64_t)latent * Tz; po.y_cstride = Tz;
-        po.rvq_zq = zq_d; po.rvq_res = residual; po.epi = EPI_RVQ;
-        launch_conv(*out_proj[i], po, B, stream, &prof);
-    }
+    quantize(-1, nq, latent, D, cfg.codebook_size, residual, B, Tz, codes, zq_d, lat_d, st.as<float>(), stream, &prof);
 }
 
 void DacModel::from_codes_dev(const int64_t* codes, int B, int n_q, int64_t Tz, float* z) {

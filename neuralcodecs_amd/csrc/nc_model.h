@@ -37,9 +37,11 @@ struct RvqStage {
     const float* c2;      // [N]
     const float* cb;      // [N][D]
 };
-// ResidualVectorQuantizer.forward for n_q stages in ONE launch (ResidualVectorQuantizer.cs:54-103); returns false when the shape has
-// no instantiation (the caller then runs the stage-by-stage launches).  residual [B,L,T] (read only), zq [B,L,T], latents
-// [B,n_q*D,T], codes [B,n_q,T].
+// The shapes the one-launch kernel has an instantiation for: D == 8, L in {256, 512, 768, 1024}, N a multiple of 64 up to 1024, n_q >= 1
+bool dac_rvq_fused_admits(int n_q, int L, int D, int N);
+// ResidualVectorQuantizer.forward for n_q stages in ONE launch (ResidualVectorQuantizer.cs:54-103); returns false, with nothing
+// launched, when the shape has no instantiation (the caller then runs the stage-by-stage launches).  residual [B,L,T] (read only),
+// zq [B,L,T], latents [B,n_q*D,T], codes [B,n_q,T].
 bool launch_dac_rvq_fused(const RvqStage* stages_dev, int n_q, int L, int D, int N, const float* residual, int B, int64_t T, int64_t* codes,
                           float* zq, float* latents, hipStream_t s, Profiler* prof);
 // z_e [B,D,T] (batch stride ze_bstride) -> codes[b*codes_bstride + t] (int64) and st [B,D,T] = z_e + (cb[idx] - z_e)
@@ -48,6 +50,29 @@ void launch_vq_argmin(const Codebook& cb, const float* z_e, int64_t ze_bstride, 
 // codes -> out [B,D,T] = cb[codes]  (Embedding + transpose, VectorQuantizer.cs:135-142)
 void launch_vq_gather(const Codebook& cb, const int64_t* codes, int64_t codes_bstride, int B, int64_t T, float* out, hipStream_t s,
                       Profiler* prof);
+
+// The DAC quantizer resident on the device (nc_dac.hip): per stage the packed projection layers of the stage-by-stage launches, the
+// codebook images and the dense projection weights of the one-launch kernel.  DacModel is one, filled by its loader; the test hook
+// nc_op_dac_rvq fills one from host arrays through the same routines.
+struct DacRvq {
+    std::vector<std::unique_ptr<ConvLayer>> in_proj, out_proj;
+    std::vector<std::unique_ptr<Codebook>> codebooks;
+    std::vector<std::unique_ptr<DevBuf>> rvq_dense;   // dense projection weights / biases of the stage-fused quantizer
+    DevBuf rvq_stages;                                // RvqStage[stages]
+    void clear_stages();
+    // the next stage from folded dense weights: w_in [D][L], w_out [L][D], codebook [N][D]; b_in [D] / b_out [L] nullable (then zero)
+    void add_stage(const float* w_in, const float* b_in, const float* w_out, const float* b_out, const float* codebook, int L, int D, int N);
+    void upload_stages();                             // after the last add_stage
+    // ResidualVectorQuantizer.forward, first n_q stages (ResidualVectorQuantizer.cs:54-103): residual [B,L,T] (updated in place by the
+    // stage-by-stage form) -> codes [B,n_q,T], zq [B,L,T], latents [B,n_q*D,T]; st: workspace of B*D*T floats.  form < 0: one launch
+    // where the shape has the instance and NC_DAC_RVQ_STAGEWISE is unset, else a launch sequence per stage; form 0 / 1 force the
+    // stage-by-stage / the one-launch form whatever the environment says (1 fails with NC_EUNSUPPORTED on a shape it does not take).
+    void quantize(int form, int n_q, int L, int D, int N, float* residual, int B, int64_t T, int64_t* codes, float* zq, float* latents,
+                  float* st, hipStream_t s, Profiler* prof);
+
+  private:
+    std::vector<RvqStage> stage_tab;
+};
 
 // ---- Euclidean RVQ of Encodec (nc_euclid_rvq.hip) ----------------------------------------------
 constexpr int EUCLID_MAX_D = 128;   // widest code vector the kernels hold in LDS
@@ -126,7 +151,7 @@ struct OwnStreamScope {
     }
 };
 
-struct DacModel : Codec {
+struct DacModel : Codec, DacRvq {
     static constexpr int kKind = 0;
     static constexpr const char* kKindName = "a DAC";
     nc_dac_config cfg{};
@@ -146,10 +171,7 @@ struct DacModel : Codec {
     DevBuf enc_alpha_out;
     ConvLayer enc_out;
 
-    std::vector<std::unique_ptr<ConvLayer>> in_proj, out_proj;
-    std::vector<std::unique_ptr<Codebook>> codebooks;
-    std::vector<std::unique_ptr<DevBuf>> rvq_dense;   // dense projection weights / biases of the stage-fused quantizer
-    DevBuf rvq_stages;                                // RvqStage[n_codebooks]
+    // the quantizer's stages: DacRvq (in_proj, out_proj, codebooks, rvq_stages)
 
     ConvLayer dec_in;
     struct DecBlk {

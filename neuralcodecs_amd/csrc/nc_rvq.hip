@@ -382,12 +382,19 @@ __global__ __launch_bounds__(256) void dac_rvq_fused_kernel(const RvqFusedArgs a
     }
 }
 
+static size_t rvq_fused_lds(int L, int N) {
+    return sizeof(float) * ((size_t)L * RP + (size_t)RD * N + N + (size_t)L * RD + 2 * RF * RD + 2 * RF);
+}
+
+bool dac_rvq_fused_admits(int n_q, int L, int D, int N) {
+    if (D != RD || L <= 0 || L % 256 != 0 || L > 1024 || N <= 0 || N % 64 != 0 || N > 1024 || n_q <= 0) return false;
+    return rvq_fused_lds(L, N) <= 160 * 1024;
+}
+
 bool launch_dac_rvq_fused(const RvqStage* stages_dev, int n_q, int L, int D, int N, const float* residual, int B, int64_t T, int64_t* codes,
                           float* zq, float* latents, hipStream_t s, Profiler* prof) {
-    static const bool off = env_present("NC_DAC_RVQ_STAGEWISE");
-    if (off || D != RD || L % 256 != 0 || L > 1024 || N % 64 != 0 || N > 1024 || n_q <= 0) return false;
-    const size_t lds = sizeof(float) * ((size_t)L * RP + (size_t)RD * N + N + (size_t)L * RD + 2 * RF * RD + 2 * RF);
-    if (lds > 160 * 1024) return false;
+    if (!dac_rvq_fused_admits(n_q, L, D, N)) return false;   // (NC_DAC_RVQ_STAGEWISE: the caller's choice, DacRvq::quantize)
+    const size_t lds = rvq_fused_lds(L, N);
     ensure_dynamic_lds((const void*)dac_rvq_fused_kernel, 160 * 1024);
     const int64_t total = (int64_t)B * T;
     RvqFusedArgs a{};

@@ -65,6 +65,50 @@ def euclid_rvq(residual, codebooks, form=1, device_index=0):
     return codes, out
 
 
+def dac_rvq(residual, w_in, b_in, codebooks, w_out, b_out, form=1, out=None, device_index=0):
+    """The DAC quantizer on residual [B,L,T] with folded weights w_in [n_q,D,L], b_in [n_q,D], codebooks [n_q,N,D], w_out [n_q,L,D],
+    b_out [n_q,L] -> (codes [B,n_q,T], zq [B,L,T], latents [B,n_q*D,T]).  form=1: all stages in one launch (NcError status
+    NC_EUNSUPPORTED where that kernel has no instance); form=0: the launches per stage.  out=(codes, zq, latents): arrays to fill; the
+    call then returns the raw status instead of raising (the refusal tests look at what an error leaves in them)."""
+    r = _f(residual); wi = _f(w_in); cb = _f(codebooks); wo = _f(w_out); bi = _f(b_in); bo = _f(b_out)
+    B, L, T = r.shape
+    nq, N, D = cb.shape
+    if nq and out is None:
+        assert wi.shape == (nq, D, L) and wo.shape == (nq, L, D) and (bi is None or bi.shape == (nq, D)) and (bo is None or bo.shape == (nq, L))
+    if out is None:
+        codes = np.empty((B, nq, T), np.int64); zq = np.empty_like(r); lat = np.empty((B, nq * D, T), np.float32)
+    else:
+        codes, zq, lat = out
+    st = _lib.lib().nc_op_dac_rvq(device_index, r.ctypes.data, B, L, T, nq, N, D, wi.ctypes.data, _p(bi), cb.ctypes.data, wo.ctypes.data, _p(bo),
+                                  int(form), codes.ctypes.data, zq.ctypes.data, lat.ctypes.data)
+    if out is not None:
+        return st
+    _lib.check(st)
+    return codes, zq, lat
+
+
+def rvq_update(q, zq, residual=None, s=1, first=False, device_index=0):
+    """SNAC's quantizer update on q [rows,T/s], zq [rows,T], residual [rows,T] or None: returns (zq', residual' or None) with
+    zq' = (0 if first else zq) + repeat(q, s) and residual' = residual - repeat(q, s); the inputs are left as they are."""
+    q = _f(q); zq = _f(zq).copy(); r = None if residual is None else _f(residual).copy()
+    rows, T = zq.shape
+    assert q.shape == (rows, T // s) and (r is None or r.shape == zq.shape)
+    _lib.check(_lib.lib().nc_op_rvq_update(device_index, q.ctypes.data, zq.ctypes.data, _p(r), rows, T, int(s), 1 if first else 0))
+    return zq, r
+
+
+def vq_gather(codebook, codes_flat, codes_offset, codes_bstride, B, T, guard=0, fill=0.0, device_index=0):
+    """out[b,d,t] = codebook[codes_flat[codes_offset + b * codes_bstride + t]][d] (a code outside [0, N) is clamped) -> the whole output
+    buffer, flat: `guard` floats of `fill`, out [B,D,T], `guard` floats of `fill`, all of it through the device and back."""
+    cb = _f(codebook); codes = np.ascontiguousarray(codes_flat, np.int64).reshape(-1)
+    N, D = cb.shape
+    assert codes_offset >= 0 and codes_bstride >= T and codes_offset + (B - 1) * codes_bstride + T <= codes.size
+    buf = np.full(B * D * T + 2 * guard, fill, np.float32)
+    _lib.check(_lib.lib().nc_op_vq_gather(device_index, cb.ctypes.data, N, D, codes.ctypes.data, int(codes_offset), int(codes_bstride), B, T,
+                                          buf.ctypes.data + 4 * guard, int(guard)))
+    return buf
+
+
 def encodec_trace_taps(model):
     """Number of taps of either stack of a loaded Encodec model (3 + 4 * len(ratios))."""
     n = C.c_int32()

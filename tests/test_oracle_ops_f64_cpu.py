@@ -176,6 +176,29 @@ def test_oracle_euclid_rvq_stages_are_the_binary64_argmin(case):
         r = r - books[q][idx].transpose(0, 2, 1)
 
 
+def test_oracle_rvq_stage_loop_is_refdac_encode_bit_for_bit():
+    """rvq_judge.oracle_stages -- the stage loop the quantizer op tests compare the engine with, composed from c_oracle.conv1d and
+    c_oracle.vq_argmin -- fed the oracle's own encoder output and the folded dac_small weights, gives RefDAC.encode's codes, latents and
+    zq bit for bit."""
+    import rvq_judge
+    from conftest import dac_cfg_from_meta, load_golden
+    from neuralcodecs_amd.weights import dac_synthetic_state_dict, save_blob
+    g = load_golden("dac_small")
+    cfg = dac_cfg_from_meta(g["meta"])
+    sd = dac_synthetic_state_dict(cfg, seed=g["meta"]["weight_seed"])
+    zq, codes, lat, ze = c_oracle.RefDAC(cfg, save_blob(sd)).encode(g["pcm"])
+    fold = lambda p: c_oracle.fold_wn_dac(sd[p + ".weight_v"], sd[p + ".weight_g"])[:, :, 0]
+    names = [f"quantizer.quantizers.{i}" for i in range(cfg.n_codebooks)]
+    stages, c2, l2, z2 = rvq_judge.oracle_stages(
+        ze, np.stack([fold(p + ".in_proj") for p in names]), np.stack([sd[p + ".in_proj.bias"] for p in names]),
+        np.stack([sd[p + ".codebook.weight"] for p in names]), np.stack([fold(p + ".out_proj") for p in names]),
+        np.stack([sd[p + ".out_proj.bias"] for p in names]))
+    assert len(stages) == cfg.n_codebooks and codes.size > 0
+    assert np.array_equal(c2, codes) and c2.dtype == codes.dtype
+    assert np.array_equal(l2, lat) and np.array_equal(z2, zq)
+    assert np.array_equal(stages[0]["r_in"], ze)
+
+
 # ---- the SNAC pieces the oracle exports ------------------------------------------------------------------------------------------------
 def test_oracle_layer_norm_attention_and_pooling_pieces():
     rng = np.random.default_rng(3)
