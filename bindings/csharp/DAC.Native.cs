@@ -225,6 +225,21 @@ public sealed unsafe class DACNative : INeuralCodec
         return pcm;
     }
 
+    /// <summary>Codes pushed as a model emits them (Dia): every push returns the PCM that became final; concatenated, the pieces are
+    /// Decode(FromCodes(all codes)), bit for bit.  Dispose the session before the model.</summary>
+    public NcSession DecodeSession(int batch, int? nQuantizers = null)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_create(_h, 1, batch, nQuantizers ?? 0, out IntPtr s));
+        return new NcSession(s, batch);
+    }
+
+    /// <summary>PCM pushed as it is recorded: every push returns the codes [batch, NumCodebooks, n] that became final.</summary>
+    public NcSession EncodeSession(int batch)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_create(_h, 0, batch, 0, out IntPtr s));
+        return new NcSession(s, batch * _config.NumCodebooks);
+    }
+
     public void Dispose()                                                           // Models/DAC.cs:329-338
     {
         if (_h != IntPtr.Zero) { NcMi355x.nc_codec_destroy(_h); _h = IntPtr.Zero; }

@@ -1,6 +1,7 @@
 // Factories for the native models, shaped like the reference's NeuralCodecs.Create{SNAC,DAC,Encodec}Async (NeuralCodecs.Torch/
 // NeuralCodecs.cs:38-80: same parameter lists; the reference class is `public static partial class NeuralCodecs`, so these members
-// join it), and the tensor <-> host-array marshalling the *Native models use at their TorchSharp-typed API surface.
+// join it), the tensor <-> host-array marshalling the *Native models use at their TorchSharp-typed API surface, and NcSession, the
+// incremental session DACNative / SNACNative hand out (DecodeSession / EncodeSession).
 // `path` names an NCWB weight blob (tools/convert_checkpoint.py converts HF safetensors / Descript .pth / SNAC torch files).
 using System;
 using System.IO;
@@ -13,6 +14,7 @@ using NeuralCodecs.Torch.Config.DAC;
 using NeuralCodecs.Torch.Config.Encodec;
 using NeuralCodecs.Torch.Config.SNAC;
 using NeuralCodecs.Torch.Models;
+using NeuralCodecs.Torch.Native;
 using TorchSharp;
 using static TorchSharp.torch;
 
@@ -82,4 +84,92 @@ internal static class NcTensor
     public static long[] Longs(Tensor t) => t.cpu().detach().to(torch.int64).contiguous().data<long>().ToArray();
     public static Tensor From(float[] a, params long[] shape) => torch.tensor(a, dtype: torch.float32).reshape(shape);
     public static Tensor From(long[] a, params long[] shape) => torch.tensor(a, dtype: torch.int64).reshape(shape);
+}
+
+/// <summary>An incremental session on a DAC or SNAC model (nc_session_*, include/nc_mi355x.h "incremental sessions"): codes or PCM are
+/// pushed as they arrive and every call returns the outputs that became final; concatenated along time they are what the one-shot call
+/// on the whole sequence returns, bit for bit.  Host arrays, synchronous.  The model must outlive its sessions.</summary>
+public sealed unsafe class NcSession : IDisposable
+{
+    private IntPtr _s;
+    private readonly int _rows;             // rows of an output: B (PCM, SNAC codes) or B * codebooks (DAC codes)
+
+    internal NcSession(IntPtr session, int rows) { _s = session; _rows = rows; }
+
+    /// <summary>Frames pushed and not yet emitted.</summary>
+    public long Pending
+    {
+        get { long n; NcMi355x.Check(NcMi355x.nc_session_pending(_s, &n)); return n; }
+    }
+
+    /// <summary>After a reset the session is as new: the next push starts another clip.</summary>
+    public void Reset() => NcMi355x.Check(NcMi355x.nc_session_reset(_s));
+
+    /// <summary>Seed of the noise a SNAC decode session draws when a push carries none (not the draw of SNAC.Decode).</summary>
+    public void SetSeed(ulong seed) => NcMi355x.Check(NcMi355x.nc_session_set_seed(_s, seed));
+
+    /// <summary>Decode session: the next frames' codes (DAC [B,nQ,n]; SNAC the levels of a row side by side) -> PCM [B,nOut].</summary>
+    public float[] PushCodes(long[] codes, long frames, float[]? noise, out long nOut)
+    {
+        ArgumentNullException.ThrowIfNull(codes);
+        long cap, n;
+        NcMi355x.Check(NcMi355x.nc_session_query(_s, frames, &cap));
+        var buf = new float[_rows * Math.Max(cap, 1)];
+        fixed (long* pc = codes) fixed (float* pn = noise, po = buf)
+            NcMi355x.Check(NcMi355x.nc_session_push(_s, pc, frames, pn, po, cap, &n));
+        nOut = n;
+        return Rows(buf, cap, n);
+    }
+
+    /// <summary>Encode session: the next samples [B,n] -> codes (DAC [B,codebooks,nOut]; SNAC [B,nOut], the levels side by side).</summary>
+    public long[] PushAudio(float[] pcm, long samples, out long nOut)
+    {
+        ArgumentNullException.ThrowIfNull(pcm);
+        long cap, n;
+        NcMi355x.Check(NcMi355x.nc_session_query(_s, samples, &cap));
+        var buf = new long[_rows * Math.Max(cap, 1)];
+        fixed (float* pp = pcm) fixed (long* po = buf)
+            NcMi355x.Check(NcMi355x.nc_session_push(_s, pp, samples, null, po, cap, &n));
+        nOut = n;
+        return Rows(buf, cap, n);
+    }
+
+    /// <summary>The end of the clip of a decode session: everything not yet emitted.</summary>
+    public float[] FlushAudio(out long nOut)
+    {
+        long cap, n;
+        NcMi355x.Check(NcMi355x.nc_session_query(_s, 0, &cap));
+        var buf = new float[_rows * Math.Max(cap, 1)];
+        fixed (float* po = buf)
+            NcMi355x.Check(NcMi355x.nc_session_flush(_s, po, cap, &n));
+        nOut = n;
+        return Rows(buf, cap, n);
+    }
+
+    /// <summary>The end of the clip of an encode session: the codes of the frames not yet emitted.</summary>
+    public long[] FlushCodes(out long nOut)
+    {
+        long cap, n;
+        NcMi355x.Check(NcMi355x.nc_session_query(_s, 0, &cap));
+        var buf = new long[_rows * Math.Max(cap, 1)];
+        fixed (long* po = buf)
+            NcMi355x.Check(NcMi355x.nc_session_flush(_s, po, cap, &n));
+        nOut = n;
+        return Rows(buf, cap, n);
+    }
+
+    private T[] Rows<T>(T[] buf, long cap, long n)                                  // [rows, cap] -> dense [rows, n]
+    {
+        var dense = new T[_rows * n];
+        for (int r = 0; r < _rows; ++r) Array.Copy(buf, r * cap, dense, r * n, n);
+        return dense;
+    }
+
+    public void Dispose()
+    {
+        if (_s != IntPtr.Zero) { NcMi355x.nc_session_destroy(_s); _s = IntPtr.Zero; }
+        GC.SuppressFinalize(this);
+    }
+
+    ~NcSession() { if (_s != IntPtr.Zero) NcMi355x.nc_session_destroy(_s); }
 }

@@ -191,6 +191,22 @@ public sealed unsafe class SNACNative : INeuralCodec
         return pcm;
     }
 
+    /// <summary>Code levels pushed as a model emits them (the Orpheus family): every push (a multiple of align frames, each level at its
+    /// own rate, with its noise blocks) returns the PCM that became final; concatenated, the pieces are Decode on the whole sequence, bit
+    /// for bit.  Dispose the session before the model.</summary>
+    public NcSession DecodeSession(int batch)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_create(_h, 1, batch, 0, out IntPtr s));
+        return new NcSession(s, batch);
+    }
+
+    /// <summary>PCM pushed as it is recorded: every push returns the code levels of the frames that became final, side by side.</summary>
+    public NcSession EncodeSession(int batch)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_create(_h, 0, batch, 0, out IntPtr s));
+        return new NcSession(s, batch);
+    }
+
     public void Dispose()
     {
         if (_h != IntPtr.Zero) { NcMi355x.nc_codec_destroy(_h); _h = IntPtr.Zero; }

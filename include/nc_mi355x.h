@@ -354,6 +354,68 @@ NC_API nc_status nc_snac_decode_ragged(nc_codec* h, const int64_t* codes_packed,
 NC_API nc_status nc_snac_decode_ragged_dev(nc_codec* h, const int64_t* codes_packed, int32_t B, const int64_t* frames, const float* noise,
                                            uint64_t seed, float* pcm_packed);
 
+/* ---------------------------------------------------------------------------- incremental sessions
+ * Codes or PCM pushed as they arrive (a text-to-speech model that emits code frames one at a time: Dia drives DAC, the Orpheus family
+ * SNAC 24 kHz; a live capture that wants codes while it records).  A session keeps the history between calls, decides after every push
+ * which outputs are final, and returns exactly those: the concatenated outputs of the pushes and the flush equal, bit for bit, what the
+ * one-shot call on the whole sequence returns.
+ * Contract.  With P frames pushed and E emitted so far, hl / hr the halos of the direction (halo_left / halo_right as
+ * nc_codec_chunk_plan reports them) and align as in nc_halo:
+ *   - a push emits the frames [E, floor_align(P - hr)); when that range is not empty it runs the window [max(0, E - hl), P) through the
+ *     existing launch sequence and keeps that range.  A window that starts at 0 has the clip's true left edge, every other window edge
+ *     is a cut edge, and every kept frame keeps clear of a cut edge by the halo;
+ *   - the flush runs [max(0, E - hl), P), whose right edge is the clip's true end, and emits [E, P);
+ *   - latency: an output is final hr frames after its own frame has arrived (the flush releases the rest); work per push of n frames:
+ *     a window of hl + n + hr frames once the session is in steady state; resident history: at most hl + hr + align frames.
+ * nc_session_schedule states the schedule as a host function (no handle, no device): one step per push, and one more for the flush
+ * when flush != 0.  NC_EINVAL: a null pointer, n_pushes < 0, n_pushes == 0 with a flush (nothing to flush), a push that is not a
+ * positive multiple of align. */
+typedef struct nc_session_step {
+    int64_t w0, w1;    /* the window the step runs, [w0, w1) in latent frames; w0 == w1: too little has arrived, nothing runs */
+    int64_t k0, k1;    /* the frames it keeps, [k0, k1); k0 == k1: none */
+    int64_t resident;  /* frames of history resident afterwards */
+} nc_session_step;
+NC_API nc_status nc_session_schedule(const nc_halo* halo, int32_t decode, int32_t n_pushes, const int64_t* push_frames, int32_t flush,
+                                     nc_session_step* steps /* n_pushes + (flush != 0) entries */);
+
+/* A session on a DAC or SNAC handle for B rows; decode != 0: codes in, PCM out, else PCM in, codes out.  n_q: the DAC codebooks a decode
+ * session reads (0 = all; SNAC and encode sessions ignore it: an encode session writes every codebook).  Several sessions may live on one
+ * handle: they share its arena and stream, and the caller serialises their calls like every other call on the handle.  A session
+ * BORROWS its handle: destroy the sessions first.  Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; the
+ * 24 kHz LSTM has unbounded context, so no window stands for the clip).
+ *   decode sessions   in: DAC codes [B, n_q, n]; SNAC every level at its own rate, [B, sum_i n / vq_strides[i]] as nc_snac_decode takes
+ *                     them (n a multiple of align).  n_in = n frames.  out: PCM rows [B, out_cap], the first *n_out samples of a row valid.
+ *                     SNAC with NoiseBlocks: `noise` holds the caller's noise for the pushed frames, one [B, 1, n * S_i] block per decoder
+ *                     stage laid end to end (S_i = the product of the first i + 1 decoder rates); the session keeps the part that belongs
+ *                     to the history, and the result equals nc_snac_decode on the noise concatenated along time.  noise == NULL: every push
+ *                     draws its block on the device from (seed, frame position of the push) -- nc_session_set_seed, 0 by default.  This
+ *                     is NOT the draw of nc_snac_decode(noise = NULL, seed): that draw's layout depends on the total length, which a
+ *                     session does not know (the reference's own noise, torch.randn at inference, is not reproducible either).
+ *   encode sessions   in: PCM rows [B, n], any n >= 1; n_in = n samples; `noise` is ignored.  Samples are buffered to whole hops (SNAC:
+ *                     hop * align).  out: DAC codes rows [B, n_codebooks, out_cap], the first *n_out frames of a row valid; SNAC rows
+ *                     [B, out_cap] holding the levels of the emitted frames side by side, coarse first (*n_out values in all).  The flush
+ *                     writes +0.0f behind the last sample up to the codec's own padding, as the ragged calls do, and emits the rest.
+ *                     There are no z / latents / zq outputs.
+ * *n_out is the number of elements written per row.  It follows from frame counts alone and is known before anything is launched, so the
+ * *_dev forms (device pointers, asynchronous on the handle's stream) never synchronise; the plain forms take host pointers and are
+ * synchronous.  nc_session_query gives the out_cap a push of n_in needs (an upper bound over every state of the session; n_in == 0: what
+ * a flush needs); out_cap is the row pitch of `out` in elements.  nc_session_pending: frames pushed and not yet emitted.
+ * NC_EINVAL, decided before anything is launched: a null pointer, n_in <= 0, a decode push that is not a multiple of align, out_cap below
+ * nc_session_query, a push or a second flush after a flush (until nc_session_reset, after which the session is as new), a flush with
+ * nothing pushed.  NC_ESTATE without weights. */
+typedef struct nc_session nc_session;
+NC_API nc_status nc_session_create(nc_codec* h, int32_t decode, int32_t B, int32_t n_q, nc_session** out);
+NC_API nc_status nc_session_destroy(nc_session* s);
+NC_API nc_status nc_session_reset(nc_session* s);
+NC_API nc_status nc_session_set_seed(nc_session* s, uint64_t seed);
+NC_API nc_status nc_session_query(const nc_session* s, int64_t n_in, int64_t* out_cap);
+NC_API nc_status nc_session_pending(const nc_session* s, int64_t* frames);
+NC_API nc_status nc_session_push(nc_session* s, const void* in, int64_t n_in, const float* noise, void* out, int64_t out_cap, int64_t* n_out);
+NC_API nc_status nc_session_push_dev(nc_session* s, const void* in, int64_t n_in, const float* noise, void* out, int64_t out_cap,
+                                     int64_t* n_out);
+NC_API nc_status nc_session_flush(nc_session* s, void* out, int64_t out_cap, int64_t* n_out);
+NC_API nc_status nc_session_flush_dev(nc_session* s, void* out, int64_t out_cap, int64_t* n_out);
+
 /* -------------------------------------------------------------------------------------- Encodec
  * replaces: new Encodec(EncodecConfig)            NeuralCodecs.Torch/Models/Encodec.cs:46-90
  * Only channels / dimension / norm / causal reach SEANet in the reference (Encodec.cs:57-68, deviation D11); the other SEANet

@@ -88,6 +88,10 @@ class NcEncodecRaggedRow(C.Structure):
                 ("length", C.c_int64), ("frames", C.c_int64)]
 
 
+class NcSessionStep(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("w0", "w1", "k0", "k1", "resident")]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
 
 _lib = None
@@ -157,6 +161,17 @@ SYMBOLS = [
     ("nc_snac_encode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("nc_snac_decode_ragged", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint64, _P]),
     ("nc_snac_decode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint64, _P]),
+    ("nc_session_schedule", C.c_int, [C.POINTER(NcHalo), C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    ("nc_session_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("nc_session_destroy", C.c_int, [_P]),
+    ("nc_session_reset", C.c_int, [_P]),
+    ("nc_session_set_seed", C.c_int, [_P, C.c_uint64]),
+    ("nc_session_query", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nc_session_pending", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("nc_session_push", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nc_session_push_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nc_session_flush", C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nc_session_flush_dev", C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("nc_encodec_create", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int, C.POINTER(_P)]),
     ("nc_encodec_set_bandwidth", C.c_int, [_P, C.c_float]),
     ("nc_encodec_query", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32,

@@ -290,6 +290,19 @@ class DAC(_lib.ProfileMixin):
             _lib.check(_lib.lib().nc_dac_decode_codes_ragged(self._h, flat.ctypes.data, B, _lib.i64_array(frames), nq, pcm.ctypes.data))
         return _lib.split_packed(pcm, sizes)
 
+    # ---- incremental sessions (codes or PCM pushed as they arrive) ---------------------------------
+    def decode_session(self, B: int, n_quantizers: Optional[int] = None):
+        """nc_session_create(decode): push codes [B, n_q, n] as a model emits them, get the PCM that became final; the pieces
+        concatenated are decode(from_codes(all codes)), bit for bit (neuralcodecs_amd/session.py)."""
+        from .session import Session
+        return Session(self, True, B, self._nq(n_quantizers))
+
+    def encode_session(self, B: int):
+        """nc_session_create(encode): push PCM [B, 1, n] of any length as it is recorded, get the codes [B, n_codebooks, n_out] that
+        became final; the pieces concatenated are the codes of encode() on the whole clip, bit for bit."""
+        from .session import Session
+        return Session(self, False, B, 0)
+
     # ---- Dia <-> DAC glue (SURVEY 8f N3) -----------------------------------------------------------
     def decode_code_matrix(self, audio_codes):
         """Dia.Decode (Models/Dia.cs:973-981): codes [T, n_q] (or batched [B, T, n_q]) -> FromCodes -> Decode -> waveform

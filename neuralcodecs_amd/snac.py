@@ -343,6 +343,20 @@ class SNAC(_lib.ProfileMixin):
                                                         seed & 0xFFFFFFFFFFFFFFFF, pcm.ctypes.data))
         return _lib.split_packed(pcm, sizes)
 
+    # ---- incremental sessions (codes or PCM pushed as they arrive) ---------------------------------
+    def decode_session(self, B: int, n_quantizers: Optional[int] = None):
+        """nc_session_create(decode): push the code levels of the next frames (a multiple of align, each level at its own rate) with
+        their noise blocks, get the PCM that became final; the pieces concatenated are decode() on the whole sequence with the noise
+        concatenated along time, bit for bit.  Without noise every push draws its own from the session's seed and the frame position,
+        which is not the draw of decode(noise=None, seed).  n_quantizers is ignored: SNAC reads every level."""
+        from .session import Session
+        return Session(self, True, B, 0)
+
+    def encode_session(self, B: int):
+        """nc_session_create(encode): push PCM [B, 1, n] of any length, get the code levels of the frames that became final."""
+        from .session import Session
+        return Session(self, False, B, 0)
+
     def decode_array(self, codes: Sequence, noise=None, seed: int = 0) -> np.ndarray:
         """SNAC.Decode(List<float[]>) (SNAC.cs:173-192)."""
         if codes is None:

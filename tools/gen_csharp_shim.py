@@ -28,7 +28,7 @@ OUT = os.path.join(ROOT, "bindings", "csharp")
 
 SCALARS = {"int": "int", "int32_t": "int", "int64_t": "long", "uint64_t": "ulong", "uint32_t": "uint", "size_t": "nuint", "float": "float", "double": "double",
            "int16_t": "short", "uint8_t": "byte", "nc_status": "NcStatus"}
-OPAQUE = {"nc_codec", "nc_group"}
+OPAQUE = {"nc_codec", "nc_group", "nc_session"}
 
 
 def strip_comments(src):
@@ -290,6 +290,7 @@ def integration_tables():
                 cites.setdefault((cm.group(1), re.sub(r"\s+", "", cm.group(2))), cm.group(3))
         ctor = re.search(r"public " + cls + r"\((.*?)\).*//\s*(Models/[\w./]+:[\d\-,]+)", raw)
         cbody = raw[ctor.end():]
+        cbody = cbody[:cbody.index("\n    }")]                   # the constructor's own body: other members create sessions
         out.append(f"**`{cls}`** (`bindings/csharp/{fname}`)")
         out.append("")
         out.append("| Managed member (reference signature) | reference | C ABI calls |")
