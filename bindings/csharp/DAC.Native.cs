@@ -240,6 +240,20 @@ public sealed unsafe class DACNative : INeuralCodec
         return new NcSession(s, batch * _config.NumCodebooks);
     }
 
+    /// <summary>slots independent decode streams stepped together (NcSessionPool.StepCodes): every slot as a DecodeSession(1, nQuantizers).</summary>
+    public NcSessionPool DecodePool(int slots, int? nQuantizers = null)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_pool_create(_h, 1, slots, nQuantizers ?? 0, out IntPtr p));
+        return new NcSessionPool(p, 1);
+    }
+
+    /// <summary>slots independent encode streams stepped together (NcSessionPool.StepAudio): every slot as an EncodeSession(1).</summary>
+    public NcSessionPool EncodePool(int slots)
+    {
+        NcMi355x.Check(NcMi355x.nc_session_pool_create(_h, 0, slots, 0, out IntPtr p));
+        return new NcSessionPool(p, _config.NumCodebooks);
+    }
+
     public void Dispose()                                                           // Models/DAC.cs:329-338
     {
         if (_h != IntPtr.Zero) { NcMi355x.nc_codec_destroy(_h); _h = IntPtr.Zero; }

@@ -1,7 +1,8 @@
 // Factories for the native models, shaped like the reference's NeuralCodecs.Create{SNAC,DAC,Encodec}Async (NeuralCodecs.Torch/
 // NeuralCodecs.cs:38-80: same parameter lists; the reference class is `public static partial class NeuralCodecs`, so these members
 // join it), the tensor <-> host-array marshalling the *Native models use at their TorchSharp-typed API surface, and NcSession, the
-// incremental session DACNative / SNACNative hand out (DecodeSession / EncodeSession).
+// incremental session DACNative / SNACNative hand out (DecodeSession / EncodeSession), and NcSessionPool, the pool of independent streams
+// they hand out (DecodePool / EncodePool).
 // `path` names an NCWB weight blob (tools/convert_checkpoint.py converts HF safetensors / Descript .pth / SNAC torch files).
 using System;
 using System.IO;
@@ -172,4 +173,75 @@ public sealed unsafe class NcSession : IDisposable
     }
 
     ~NcSession() { if (_s != IntPtr.Zero) NcMi355x.nc_session_destroy(_s); }
+}
+
+/// <summary>A session pool on a DAC or SNAC model (nc_session_pool_*, include/nc_mi355x.h "session pool"): independent streams in slots,
+/// any subset of them advanced by one Step, each by its own amount; every slot returns what a single-row NcSession returns for the same
+/// pushes, bit for bit.  Host arrays, synchronous.  The model must outlive its pools.</summary>
+public sealed unsafe class NcSessionPool : IDisposable
+{
+    private IntPtr _p;
+    private readonly int _outRows;          // rows of a slot's output: 1 (PCM, SNAC codes) or the codebooks (DAC codes)
+
+    internal NcSessionPool(IntPtr pool, int outRows) { _p = pool; _outRows = outRows; }
+
+    /// <summary>Frames the slot has pushed and not yet emitted.</summary>
+    public long Pending(int slot)
+    {
+        long n;
+        NcMi355x.Check(NcMi355x.nc_session_pool_pending(_p, slot, &n));
+        return n;
+    }
+
+    /// <summary>After a reset the slot is as new: its next push starts another clip.</summary>
+    public void Reset(int slot) => NcMi355x.Check(NcMi355x.nc_session_pool_reset_slot(_p, slot));
+
+    /// <summary>Seed of the noise the slot of a SNAC decode pool draws when a step carries none: as NcSession.SetSeed for that stream.</summary>
+    public void SetSeed(int slot, ulong seed) => NcMi355x.Check(NcMi355x.nc_session_pool_set_seed(_p, slot, seed));
+
+    /// <summary>The exact outputs per row every entry of such a step would return now (nIn[i] == 0: a flush).</summary>
+    public long[] Query(int[] slots, long[] nIn)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        if (nIn.Length != slots.Length) throw new ArgumentException("one nIn per slot");
+        var nOut = new long[Math.Max(slots.Length, 1)];
+        fixed (int* ps = slots) fixed (long* pi = nIn, po = nOut)
+            NcMi355x.Check(NcMi355x.nc_session_pool_query(_p, slots.Length, ps, pi, po));
+        return nOut;
+    }
+
+    /// <summary>Decode pool: entry i pushes nIn[i] frames of slot slots[i] (0: flush); codes packed entry after entry (DAC [nQ,n]; SNAC
+    /// the levels side by side) -> PCM packed entry after entry, nOut[i] samples each.</summary>
+    public float[] StepCodes(int[] slots, long[] nIn, long[]? codesPacked, float[]? noisePacked, out long[] nOut)
+    {
+        nOut = Query(slots, nIn);
+        long cap = 0;
+        for (int i = 0; i < slots.Length; ++i) cap += _outRows * nOut[i];
+        var buf = new float[Math.Max(cap, 1)];
+        fixed (int* ps = slots) fixed (long* pi = nIn, pc = codesPacked, pn = nOut) fixed (float* pz = noisePacked, po = buf)
+            NcMi355x.Check(NcMi355x.nc_session_pool_step(_p, slots.Length, ps, pi, pc, pz, po, cap, pn));
+        return buf.AsSpan(0, (int)cap).ToArray();
+    }
+
+    /// <summary>Encode pool: entry i pushes nIn[i] samples of slot slots[i] (0: flush); PCM packed entry after entry -> codes packed entry
+    /// after entry (DAC [codebooks,nOut[i]]; SNAC the nOut[i] values of the emitted frames, levels side by side).</summary>
+    public long[] StepAudio(int[] slots, long[] nIn, float[]? pcmPacked, out long[] nOut)
+    {
+        nOut = Query(slots, nIn);
+        long cap = 0;
+        for (int i = 0; i < slots.Length; ++i) cap += _outRows * nOut[i];
+        var buf = new long[Math.Max(cap, 1)];
+        fixed (int* ps = slots) fixed (long* pi = nIn, pn = nOut, po = buf) fixed (float* pp = pcmPacked)
+            NcMi355x.Check(NcMi355x.nc_session_pool_step(_p, slots.Length, ps, pi, pp, null, po, cap, pn));
+        return buf.AsSpan(0, (int)cap).ToArray();
+    }
+
+    public void Dispose()
+    {
+        if (_p != IntPtr.Zero) { NcMi355x.nc_session_pool_destroy(_p); _p = IntPtr.Zero; }
+        GC.SuppressFinalize(this);
+    }
+
+    ~NcSessionPool() { if (_p != IntPtr.Zero) NcMi355x.nc_session_pool_destroy(_p); }
 }

@@ -416,6 +416,43 @@ NC_API nc_status nc_session_push_dev(nc_session* s, const void* in, int64_t n_in
 NC_API nc_status nc_session_flush(nc_session* s, void* out, int64_t out_cap, int64_t* n_out);
 NC_API nc_status nc_session_flush_dev(nc_session* s, void* out, int64_t out_cap, int64_t* n_out);
 
+/* ---------------------------------------------------------------------------- session pool
+ * n_slots independent streams on one DAC or SNAC handle, one direction, stepped together (a server with many users whose streams begin,
+ * push and end at different times).  Every slot is a B = 1 session with its own schedule state; one step advances any subset of slots,
+ * each by its own amount, and every slot's output is, bit for bit, what a B = 1 nc_session returns for the same sequence of pushes
+ * (DESIGN.md 4g).  Entries whose step runs a window are grouped by the window's width in frames; a group runs as one uniform batch
+ * through the existing launch sequence (at most the handle's ragged max_windows rows per batch, nc_codec_set_ragged_window).
+ * A step is n entries (slots[i], n_in[i]): n_in > 0 pushes that many frames (decode) or samples (encode), n_in == 0 flushes the slot; a
+ * slot appears at most once.  Inputs are packed in entry order: DAC decode codes [n_q, n_in] per entry (n_q fixed at creation; 0 = all),
+ * SNAC decode the levels of the entry side by side, encode the PCM samples; a flush contributes nothing.  noise_packed (SNAC decode
+ * with NoiseBlocks): per pushing entry, stage after stage, as nc_session_push takes it for B = 1; NULL: every pushing entry draws its
+ * block from (the slot's seed, the slot's frame position) exactly as a session with that seed does.  Outputs are packed entry after
+ * entry: decode [n_out[i]] samples; DAC encode [n_codebooks, n_out[i]]; SNAC encode the n_out[i] values of the emitted frames, levels
+ * side by side.  n_out[i] is host arithmetic: nc_session_pool_query returns the exact n_out of every entry for the pool's current
+ * state, so the packed output can be sized before the step; out_cap is the capacity of out_packed in elements.  The *_dev form takes
+ * device pointers and is asynchronous on the handle's stream; the plain form takes host pointers and is synchronous.
+ * The whole call is validated before anything is launched and before any slot changes -- NC_EINVAL: a null pointer, n <= 0, a slot out
+ * of range or named twice, n_in < 0, a decode push that is not a multiple of align, a push or flush of a flushed slot (until
+ * nc_session_pool_reset_slot), a flush of a slot with nothing pushed, out_cap below the sum the query gives; NC_ESTATE without weights;
+ * NC_EUNSUPPORTED for Encodec handles.  A refused step leaves every slot as it was.  A pool BORROWS its handle: destroy it first.
+ * nc_session_pool_plan states the grouping as a host function (no handle, no device): stream i has pushed[i] / emitted[i] frames and
+ * pushes push_frames[i] more (0: flush); steps[i] is its step as nc_session_schedule reports it, group_of[i] the batch its window runs
+ * in (-1: no window), batches numbered narrowest window first; no batch has more than max_rows rows (0 = the default, 128). */
+typedef struct nc_session_pool nc_session_pool;
+NC_API nc_status nc_session_pool_plan(const nc_halo* halo, int32_t decode, int32_t n, const int64_t* pushed, const int64_t* emitted,
+                                      const int64_t* push_frames, int32_t max_rows, nc_session_step* steps, int32_t* group_of,
+                                      int32_t* n_groups);
+NC_API nc_status nc_session_pool_create(nc_codec* h, int32_t decode, int32_t n_slots, int32_t n_q, nc_session_pool** out);
+NC_API nc_status nc_session_pool_destroy(nc_session_pool* p);
+NC_API nc_status nc_session_pool_reset_slot(nc_session_pool* p, int32_t slot);
+NC_API nc_status nc_session_pool_set_seed(nc_session_pool* p, int32_t slot, uint64_t seed);
+NC_API nc_status nc_session_pool_pending(const nc_session_pool* p, int32_t slot, int64_t* frames);
+NC_API nc_status nc_session_pool_query(const nc_session_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in, int64_t* n_out);
+NC_API nc_status nc_session_pool_step(nc_session_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in, const void* in_packed,
+                                      const float* noise_packed, void* out_packed, int64_t out_cap, int64_t* n_out);
+NC_API nc_status nc_session_pool_step_dev(nc_session_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in, const void* in_packed,
+                                          const float* noise_packed, void* out_packed, int64_t out_cap, int64_t* n_out);
+
 /* -------------------------------------------------------------------------------------- Encodec
  * replaces: new Encodec(EncodecConfig)            NeuralCodecs.Torch/Models/Encodec.cs:46-90
  * Only channels / dimension / norm / causal reach SEANet in the reference (Encodec.cs:57-68, deviation D11); the other SEANet

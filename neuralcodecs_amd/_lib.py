@@ -172,7 +172,16 @@ SYMBOLS = [
     ("nc_session_push_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("nc_session_flush", C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("nc_session_flush_dev", C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
-    ("nc_encodec_create", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int, C.POINTER(_P)]),
+    ("nc_session_pool_plan", C.c_int, [C.POINTER(NcHalo), C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    ("nc_session_pool_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("nc_session_pool_destroy", C.c_int, [_P]),
+    ("nc_session_pool_reset_slot", C.c_int, [_P, C.c_int32]),
+    ("nc_session_pool_set_seed", C.c_int, [_P, C.c_int32, C.c_uint64]),
+    ("nc_session_pool_pending", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nc_session_pool_query", C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    ("nc_session_pool_step", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("nc_session_pool_step_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("nc_encodec_create", C.c_int,[C.POINTER(NcEncodecConfig), C.c_int, C.POINTER(_P)]),
     ("nc_encodec_set_bandwidth", C.c_int, [_P, C.c_float]),
     ("nc_encodec_query", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32,
                                    C.POINTER(C.c_int64)]),

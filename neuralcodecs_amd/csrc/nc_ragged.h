@@ -10,6 +10,8 @@
 
 namespace nc {
 
+constexpr int32_t kRaggedDefaultMaxWindows = 128;   // rows per launch batch where the handle sets none
+
 struct RgSeg { int64_t src, dst, n, fill; };   // elements
 
 struct RgTables {

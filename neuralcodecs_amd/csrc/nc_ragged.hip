@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void ragged_scatter_i64(const RgSeg* __restric
 // ---- planner ---------------------------------------------------------------------------------------------------------------------
 // the best measured pairs of profiles/ragged_bench.json
 constexpr int64_t kDefaultKeptDac = 128, kDefaultKeptSnac = 256;
-constexpr int32_t kDefaultMaxWindows = 128;
+constexpr int32_t kDefaultMaxWindows = kRaggedDefaultMaxWindows;
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

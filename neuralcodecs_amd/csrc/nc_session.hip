@@ -8,6 +8,8 @@
 // left edge unless that edge is frame 0 (the clip's true start) and at least hr in front of its right edge unless the step is the flush
 // (the clip's true end).  That is the premise of the chunked calls (nc_chunk.hip), so every kept output is the one-shot number.
 //
+// The schedule, the row families and the frame arithmetic of a step live in nc_session.h, shared with the session pool.
+//
 // Device work.  Two kernels, no tables: their few row families travel as kernel arguments.
 //   session_assemble  one launch builds the window rows as history followed by the pushed data (followed by +0.0f where an encode flush
 //                     pads the last hop) AND writes the next history, a suffix of the same concatenation, into the session's other
@@ -16,53 +18,14 @@
 // Both write with 16-byte stores from the first 16-byte boundary of a destination row, a scalar head in front and a scalar tail behind
 // (the idiom of ragged_gather_* / ragged_scatter_*).  Everything else a step launches is the *_dev launch sequence on the handle's
 // ck_* buffers; a process that creates no session launches what it launched before.
-#include <algorithm>
-
-#include "nc_guard.h"
+#include "nc_session.h"
 
 namespace nc {
 
 namespace {
 
-constexpr int SS_MAX_LEVELS = 8;
-
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
-template <class T>
-struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
-
-// element i of a[0, na) ++ b[0, nb) ++ zeros
-template <class T>
-__device__ __forceinline__ T cat_at(const T* __restrict__ a, int64_t na, const T* __restrict__ b, int64_t nb, int64_t i) {
-    return i < na ? a[i] : (i < na + nb ? b[i - na] : T(0));
-}
-
-// d[j] = (a ++ b ++ zeros)[s0 + j] for j in [0, total): reads stay inside a[0, na) and b[0, nb), writes inside d[0, total)
-template <class T>
-__device__ __forceinline__ void concat_copy(const T* __restrict__ a, int64_t na, const T* __restrict__ b, int64_t nb, int64_t s0,
-                                            T* __restrict__ d, int64_t total) {
-    constexpr int V = 16 / sizeof(T);
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(d) & 15) / sizeof(T));
-    const int64_t head = mis ? (total < V - mis ? total : V - mis) : 0;
-    const int64_t nvec = (total - head) / V, tail0 = head + nvec * V;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    if (tid < head) d[tid] = cat_at(a, na, b, nb, s0 + tid);
-    for (int64_t v = tid; v < nvec; v += stride) {
-        const int64_t base = head + v * V, i = s0 + base;
-        const T* p = nullptr;   // the vector lies inside one of the two pieces
-        if (i + V <= na) p = a + i;
-        else if (i >= na && i + V <= na + nb) p = b + (i - na);
-        Vec16<T> x;
-        if (p && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            x = *reinterpret_cast<const Vec16<T>*>(p);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) x.v[j] = cat_at(a, na, b, nb, i + j);
-        }
-        *reinterpret_cast<Vec16<T>*>(d + base) = x;
-    }
-    if (tid < total - tail0) d[tail0 + tid] = cat_at(a, na, b, nb, s0 + tail0 + tid);
-}
-
+// (concat_copy, the copy both kernels are made of: nc_session.h)
 // One row family of an assembly launch (a code level, a noise stage, the PCM): `rows` rows, each hist_n resident elements followed by
 // new_n pushed ones.  The window row takes the first win_n elements of that concatenation (+0 behind its end); the next history is
 // its elements [next_off, hist_n + new_n).  History rows are dense; the pushed data and the window have a base and a row pitch.
@@ -117,60 +80,7 @@ __global__ __launch_bounds__(256) void session_emit_i64(SsEmitArgs a, const int6
     emit_body<int64_t>(a, src, dst);
 }
 
-// ---- schedule --------------------------------------------------------------------------------------------------------------------
-struct SsStep { int64_t w0, w1, k0, k1, h0n; };   // window, kept frames, first resident frame afterwards
-
-SsStep step_push(int64_t hl, int64_t hr, int64_t align, int64_t E, int64_t P1) {
-    const int64_t h0 = std::max<int64_t>(0, E - hl), e1 = P1 > hr ? (P1 - hr) / align * align : 0;
-    SsStep s;
-    s.k0 = E; s.k1 = std::max(E, e1);
-    s.w0 = h0; s.w1 = s.k1 > s.k0 ? P1 : h0;
-    s.h0n = std::max<int64_t>(0, s.k1 - hl);
-    return s;
-}
-SsStep step_flush(int64_t hl, int64_t E, int64_t P1) { return {std::max<int64_t>(0, E - hl), P1, E, P1, P1}; }
-
-void halos_of(const nc_halo& h, bool decode, int64_t& hl, int64_t& hr) {   // as make_plan (nc_chunk.hip)
-    hl = decode ? h.dec_right : h.enc_right;
-    hr = decode ? h.dec_left : h.enc_left;
-    if (h.align <= 0 || hl < 0 || hr < 0 || hl % h.align != 0 || hr % h.align != 0) fail(NC_EINVAL, "halo: align must be positive and divide the halos");
-}
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// ---- row families ----------------------------------------------------------------------------------------------------------------
-// Level i of a family holds u * mul[i] / div[i] elements per row for u units (frames; samples for the PCM).  Caller-side tensors and the
-// window keep the levels of a row side by side (row_major: SNAC codes) or level after level (DAC codes, PCM, noise stages); the history
-// is always level after level with dense rows.
-struct Family {
-    int nl = 1;
-    int64_t mul[SS_MAX_LEVELS] = {1}, div[SS_MAX_LEVELS] = {1};
-    bool row_major = false;
-    int64_t len(int i, int64_t u) const { return u * mul[i] / div[i]; }
-    int64_t total(int64_t u) const {
-        int64_t n = 0;
-        for (int i = 0; i < nl; ++i) n += len(i, u);
-        return n;
-    }
-};
-struct Lay { int64_t len[SS_MAX_LEVELS], base[SS_MAX_LEVELS], pitch[SS_MAX_LEVELS]; };
-Lay lay_of(const Family& f, int64_t u, int64_t rows, bool row_major) {
-    Lay l{};
-    int64_t off = 0;
-    for (int i = 0; i < f.nl; ++i) {
-        l.len[i] = f.len(i, u);
-        l.base[i] = row_major ? off : rows * off;
-        l.pitch[i] = row_major ? f.total(u) : l.len[i];
-        off += l.len[i];
-    }
-    return l;
-}
-
-unsigned grid_x(int64_t longest, size_t elt) {
-    const int64_t per_block = 256 * (16 / (int64_t)elt);
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div(longest, per_block)), 4096);
-}
-
+// ---- launches (schedule and row families: nc_session.h) ---------------------------------------------------------------------------
 // hist (hist_u units per row) ++ nw (new_u) -> win (win_u units per row; null: no window) and next (the units from next_off_u on)
 template <class T>
 void assemble(Codec& m, void (*kernel)(SsArgs, const T*, const T*, T*, T*), const Family& f, int rows, int64_t hist_u, int64_t new_u,
@@ -194,7 +104,7 @@ void assemble(Codec& m, void (*kernel)(SsArgs, const T*, const T*, T*, T*), cons
     }
     if (longest <= 0) return;
     ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
-    hipLaunchKernelGGL(kernel, dim3(grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)(2 * f.nl)), dim3(256), 0, m.stream, a, hist, nw, win, next);
+    hipLaunchKernelGGL(kernel, dim3(ss_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)(2 * f.nl)), dim3(256), 0, m.stream, a, hist, nw, win, next);
     NC_HIP(hipGetLastError());
 }
 
@@ -211,7 +121,7 @@ void emit(Codec& m, void (*kernel)(SsEmitArgs, const T*, T*), int nl, int rows, 
     }
     if (longest <= 0) return;
     ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
-    hipLaunchKernelGGL(kernel, dim3(grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)nl), dim3(256), 0, m.stream, a, src, dst);
+    hipLaunchKernelGGL(kernel, dim3(ss_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)nl), dim3(256), 0, m.stream, a, src, dst);
     NC_HIP(hipGetLastError());
 }
 
@@ -221,87 +131,108 @@ void emit(Codec& m, void (*kernel)(SsEmitArgs, const T*, T*), int nl, int rows, 
 
 using namespace nc;
 
-// the opaque session of the C ABI
-struct nc_session {
-    nc_codec* h = nullptr;
-    bool dac = true, decode = true, with_noise = false;
-    int B = 1, nq = 0, n_codebooks = 0;
-    int64_t hl = 0, hr = 0, align = 1;
-    int64_t hop = 1;              // input samples per frame (encode)
-    int64_t H = 1;                // output samples per frame (decode)
-    Family codes;                 // the code levels (SNAC) / the one code row family (DAC), in frames
-    Family main, noise;           // what is pushed: the codes (decode) or the PCM (encode); the NoiseBlock inputs
+// the opaque session of the C ABI: what the stream is (SessionGeom), where it stands (SessionState), and its device buffers
+struct nc_session : SessionGeom, SessionState {
     uint64_t seed = 0;
-    // state: frames pushed and emitted, samples pushed (encode), first resident frame, which history buffer is current
-    int64_t P = 0, E = 0, S = 0, h0 = 0;
-    bool flushed = false;
-    int cur = 0;
     DevBuf hist[2], nhist[2];     // resident history of the main tensor and of the noise, alternating
     DevBuf in_stage, nz_stage, out_stage;   // host-pointer calls and drawn noise
-
-    int rows() const { return dac && decode ? B * nq : B; }
-    size_t elt() const { return decode ? 8 : 4; }
-    int64_t unit() const { return hop * align; }
-    // frames a push of n_in (0: the flush) can emit at most, whatever the state
-    int64_t cap_frames(int64_t n_in) const {
-        if (decode) return n_in > 0 ? n_in : hr + align;
-        return n_in > 0 ? (n_in / unit() + 1) * align : hr + 2 * align;
-    }
-    int64_t out_elems(int64_t frames) const {   // per row
-        if (decode) return frames * H;
-        return codes.total(frames);   // DAC: per codebook row; SNAC: all levels of a row
-    }
 };
 
-namespace {
+namespace nc {
 
-void reset(nc_session& s) {
-    s.P = s.E = s.S = s.h0 = 0;
-    s.flushed = false;
-    s.cur = 0;
+void session_check(const SessionGeom& g, const SessionState& s, int64_t n_in, bool flush) {
+    if (s.flushed) fail(NC_EINVAL, "the session has been flushed: nc_session_reset starts the next clip");
+    if (!flush) {
+        if (n_in <= 0 || n_in > ((int64_t)1 << 30)) fail(NC_EINVAL, "n_in must be in 1..2^30");
+        if (g.decode && n_in % g.align != 0) fail(NC_EINVAL, "a push of %lld frames is not a multiple of %lld", (long long)n_in, (long long)g.align);
+    } else if ((g.decode ? s.P : s.S) <= 0) {
+        fail(NC_EINVAL, "nothing has been pushed");
+    }
 }
 
-uint64_t mix_seed(uint64_t seed, int64_t frame) { return seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)frame + 1)); }
+void session_geom(nc_codec* h, bool decode, int B, int n_q, SessionGeom& g) {
+    codec_of(h);
+    if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles have no sessions: 48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context");
+    if (B <= 0 || n_q < 0) fail(NC_EINVAL, "B must be positive and n_q must not be negative");
+    g.h = h; g.dac = h->kind == DacModel::kKind; g.decode = decode; g.B = B;
+    nc_halo halo{};
+    int nd = 0;
+    const int32_t* dr = nullptr;
+    if (g.dac) {
+        const DacModel& m = as<DacModel>(h);
+        if (n_q > m.cfg.n_codebooks) fail(NC_EINVAL, "n_q = %d exceeds the model's %d codebooks", n_q, m.cfg.n_codebooks);
+        if (nc_dac_halo(&m.cfg, &halo) != NC_OK) fail(NC_EINVAL, "%s", get_last_error());
+        g.n_codebooks = m.cfg.n_codebooks;
+        g.nq = n_q > 0 ? n_q : m.cfg.n_codebooks;
+        g.hop = m.hop;
+        nd = m.cfg.n_decoder_rates; dr = m.cfg.decoder_rates;
+        g.codes.row_major = false;   // [B, n_q, frames]: one family of B * n_q rows
+    } else {
+        const SnacModel& m = as<SnacModel>(h);
+        if (nc_snac_halo(&m.cfg, &halo) != NC_OK) fail(NC_EINVAL, "%s", get_last_error());
+        if (m.pad_to != (int64_t)m.hop * halo.align) fail(NC_ESTATE, "internal: SNAC pads to %lld samples, the halo aligns to %lld frames", (long long)m.pad_to, (long long)halo.align);
+        g.hop = m.hop;
+        nd = m.cfg.n_decoder_rates; dr = m.cfg.decoder_rates;
+        g.with_noise = g.decode && m.cfg.noise != 0;
+        g.codes.nl = m.cfg.n_vq_strides;
+        for (int i = 0; i < g.codes.nl; ++i) { g.codes.mul[i] = 1; g.codes.div[i] = m.cfg.vq_strides[i]; }
+        g.codes.row_major = true;    // the levels of a row side by side
+        g.noise.nl = nd;
+        int64_t S = 1;
+        for (int i = 0; i < nd; ++i) { S *= dr[i]; g.noise.mul[i] = S; g.noise.div[i] = 1; }
+    }
+    for (int i = 0; i < nd; ++i) g.H *= dr[i];
+    session_halos(halo, g.decode, g.hl, g.hr);
+    g.align = halo.align;
+    if (g.decode) g.main = g.codes;   // an encode session's main family is the PCM: one level of samples (the default Family)
+    if ((int64_t)g.rows() > 65535 || (int64_t)B * std::max(1, g.n_codebooks) > 65535) fail(NC_EINVAL, "B = %d rows exceed one launch grid", B);
+}
+
+SessionMove session_move(const SessionGeom& g, const SessionState& s, int64_t n_in, bool flush) {
+    Codec& m = codec_of(g.h);
+    SessionMove v{};
+    v.new_u = flush ? 0 : n_in;                                               // pushed units: frames (decode) or samples (encode)
+    v.S1 = s.S + (g.decode ? 0 : v.new_u);
+    if (g.decode) v.P1 = s.P + v.new_u;
+    else v.P1 = flush ? ss_ceil_div(v.S1, g.unit()) * g.align : v.S1 / g.unit() * g.align;   // the flush pads as the codec's own Preprocess does
+    v.st = flush ? step_flush(g.hl, s.E, v.P1) : step_push(g.hl, g.hr, g.align, s.E, v.P1);
+    if (v.st.w0 != s.h0) fail(NC_ESTATE, "internal: session history starts at frame %lld, the window at %lld", (long long)s.h0, (long long)v.st.w0);
+    v.run = v.st.k1 > v.st.k0;
+    v.Wf = v.P1 - s.h0; v.ke = v.st.k1 - v.st.k0; v.k_off = v.st.k0 - s.h0;
+    const int64_t per = g.decode ? 1 : g.hop;                                 // units per frame
+    v.hist_u = (g.decode ? s.P : s.S) - s.h0 * per;
+    v.win_u = v.run ? v.Wf * per : 0;
+    v.next_off_u = std::min((v.st.h0n - s.h0) * per, v.hist_u + v.new_u);
+    v.next_u = v.hist_u + v.new_u - v.next_off_u;
+    if (v.run && g.decode) {
+        v.Lw = g.dac ? static_cast<DacModel&>(m).decoded_len(v.Wf) : static_cast<SnacModel&>(m).decoded_len(v.Wf);
+        v.nout = flush ? v.Lw - v.k_off * g.H : v.ke * g.H;
+        if (v.nout <= 0 || v.k_off * g.H + v.nout > v.Lw) fail(NC_ESTATE, "internal: decoded window of %lld samples does not cover its kept frames", (long long)v.Lw);
+    } else if (v.run) {
+        v.nout = g.out_elems(v.ke);
+    }
+    return v;
+}
+
+}  // namespace nc
+
+namespace {
 
 void step(nc_session& s, bool host, const void* in, int64_t n_in, const float* noise, void* out, int64_t out_cap, int64_t* n_out, bool flush) {
     Codec& m = codec_of(s.h);
     if (!out || !n_out) fail(NC_EINVAL, "out and n_out must not be null");
-    if (s.flushed) fail(NC_EINVAL, "the session has been flushed: nc_session_reset starts the next clip");
-    if (!flush) {
-        if (!in) fail(NC_EINVAL, "in must not be null");
-        if (n_in <= 0 || n_in > ((int64_t)1 << 30)) fail(NC_EINVAL, "n_in must be in 1..2^30");
-        if (s.decode && n_in % s.align != 0) fail(NC_EINVAL, "a push of %lld frames is not a multiple of %lld", (long long)n_in, (long long)s.align);
-    } else if ((s.decode ? s.P : s.S) <= 0) {
-        fail(NC_EINVAL, "nothing has been pushed");
-    }
+    if (!flush && !in && !s.flushed) fail(NC_EINVAL, "in must not be null");
+    session_check(s, s, n_in, flush);
     if (!m.loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
     if (out_cap < s.out_elems(s.cap_frames(flush ? 0 : n_in)))
         fail(NC_EINVAL, "out_cap %lld is below what nc_session_query asks for (%lld)", (long long)out_cap, (long long)s.out_elems(s.cap_frames(flush ? 0 : n_in)));
 
     // ---- the step, on frame counts alone
-    const int64_t new_u = flush ? 0 : n_in;                                   // pushed units: frames (decode) or samples (encode)
-    const int64_t S1 = s.S + (s.decode ? 0 : new_u);
-    int64_t P1;
-    if (s.decode) P1 = s.P + new_u;
-    else P1 = flush ? ceil_div(S1, s.unit()) * s.align : S1 / s.unit() * s.align;   // the flush pads as the codec's own Preprocess does
-    const SsStep st = flush ? step_flush(s.hl, s.E, P1) : step_push(s.hl, s.hr, s.align, s.E, P1);
-    if (st.w0 != s.h0) fail(NC_ESTATE, "internal: session history starts at frame %lld, the window at %lld", (long long)s.h0, (long long)st.w0);
-    const bool run = st.k1 > st.k0;
-    const int64_t Wf = P1 - s.h0, ke = st.k1 - st.k0, k_off = st.k0 - s.h0;
-    const int64_t per = s.decode ? 1 : s.hop;                                 // units per frame
-    const int64_t hist_u = (s.decode ? s.P : s.S) - s.h0 * per;
-    const int64_t win_u = run ? Wf * per : 0;
-    const int64_t next_off_u = std::min((st.h0n - s.h0) * per, hist_u + new_u);
-    const int64_t next_u = hist_u + new_u - next_off_u;
+    const SessionMove mv = session_move(s, s, n_in, flush);
+    const bool run = mv.run;
+    const int64_t Wf = mv.Wf, ke = mv.ke, k_off = mv.k_off, hist_u = mv.hist_u, new_u = mv.new_u, win_u = mv.win_u, next_off_u = mv.next_off_u,
+                  next_u = mv.next_u, nout = mv.nout, Lw = mv.Lw;
     const int rows = s.rows();
-    int64_t nout = 0, Lw = 0;
-    if (run && s.decode) {
-        Lw = s.dac ? static_cast<DacModel&>(m).decoded_len(Wf) : static_cast<SnacModel&>(m).decoded_len(Wf);
-        nout = flush ? Lw - k_off * s.H : ke * s.H;
-        if (nout <= 0 || k_off * s.H + nout > Lw) fail(NC_ESTATE, "internal: decoded window of %lld samples does not cover its kept frames", (long long)Lw);
-    } else if (run) {
-        nout = s.out_elems(ke);
-    }
     if (nout > out_cap) fail(NC_ESTATE, "internal: a step of %lld outputs per row exceeds the queried capacity", (long long)nout);
 
     // ---- launches
@@ -397,8 +328,7 @@ void step(nc_session& s, bool host, const void* in, int64_t n_in, const float* n
         }
     }
     // ---- the session moves on only once everything is queued
-    s.P = P1; s.S = S1; s.E = st.k1; s.h0 = st.h0n; s.cur = nxt;
-    s.flushed = flush;
+    session_commit(s, mv, flush);
     *n_out = nout;
 }
 
@@ -429,7 +359,7 @@ nc_status nc_session_schedule(const nc_halo* halo, int32_t decode, int32_t n_pus
         if (n_pushes < 0 || (n_pushes > 0 && !push_frames)) fail(NC_EINVAL, "n_pushes must not be negative and push_frames must not be null");
         if (n_pushes == 0) fail(NC_EINVAL, flush ? "nothing to flush" : "no pushes");
         int64_t hl, hr;
-        halos_of(*halo, decode != 0, hl, hr);
+        session_halos(*halo, decode != 0, hl, hr);
         for (int i = 0; i < n_pushes; ++i)
             if (push_frames[i] <= 0 || push_frames[i] % halo->align != 0 || push_frames[i] > ((int64_t)1 << 40))
                 fail(NC_EINVAL, "push %d: %lld frames is not a positive multiple of %lld", i, (long long)push_frames[i], (long long)halo->align);
@@ -448,42 +378,8 @@ nc_status nc_session_create(nc_codec* h, int32_t decode, int32_t B, int32_t n_q,
     return guard([&] {
         if (!out) fail(NC_EINVAL, "out must not be null");
         *out = nullptr;
-        codec_of(h);
-        if (h->kind == EncodecModel::kKind) fail(NC_EUNSUPPORTED, "Encodec handles have no sessions: 48 kHz is segmented per second already, the 24 kHz LSTM has unbounded context");
-        if (B <= 0 || n_q < 0) fail(NC_EINVAL, "B must be positive and n_q must not be negative");
         std::unique_ptr<nc_session> s(new nc_session);
-        s->h = h; s->dac = h->kind == DacModel::kKind; s->decode = decode != 0; s->B = B;
-        nc_halo halo{};
-        int nd = 0;
-        const int32_t* dr = nullptr;
-        if (s->dac) {
-            const DacModel& m = as<DacModel>(h);
-            if (n_q > m.cfg.n_codebooks) fail(NC_EINVAL, "n_q = %d exceeds the model's %d codebooks", n_q, m.cfg.n_codebooks);
-            if (nc_dac_halo(&m.cfg, &halo) != NC_OK) fail(NC_EINVAL, "%s", get_last_error());
-            s->n_codebooks = m.cfg.n_codebooks;
-            s->nq = n_q > 0 ? n_q : m.cfg.n_codebooks;
-            s->hop = m.hop;
-            nd = m.cfg.n_decoder_rates; dr = m.cfg.decoder_rates;
-            s->codes.row_major = false;   // [B, n_q, frames]: one family of B * n_q rows
-        } else {
-            const SnacModel& m = as<SnacModel>(h);
-            if (nc_snac_halo(&m.cfg, &halo) != NC_OK) fail(NC_EINVAL, "%s", get_last_error());
-            if (m.pad_to != (int64_t)m.hop * halo.align) fail(NC_ESTATE, "internal: SNAC pads to %lld samples, the halo aligns to %lld frames", (long long)m.pad_to, (long long)halo.align);
-            s->hop = m.hop;
-            nd = m.cfg.n_decoder_rates; dr = m.cfg.decoder_rates;
-            s->with_noise = s->decode && m.cfg.noise != 0;
-            s->codes.nl = m.cfg.n_vq_strides;
-            for (int i = 0; i < s->codes.nl; ++i) { s->codes.mul[i] = 1; s->codes.div[i] = m.cfg.vq_strides[i]; }
-            s->codes.row_major = true;    // the levels of a row side by side
-            s->noise.nl = nd;
-            int64_t S = 1;
-            for (int i = 0; i < nd; ++i) { S *= dr[i]; s->noise.mul[i] = S; s->noise.div[i] = 1; }
-        }
-        for (int i = 0; i < nd; ++i) s->H *= dr[i];
-        halos_of(halo, s->decode, s->hl, s->hr);
-        s->align = halo.align;
-        if (s->decode) s->main = s->codes;   // an encode session's main family is the PCM: one level of samples (the default Family)
-        if ((int64_t)s->rows() > 65535 || (int64_t)B * std::max(1, s->n_codebooks) > 65535) fail(NC_EINVAL, "B = %d rows exceed one launch grid", B);
+        session_geom(h, decode != 0, B, n_q, *s);
         *out = s.release();
     });
 }
@@ -493,7 +389,7 @@ nc_status nc_session_destroy(nc_session* s) {
 }
 
 nc_status nc_session_reset(nc_session* s) {
-    return guard([&] { reset(session_of(s)); });
+    return guard([&] { static_cast<SessionState&>(session_of(s)) = SessionState{}; });
 }
 
 nc_status nc_session_set_seed(nc_session* s, uint64_t seed) {

@@ -303,6 +303,19 @@ class DAC(_lib.ProfileMixin):
         from .session import Session
         return Session(self, False, B, 0)
 
+    # ---- session pools (many independent streams stepped in one batch) ------------------------------
+    def decode_pool(self, n_slots: int, n_q: Optional[int] = None):
+        """nc_session_pool_create(decode): n_slots independent decode streams reading n_q codebooks; one step() advances any subset of
+        them, each by its own amount, and every slot returns what a B = 1 decode_session returns for the same pushes, bit for bit
+        (neuralcodecs_amd/session.py)."""
+        from .session import SessionPool
+        return SessionPool(self, True, n_slots, self._nq(n_q))
+
+    def encode_pool(self, n_slots: int):
+        """nc_session_pool_create(encode): n_slots independent encode streams (SessionPool)."""
+        from .session import SessionPool
+        return SessionPool(self, False, n_slots, 0)
+
     # ---- Dia <-> DAC glue (SURVEY 8f N3) -----------------------------------------------------------
     def decode_code_matrix(self, audio_codes):
         """Dia.Decode (Models/Dia.cs:973-981): codes [T, n_q] (or batched [B, T, n_q]) -> FromCodes -> Decode -> waveform

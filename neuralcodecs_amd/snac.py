@@ -357,6 +357,19 @@ class SNAC(_lib.ProfileMixin):
         from .session import Session
         return Session(self, False, B, 0)
 
+    # ---- session pools (many independent streams stepped in one batch) ------------------------------
+    def decode_pool(self, n_slots: int, n_q: Optional[int] = None):
+        """nc_session_pool_create(decode): n_slots independent decode streams; one step() advances any subset of them, each by its own
+        amount, and every slot returns what a B = 1 decode_session returns for the same pushes, bit for bit (neuralcodecs_amd/session.py).
+        n_q is ignored: SNAC reads every level."""
+        from .session import SessionPool
+        return SessionPool(self, True, n_slots, 0)
+
+    def encode_pool(self, n_slots: int):
+        """nc_session_pool_create(encode): n_slots independent encode streams (SessionPool)."""
+        from .session import SessionPool
+        return SessionPool(self, False, n_slots, 0)
+
     def decode_array(self, codes: Sequence, noise=None, seed: int = 0) -> np.ndarray:
         """SNAC.Decode(List<float[]>) (SNAC.cs:173-192)."""
         if codes is None:
