@@ -101,23 +101,18 @@ def dw_oracle(xin, w, b, pad, dil):
     return np.ascontiguousarray(c_oracle.conv1d(xp, w.reshape(C, 1, K), b, 1, 0, dil, groups=C)[:, :, :T])
 
 
-def _dw_case(rng, B, C, T, K, pad, dil, s_in, s_out, bias):
-    x = _rand(rng, B, C, T, scale=1.5)
-    w = _rand(rng, C, K, scale=1.0 / np.sqrt(K)); b = _rand(rng, C, scale=0.1) if bias else None
-    ai = _alpha(rng, C) if s_in else None
-    ao = _alpha(rng, C) if s_out else None
-    xin = c_oracle.snake(x, ai) if s_in else x
+def dw_judge(got, x, w, b, pad, dil, ai, ao, what):
+    """A depthwise result (the engine's, or on the CPU the oracle's own) for x, w, b and the Snakes ai / ao (None: no Snake): equal to the
+    oracle's composition bit for bit, and within the binary64 bound: K taps + bias on the oracle-activated input, then the Snake table
+    (|Snake'| <= 2 carries the linear error through).  Returns the largest error / allowed."""
+    xin = c_oracle.snake(x, ai) if ai is not None else x
     lin32 = dw_oracle(xin, w, b, pad, dil)
-    want = c_oracle.snake(lin32, ao) if s_out else lin32
-    got = ops.dwconv1d(x, w, b, pad, dil, alpha_in=ai, alpha_out=ao)
-    what = f"B={B} C={C} T={T} K={K} pad={pad} dil={dil} snake_in={s_in} snake_out={s_out} bias={bias} [{dw_form(K, pad, dil, T)}]"
-    _check_forms([dw_form(K, pad, dil, T)], what)
+    want = c_oracle.snake(lin32, ao) if ao is not None else lin32
     assert got.shape == want.shape
     assert np.array_equal(got, want), f"{what}: max abs diff {np.abs(got - want).max()}"
-    # binary64: K taps + bias on the oracle-activated input, then the Snake table (|Snake'| <= 2 carries the linear error through)
     w64 = ref64.dwconv_first_t(xin, w, b, pad, dil)
     bound = ref64.dwconv_first_t_bound(xin, w, b, pad, dil)
-    if s_out:
+    if ao is not None:
         assert np.all(np.abs(lin32.astype(np.float64) - w64) <= bound), what
         allowed = 2.0 * bound + snake_tol(lin32, ao)
         w64 = ref64.snake(w64, ao)
@@ -126,6 +121,18 @@ def _dw_case(rng, B, C, T, K, pad, dil, s_in, s_out, bias):
     err = np.abs(got.astype(np.float64) - w64)
     assert np.all(err <= allowed), f"{what}: {float((err / np.maximum(allowed, 1e-300)).max()):.3g} x the allowed error"
     return float((err / np.maximum(allowed, 1e-300)).max())
+
+
+def _dw_case(rng, B, C, T, K, pad, dil, s_in, s_out, bias):
+    """One hook call on seeded inputs, judged by dw_judge (which tests/test_activation_range_gpu.py calls with values of its own)."""
+    x = _rand(rng, B, C, T, scale=1.5)
+    w = _rand(rng, C, K, scale=1.0 / np.sqrt(K)); b = _rand(rng, C, scale=0.1) if bias else None
+    ai = _alpha(rng, C) if s_in else None
+    ao = _alpha(rng, C) if s_out else None
+    got = ops.dwconv1d(x, w, b, pad, dil, alpha_in=ai, alpha_out=ao)
+    what = f"B={B} C={C} T={T} K={K} pad={pad} dil={dil} snake_in={s_in} snake_out={s_out} bias={bias} [{dw_form(K, pad, dil, T)}]"
+    _check_forms([dw_form(K, pad, dil, T)], what)
+    return dw_judge(got, x, w, b, pad, dil, ai, ao, what)
 
 
 @pytest.mark.parametrize("T", DW_T)
@@ -275,13 +282,16 @@ def test_avg_pool_strides_and_ragged_lengths(s):
 
 
 # ---------------------------------------------------------------------------------------------------------------- SNAC unit
-def _unit_inputs(rng, B, C, T, with_b1, with_next):
-    x = _rand(rng, B, C, T, scale=1.5)
-    a1, a2 = _alpha(rng, C), _alpha(rng, C)
+def _unit_inputs(rng, B, C, T, with_b1, with_next, x=None, a1=None):
+    """Seeded inputs of one unit; x, a1: values to use in place of the drawn ones (tests/test_activation_range_gpu.py, which chooses a2
+    and the next unit's alpha from the oracle's results afterwards; the draws are made all the same)."""
+    xd = _rand(rng, B, C, T, scale=1.5)
+    a1d, a2d = _alpha(rng, C), _alpha(rng, C)
     w7 = _rand(rng, C, 7, scale=1.0 / np.sqrt(7)); b7 = _rand(rng, C, scale=0.1)
     w1 = _rand(rng, C, C, scale=1.0 / np.sqrt(C)); b1 = _rand(rng, C, scale=0.1) if with_b1 else None
-    an = _alpha(rng, C) if with_next else None
-    return x, w7, b7, a1, a2, w1, b1, an
+    and_ = _alpha(rng, C) if with_next else None
+    pick = lambda given, drawn: drawn if given is None else given
+    return pick(x, xd), w7, b7, pick(a1, a1d), a2d, w1, b1, and_
 
 
 def _unit_oracle(x, w7, b7, a1, a2, w1, b1, an, dil):

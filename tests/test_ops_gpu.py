@@ -287,8 +287,10 @@ def one_clip(sp, i):
 
 @pytest.mark.parametrize("C,res,snake", STREAMING_CASES)
 def test_pointwise_streaming_variant_bit_exact(C, res, snake):
-    """Long narrow rows (>= 2048 column tiles): the tile-per-workgroup pointwise kernel.  Bit equality over all 8 clips; the binary64
-    bound on the last clip (8 x 192 x 66 000 in binary64 twice over is most of this file's time otherwise)."""
+    """Long narrow rows (>= 2048 column tiles) on the pointwise kernel.  (These were once a separate tile-per-workgroup instance;
+    launch_conv1x1 now has one tile map and one kernel table for every length, so this is the pointwise kernel at large offsets.)  Bit
+    equality over all 8 clips; the binary64 bound on the last clip (8 x 192 x 66 000 in binary64 twice over is most of this file's time
+    otherwise)."""
     sp = case_streaming(C, res, snake)
     want = oracle_conv(sp)
     got = _engine(sp)

@@ -2,6 +2,9 @@
 import numpy as np
 import pytest
 
+import op_judge
+import ref64
+
 from conftest import audit_code_mismatches, dac_cfg_from_meta
 from neuralcodecs_amd.weights import dac_synthetic_state_dict, save_blob, synthetic_pcm
 from oracle import c_oracle
@@ -92,6 +95,13 @@ def test_sin_tanh_accuracy():
     assert np.abs(y - want).max() < 4e-6   # |x|<=30: one ulp of 30 is 1.9e-6
     t = c_oracle.tanh(np.linspace(-12, 12, 100001).astype(np.float32))
     assert np.abs(t - np.tanh(np.linspace(-12, 12, 100001).astype(np.float32).astype(np.float64))).max() < 3e-7
+    # ... and out to |x| = 1e4 (alpha = 1: the argument of the sine is x itself) against binary64, held to the committed table of
+    # tests/golden/op_error_bounds.json: per decade of |x|, in ulp of the binary32 result, times op_judge.MARGIN
+    xw = np.concatenate([np.linspace(-1e4, 1e4, 400001), np.logspace(-3, 4, 70001), -np.logspace(-3, 4, 70001)]).astype(np.float32)
+    xw = xw[np.abs(xw.astype(np.float64)) <= 1e4].reshape(1, 1, -1)
+    one = np.array([1.0], np.float32)
+    assert np.all(np.abs(c_oracle.snake(xw, one).astype(np.float64) - ref64.snake(xw, one)) <= op_judge.snake_tol(xw, one))
+    assert np.all(np.abs(c_oracle.tanh(xw).astype(np.float64) - ref64.tanh(xw)) <= op_judge.tanh_tol(xw))
 
 
 def test_conv_length_formulas_and_values():

@@ -22,6 +22,7 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
 
 import op_judge  # noqa: E402
 import ref64  # noqa: E402
+import test_activation_range_gpu as A  # noqa: E402
 import test_elem_ops_gpu as E  # noqa: E402   (imports open no GPU: the engine library is loaded on first use)
 import test_ops_gpu as G  # noqa: E402
 from op_judge import judge_conv, oracle_conv  # noqa: E402
@@ -155,6 +156,45 @@ def test_snake_and_tanh_error_tables():
     x = np.float32([[[-3.0, 0.0, 1e-45, 1e-40, 7.5]]])
     assert np.array_equal(c_oracle.snake(x, np.float32([0.0])), x)
     assert np.array_equal(c_oracle.snake(x[:, :, 1:4], np.float32([1.0])), x[:, :, 1:4])
+
+
+# ---- the activation range: every case of tests/test_activation_range_gpu.py ------------------------------------------------------------
+@pytest.mark.parametrize("name", list(A.CONV_CASES))
+def test_oracle_activation_range_conv_cases(name):
+    """Wide alphas (1e-3 .. 50), |alpha x| in every decade up to 0.9e4, tanh in all three branches: the oracle within judge_conv, and the
+    builder's own domain and coverage conditions (asserted when the case is built, and again here)."""
+    sp = A.conv_case(name)
+    A.assert_conditions(sp, name)
+    print(name, "oracle error / allowed", _judge_oracle(sp))
+
+
+@pytest.mark.parametrize("name", list(A.RES_UNIT_CASES))
+def test_oracle_activation_range_residual_unit_cases(name):
+    sp7, sp1 = A.res_unit_case(name)
+    A.assert_conditions(sp7, name)
+    print(name, "oracle error / allowed", _judge_oracle(sp7), _judge_oracle(sp1))
+
+
+@pytest.mark.parametrize("dil,T,B", A.DW_CASES)
+def test_oracle_activation_range_depthwise_cases(dil, T, B):
+    x, w, b, ai, ao = A.dw_case(dil, T, B)
+    A.snake_coverage(x, ai, "alpha_in", True)
+    lin = E.dw_oracle(c_oracle.snake(x, ai), w, b, 3 * dil, dil)
+    A.snake_coverage(lin, ao, "alpha_out", False)
+    print("oracle error / allowed", E.dw_judge(c_oracle.snake(lin, ao), x, w, b, 3 * dil, dil, ai, ao, f"oracle, dil={dil} T={T} B={B}"))
+
+
+@pytest.mark.parametrize("C,dil,T,with_next", A.UNIT_CASES)
+def test_oracle_activation_range_snac_unit_cases(C, dil, T, with_next):
+    x, w7, b7, a1, a2, w1, b1, an = A.unit_case(C, dil, T, with_next)
+    A.snake_coverage(x, a1, "a1", True)
+    lin7 = E.dw_oracle(c_oracle.snake(x, a1), w7, b7, 3 * dil, dil)
+    A.snake_coverage(lin7, a2, "a2", False)
+    E.dw_judge(c_oracle.snake(lin7, a2), x, w7, b7, 3 * dil, dil, a1, a2, "oracle, depthwise half")
+    want, sp1 = E._unit_oracle(x, w7, b7, a1, a2, w1, b1, an, dil)
+    if with_next:
+        A.snake_coverage(op_judge.oracle_linear(sp1), an, "next", False)
+    print("oracle error / allowed", judge_conv(want, sp1, "oracle"))
 
 
 # ---- quantizers ------------------------------------------------------------------------------------------------------------------------
