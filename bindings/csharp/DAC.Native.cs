@@ -225,6 +225,58 @@ public sealed unsafe class DACNative : INeuralCodec
         return pcm;
     }
 
+    /// <summary>Dia.GenerateOutput on host arrays: delayed codes [B, tGen, C] and the valid length of every item -> the packed waveforms,
+    /// outLens[b] samples per item.  The delay pattern is undone, the last max(delay) steps cut, codes outside [minValid, maxValid] set
+    /// to 0, all items decoded as one ragged batch and, with speed (one factor per item, null: none), stretched as Dia.AdjustSpeed does.</summary>
+    public float[] DecodeDiaOutput(long[] codesDelayed, int B, long tGen, int[] delayPattern, long[] lengths, float[]? speed, out long[] outLens,
+                                   long minValid = 0, long maxValid = 1023)   // Models/Dia.cs:1010-1093
+    {
+        ArgumentNullException.ThrowIfNull(codesDelayed);
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        ArgumentNullException.ThrowIfNull(lengths);
+        outLens = new long[lengths.Length];
+        int C = delayPattern.Length;
+        fixed (int* pd = delayPattern) fixed (long* pl = lengths, po = outLens) fixed (float* ps = speed)
+            NcMi355x.Check(NcMi355x.nc_dia_output_query(_h, B, tGen, C, pd, pl, ps, null, null, po));
+        long total = 0;
+        foreach (long n in outLens) total += n;
+        var pcm = new float[total];
+        fixed (long* pc = codesDelayed, pl = lengths) fixed (int* pd = delayPattern) fixed (float* ps = speed, pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_dia_decode_output(_h, pc, B, tGen, C, pd, pl, minValid, maxValid, ps, pp));
+        return pcm;
+    }
+
+    /// <summary>AudioUtils.ApplyAudioDelay on DEVICE arrays (int64 [B, T, C], asynchronous on hipStream): the voice prompt delayed with BOS fill.</summary>
+    public void ApplyAudioDelay(IntPtr codesDev, int B, long T, int[] delayPattern, long padValue, long bosValue, IntPtr outDev, IntPtr hipStream)
+    {
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        fixed (int* pd = delayPattern)
+            NcMi355x.Check(NcMi355x.nc_dia_apply_delay_dev(NcMi355x.DeviceIndex(_config.Device), (long*)codesDev, B, T, delayPattern.Length, pd, padValue,
+                                                           bosValue, (long*)outDev, (void*)hipStream));
+    }
+
+    /// <summary>AudioUtils.RevertAudioDelay with the cut and the mask of Dia.GenerateOutput on DEVICE arrays: [B, T, C] -> [B, T - max(delay), C].</summary>
+    public void RevertAudioDelay(IntPtr codesDev, int B, long T, int[] delayPattern, IntPtr outDev, IntPtr hipStream, long minValid = 0, long maxValid = 1023)
+    {
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        fixed (int* pd = delayPattern)
+            NcMi355x.Check(NcMi355x.nc_dia_revert_delay_dev(NcMi355x.DeviceIndex(_config.Device), (long*)codesDev, B, T, delayPattern.Length, pd, minValid,
+                                                            maxValid, (long*)outDev, (void*)hipStream));
+    }
+
+    /// <summary>Dia.AdjustSpeed on rows of packed PCM on the DEVICE: row b of lens[b] samples -> AdjustSpeedLen(lens[b], speed[b]) samples.</summary>
+    public void AdjustSpeed(IntPtr pcmPackedDev, long[] lens, float[] speed, IntPtr outPackedDev, IntPtr hipStream)   // Models/Dia.cs:947-966
+    {
+        ArgumentNullException.ThrowIfNull(lens);
+        ArgumentNullException.ThrowIfNull(speed);
+        fixed (long* pl = lens) fixed (float* ps = speed)
+            NcMi355x.Check(NcMi355x.nc_dia_adjust_speed_dev(NcMi355x.DeviceIndex(_config.Device), (float*)pcmPackedDev, lens.Length, pl, ps,
+                                                            (float*)outPackedDev, (void*)hipStream));
+    }
+
+    /// <summary>`(int)(L / speed)` with AdjustSpeed's early returns: the samples AdjustSpeed yields for a row of L.</summary>
+    public static long AdjustSpeedLen(long L, float speed) => NcMi355x.nc_dia_adjust_speed_len(L, speed);
+
     /// <summary>Codes pushed as a model emits them (Dia): every push returns the PCM that became final; concatenated, the pieces are
     /// Decode(FromCodes(all codes)), bit for bit.  Dispose the session before the model.</summary>
     public NcSession DecodeSession(int batch, int? nQuantizers = null)

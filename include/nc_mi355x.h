@@ -293,7 +293,8 @@ NC_API nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t 
  * tensors and enqueue on the handle's stream; the plain forms take host pointers, are synchronous, and stage the whole packed tensors on the
  * device.  NC_EINVAL for B <= 0, a length <= 0 or a null pointer; whatever status the uniform call on any one clip would return is returned
  * for the whole batch; every refusal is decided before anything is launched.
- * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair, nc_snac_encode_tensor and the group calls.
+ * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair (Dia's delayed matrices of unequal valid lengths
+ * decode through nc_dia_decode_output, "Dia output stage" below), nc_snac_encode_tensor and the group calls.
  * Encodec clips are never cut into windows (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context, so no window
  * of a clip stands for the clip): nc_codec_set_ragged_window / nc_codec_ragged_plan return NC_EUNSUPPORTED for Encodec handles.  Encodec
  * has ragged calls of its own that pool the SEGMENTS of all clips, nc_encodec_*_ragged below ("Encodec ragged batches"). */
@@ -603,6 +604,60 @@ NC_API nc_status nc_audio_deinterleave_dev(int device_index, const float* interl
                                            void* hip_stream);
 NC_API nc_status nc_audio_resample_linear_dev(int device_index, const float* in, int32_t B, int64_t n_in, int32_t src_rate, int32_t dst_rate,
                                               float* out, void* hip_stream);
+
+/* -------------------------------------------------------------------------------------- Dia output stage
+ * What Dia runs between its language model and DAC, and behind DAC, as device kernels (csrc/nc_dia.hip): a batch of
+ * generations stays in HBM from the delayed codes to the waveforms and decodes as ONE ragged batch instead of B single-clip decodes.
+ *   codes_delayed  int64 [B, T_gen, C], Dia's layout (C fastest); C = the model's n_codebooks, at most 32
+ *   delay[]        C non-negative steps (DataConfig.DelayPattern), maxd = max(delay); T_gen > maxd
+ *   lengths[]      valid steps F_b of every item, 1 <= F_b <= T_gen - maxd
+ *   speed[]        speed factor of every item, finite and > 0; NULL: no speed adjustment
+ * delay[], lengths[] and speed[] are HOST arrays in both forms, as in the ragged calls.  Packed layouts as there: item b behind item b-1.
+ * Every step is exact: the code kernels move integers; the speed kernel spells out the rounding of every binary32 operation, so each
+ * output sample is one fixed bit pattern.  NC_EINVAL, before anything is launched, for: B <= 0; a null pointer (speed
+ * excepted); C != n_codebooks or C > 32; a negative delay; T_gen <= maxd; a length <= 0 or > T_gen - maxd; a speed that is not finite or
+ * <= 0; by the decode calls also min_valid < 0 or max_valid >= codebook_size (a code the mask lets through would index past the
+ * codebook; Dia's 0 .. 1023 is DAC 44.1 kHz's whole codebook).  NC_ESTATE without weights.
+ *
+ * replaces: Dia.GenerateOutput                       Models/Dia.cs:1010-1093: BuildRevertIndices / RevertAudioDelay (Modules/Dia/
+ *           AudioUtils.cs:108-176), the cut of the last maxd steps and the mask of codes outside [min_valid, max_valid] to 0 (Dia.cs:
+ *           1039-1044; MinValidCodebookIndex = 0, MaxValidCodebookIndex = 1023, Dia.cs:53-58), Decode of item b at its own length
+ *           (Dia.cs:1055-1058), AdjustSpeed (Dia.cs:947-966, below).  pcm_packed receives out_lens[b] samples per item.  Without speed,
+ *           item b equals nc_dac_decode_code_matrix on its reverted [F_b, C] codes alone, bit for bit.
+ * nc_dia_output_query (host arithmetic: nothing is launched): frames_out[b] = F_b, decoded_lens[b] = the decoded samples L_b,
+ *           out_lens[b] = nc_dia_adjust_speed_len(L_b, speed[b]) (L_b without speed); outputs nullable. */
+NC_API nc_status nc_dia_output_query(const nc_codec* h, int32_t B, int64_t T_gen, int32_t C, const int32_t* delay, const int64_t* lengths,
+                                     const float* speed, int64_t* frames_out, int64_t* decoded_lens, int64_t* out_lens);
+NC_API nc_status nc_dia_decode_output(nc_codec* h, const int64_t* codes_delayed, int32_t B, int64_t T_gen, int32_t C, const int32_t* delay,
+                                      const int64_t* lengths, int64_t min_valid, int64_t max_valid, const float* speed, float* pcm_packed);
+NC_API nc_status nc_dia_decode_output_dev(nc_codec* h, const int64_t* codes_delayed, int32_t B, int64_t T_gen, int32_t C, const int32_t* delay,
+                                          const int64_t* lengths, int64_t min_valid, int64_t max_valid, const float* speed,
+                                          float* pcm_packed);
+/* The pieces on their own: device pointers, asynchronous on `hip_stream` (NULL = null stream), no handle.
+ * replaces: AudioUtils.BuildDelayIndices / ApplyAudioDelay   Modules/Dia/AudioUtils.cs:19-94 (the voice prompt, Dia.cs:387-393):
+ *           out[b, t, c] = t - delay[c] < 0 ? bos : codes[b, t - delay[c], c], int64 [B, T, C].  `pad` is taken as ApplyAudioDelay takes
+ *           it and never written: its mask `t - delay[c] >= T` cannot fire for delay >= 0.
+ * replaces: AudioUtils.BuildRevertIndices / RevertAudioDelay Modules/Dia/AudioUtils.cs:108-176 with the cut and the mask of Dia.cs:1039-1044:
+ *           out[b, t, c] = codes[b, min(t + delay[c], T - 1), c] for t < T - maxd, values outside [min_valid, max_valid] written as 0;
+ *           out int64 [B, T - maxd, C].  RevertAudioDelay's pad mask tests the index AFTER the clamp to T - 1 and cannot fire: no pad argument. */
+NC_API nc_status nc_dia_apply_delay_dev(int device_index, const int64_t* codes, int32_t B, int64_t T, int32_t C, const int32_t* delay, int64_t pad,
+                                        int64_t bos, int64_t* out, void* hip_stream);
+NC_API nc_status nc_dia_revert_delay_dev(int device_index, const int64_t* codes, int32_t B, int64_t T, int32_t C, const int32_t* delay,
+                                         int64_t min_valid, int64_t max_valid, int64_t* out, void* hip_stream);
+/* The same values in the packed layout nc_dac_decode_codes_ragged reads (the first launch of nc_dia_decode_output on its own): item b as
+ * [C, lengths[b]] row-major, item after item, 1 <= lengths[b] <= T - maxd (a HOST array). */
+NC_API nc_status nc_dia_revert_pack_dev(int device_index, const int64_t* codes, int32_t B, int64_t T, int32_t C, const int32_t* delay,
+                                        const int64_t* lengths, int64_t min_valid, int64_t max_valid, int64_t* out_packed, void* hip_stream);
+/* replaces: Dia.AdjustSpeed                          Models/Dia.cs:947-966 through TorchUtils.Interp (Utils/TorchUtils.cs:58-82) on rows of
+ *           packed PCM: row b of lens[b] samples -> nc_dia_adjust_speed_len(lens[b], speed[b]) samples, y = offset * x + slope at
+ *           x = linspace(0, L - 1, T)[i] (binary32: step = (L - 1) / (T - 1); i < T / 2: i * step, else (L - 1) - (T - 1 - i) * step,
+ *           each position one fused multiply-add as ATen's CPU kernel evaluates it; offset * x and + slope are rounded separately).
+ *           A row whose length does not change is copied.  out_packed must not overlap pcm_packed.
+ * nc_dia_adjust_speed_len: `(int)(L / speed)` in binary32 with AdjustSpeed's early returns -- L where |speed - 1| < 1e-5, where the
+ *           quotient truncates to 0 or to L; -1 for L <= 0, a speed that is not finite or <= 0, or a quotient of 2^31 or more. */
+NC_API int64_t nc_dia_adjust_speed_len(int64_t L, float speed);
+NC_API nc_status nc_dia_adjust_speed_dev(int device_index, const float* pcm_packed, int32_t B, const int64_t* lens, const float* speed,
+                                         float* out_packed, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path

@@ -211,6 +211,14 @@ SYMBOLS = [
     ("nc_audio_interleave_dev", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P]),
     ("nc_audio_deinterleave_dev", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P]),
     ("nc_audio_resample_linear_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    ("nc_dia_output_query", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("nc_dia_decode_output", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_decode_output_dev", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_apply_delay_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_revert_delay_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_revert_pack_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_adjust_speed_len", C.c_int64, [C.c_int64, C.c_float]),
+    ("nc_dia_adjust_speed_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P, _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),

@@ -184,6 +184,8 @@ struct DacModel : Codec, DacRvq {
 
     // workspace (grow-only)
     DevBuf act[3], resid, zq, lat, st, codes_ws;
+    // nc_dia.hip: the reverted codes in the packed ragged layout and the decoded PCM in front of the speed adjustment (grow-only)
+    DevBuf dia_codes, dia_pcm;
 
     explicit DacModel(const nc_dac_config& c);
     void load(const Blob& blob) override;

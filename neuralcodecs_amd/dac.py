@@ -365,6 +365,14 @@ class DAC(_lib.ProfileMixin):
             _lib.check(_lib.lib().nc_dac_encode_code_matrix(self._h, x.ctypes.data, B, T, sr, codes.ctypes.data))
         return codes[0] if single else codes
 
+    def decode_dia_output(self, codes_delayed, lengths, delay_pattern, speed=None, valid_range=(0, 1023)):
+        """Dia.GenerateOutput (Models/Dia.cs:1010-1093): delayed codes [B, T_gen, C] and the valid length of every item -> list of
+        waveforms.  The delay pattern is undone, the last max(delay) steps cut and codes outside valid_range (Dia.cs:53-58) set to 0 in
+        one launch that writes the packed ragged layout; all items decode as one ragged batch, each at its own length; speed (one
+        factor or one per item, Dia.AdjustSpeed) stretches the waveforms by linear interpolation (neuralcodecs_amd/dia.py)."""
+        from .dia import decode_dia_output
+        return decode_dia_output(self, codes_delayed, lengths, delay_pattern, speed, valid_range)
+
     @staticmethod
     def decode_one_frame(model: "DAC", audio_codes):
         """Modules/Dia/AudioUtils.cs:189-199: exactly one [1, n_q, T] frame -> FromCodes -> Decode."""

@@ -1,0 +1,190 @@
+"""Dia's output stage on the device (csrc/nc_dia.hip): the steps the reference runs on either side of DAC in its one production caller.
+
+Mirror of the reference's helpers (same argument meaning):
+    dia_apply_delay(codes, delay_pattern, bos, pad)    AudioUtils.BuildDelayIndices / ApplyAudioDelay    Modules/Dia/AudioUtils.cs:19-94
+    dia_revert_delay(codes, delay_pattern, valid)      AudioUtils.BuildRevertIndices / RevertAudioDelay  Modules/Dia/AudioUtils.cs:108-176
+                                                       + the cut and the mask of Dia.GenerateOutput      Models/Dia.cs:1039-1044
+    adjust_speed(rows, speed)                          Dia.AdjustSpeed / TorchUtils.Interp               Models/Dia.cs:947-966
+    DAC.decode_dia_output(...)                         Dia.GenerateOutput                                Models/Dia.cs:1010-1093
+
+torch device tensors stay on the device (zero-copy, torch's current stream); numpy arrays are copied in and out, as in audio.py.  There
+is no CPU implementation here: without the HIP library and a GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .audio import _is_torch, _torch
+
+# Dia.cs:53-58: MinValidCodebookIndex = 0, MaxValidCodebookIndex = 1023
+VALID_RANGE = (0, 1023)
+
+
+def _i32_array(values):
+    v = [int(x) for x in values]
+    return (C.c_int32 * len(v))(*v)
+
+
+def _f32_array(values):
+    v = [float(x) for x in values]
+    return (C.c_float * len(v))(*v)
+
+
+def _speeds(speed, B):
+    """None, one factor for all items or one per item -> a host float array (or None)"""
+    if speed is None:
+        return None
+    s = [float(speed)] * B if np.ndim(speed) == 0 else [float(x) for x in speed]
+    if len(s) != B:
+        raise ValueError("one speed factor per item")
+    return _f32_array(s)
+
+
+def adjust_speed_len(L: int, speed: float) -> int:
+    """nc_dia_adjust_speed_len: samples Dia.AdjustSpeed returns for L samples at this speed factor (host arithmetic, no device)."""
+    n = int(_lib.lib().nc_dia_adjust_speed_len(int(L), float(speed)))
+    if n < 0:
+        raise ValueError(f"{L} samples at speed {speed} have no length")
+    return n
+
+
+def _on_device(x, np_dtype, torch_dtype_name):
+    """x -> (contiguous device tensor, was_torch)"""
+    torch = _torch()
+    tdt = getattr(torch, torch_dtype_name)
+    if _is_torch(x):
+        xt = x.contiguous().to(tdt)
+        return (xt if xt.is_cuda else xt.cuda()), True
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np_dtype))).cuda(), False
+
+
+def _hand_back(out, was_torch):
+    if was_torch:
+        return out
+    _torch().cuda.synchronize(out.device)
+    return out.cpu().numpy()
+
+
+def _codes_btc(codes):
+    if codes is None:
+        raise ValueError("codes must not be null")
+    single = codes.ndim == 2
+    c = codes[None] if single else codes
+    if c.ndim != 3:
+        raise ValueError("codes must be [T, C] or [B, T, C]")
+    return c, single
+
+
+def dia_apply_delay(codes, delay_pattern, bos: int, pad: int = 0):
+    """out[b, t, c] = bos where t < delay[c], else codes[b, t - delay[c], c]; codes int64 [B, T, C] (or [T, C])."""
+    c, single = _codes_btc(codes)
+    B, T, Cn = (int(v) for v in c.shape)
+    if len(delay_pattern) != Cn:
+        raise ValueError("one delay per channel")
+    x, was_torch = _on_device(c, np.int64, "int64")
+    torch = _torch()
+    out = torch.empty_like(x)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_apply_delay_dev(x.device.index or 0, x.data_ptr(), B, T, Cn, _i32_array(delay_pattern), int(pad), int(bos),
+                                                 out.data_ptr(), stream))
+    out = _hand_back(out, was_torch)
+    return out[0] if single else out
+
+
+def dia_revert_delay(codes, delay_pattern, valid_range=VALID_RANGE):
+    """codes int64 [B, T, C] (or [T, C]) -> [B, T - max(delay), C]: out[b, t, c] = codes[b, t + delay[c], c], codes outside valid_range
+    written as 0 (the matrix Dia.GenerateOutput decodes from)."""
+    c, single = _codes_btc(codes)
+    B, T, Cn = (int(v) for v in c.shape)
+    if len(delay_pattern) != Cn:
+        raise ValueError("one delay per channel")
+    x, was_torch = _on_device(c, np.int64, "int64")
+    torch = _torch()
+    out = torch.empty((B, max(0, T - max(int(d) for d in delay_pattern)), Cn), dtype=torch.int64, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_revert_delay_dev(x.device.index or 0, x.data_ptr(), B, T, Cn, _i32_array(delay_pattern), int(valid_range[0]),
+                                                  int(valid_range[1]), out.data_ptr(), stream))
+    out = _hand_back(out, was_torch)
+    return out[0] if single else out
+
+
+def dia_revert_pack(codes, lengths, delay_pattern, valid_range=VALID_RANGE):
+    """The reverted and masked codes of dia_revert_delay in the packed layout DAC.decode_codes_ragged reads: a list of [C, lengths[b]]."""
+    if codes is None or codes.ndim != 3:
+        raise ValueError("codes must be [B, T, C]")
+    B, T, Cn = (int(v) for v in codes.shape)
+    lengths = [int(n) for n in lengths]
+    if len(lengths) != B or len(delay_pattern) != Cn:
+        raise ValueError("one length per item and one delay per channel")
+    x, was_torch = _on_device(codes, np.int64, "int64")
+    torch = _torch()
+    out = torch.empty(max(1, Cn * sum(max(0, n) for n in lengths)), dtype=torch.int64, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_revert_pack_dev(x.device.index or 0, x.data_ptr(), B, T, Cn, _i32_array(delay_pattern), _lib.i64_array(lengths),
+                                                 int(valid_range[0]), int(valid_range[1]), out.data_ptr(), stream))
+    return [p.reshape(Cn, -1) for p in _lib.split_packed(_hand_back(out, was_torch), [Cn * n for n in lengths])]
+
+
+def adjust_speed(rows, speed):
+    """Dia.AdjustSpeed on a list of 1-D waveforms (or one): row b stretched to adjust_speed_len(len, speed[b]) samples by linear
+    interpolation; speed is one factor or one per row.  A row whose length does not change comes back as a copy."""
+    single = not isinstance(rows, (list, tuple))
+    rs = [rows] if single else list(rows)
+    if not rs or any(r.ndim != 1 or r.shape[0] == 0 for r in rs):
+        raise ValueError("every row must be 1-D and not empty")
+    B = len(rs)
+    lens = [int(r.shape[0]) for r in rs]
+    sp = _speeds(speed, B)
+    if sp is None:
+        raise ValueError("speed must not be null")
+    out_lens = [adjust_speed_len(n, s) for n, s in zip(lens, sp)]
+    torch = _torch()
+    was_torch = _is_torch(rs[0])
+    if was_torch:
+        flat = torch.cat([r.to(torch.float32) for r in rs]).contiguous()
+        flat = flat if flat.is_cuda else flat.cuda()
+    else:
+        flat = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(r, np.float32) for r in rs]))).cuda()
+    out = torch.empty(sum(out_lens), dtype=torch.float32, device=flat.device)
+    stream = torch.cuda.current_stream(flat.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_adjust_speed_dev(flat.device.index or 0, flat.data_ptr(), B, _lib.i64_array(lens), sp, out.data_ptr(), stream))
+    pieces = _lib.split_packed(_hand_back(out, was_torch), out_lens)
+    return pieces[0] if single else pieces
+
+
+def output_query(dac, T_gen: int, lengths, delay_pattern, speed=None):
+    """nc_dia_output_query: (frames, decoded samples, samples after the speed adjustment) of every item -- host arithmetic."""
+    B = len(lengths)
+    fr, dl, ol = (C.c_int64 * max(1, B))(), (C.c_int64 * max(1, B))(), (C.c_int64 * max(1, B))()
+    _lib.check(_lib.lib().nc_dia_output_query(dac._h, B, int(T_gen), len(delay_pattern), _i32_array(delay_pattern), _lib.i64_array(lengths),
+                                              _speeds(speed, B), fr, dl, ol))
+    return list(fr)[:B], list(dl)[:B], list(ol)[:B]
+
+
+def decode_dia_output(dac, codes_delayed, lengths, delay_pattern, speed=None, valid_range=VALID_RANGE):
+    """Dia.GenerateOutput: delayed codes int64 [B, T_gen, C] + the valid length of every item -> list of B waveforms.  One revert-and-pack
+    launch, the ragged decode of all items, one interpolation launch where a speed factor asks for it (nc_dia_decode_output[_dev])."""
+    if codes_delayed is None or codes_delayed.ndim != 3:
+        raise ValueError("codes must be [B, T_gen, C]")
+    B, T_gen, Cn = (int(v) for v in codes_delayed.shape)
+    lengths = [int(n) for n in lengths]
+    if len(lengths) != B or len(delay_pattern) != Cn:
+        raise ValueError("one length per item and one delay per channel")
+    sp = _speeds(speed, B)
+    _, _, out_lens = output_query(dac, T_gen, lengths, delay_pattern, speed)
+    L = _lib.lib()
+    args = (B, T_gen, Cn, _i32_array(delay_pattern), _lib.i64_array(lengths), int(valid_range[0]), int(valid_range[1]), sp)
+    if _is_torch(codes_delayed):
+        import torch
+        c = codes_delayed.contiguous().to(torch.int64)
+        pcm = torch.empty(sum(out_lens), dtype=torch.float32, device=c.device)
+        dac._bind_torch_stream()
+        _lib.check(L.nc_dia_decode_output_dev(dac._h, c.data_ptr(), *args, pcm.data_ptr()))
+    else:
+        c = np.ascontiguousarray(codes_delayed, dtype=np.int64)
+        pcm = np.empty(sum(out_lens), np.float32)
+        _lib.check(L.nc_dia_decode_output(dac._h, c.ctypes.data, *args, pcm.ctypes.data))
+    return _lib.split_packed(pcm, out_lens)
