@@ -255,6 +255,40 @@ public sealed unsafe class DACNative : INeuralCodec
                                                            bosValue, (long*)outDev, (void*)hipStream));
     }
 
+    /// <summary>Dia.PrepareAudioPrompt on DEVICE arrays (asynchronous on hipStream): the packed codes of EncodeRagged (item b as
+    /// [C, frames[b]] int64, 0 frames: no prompt) -> the delayed prefill int32 [B, tMax, C] with its BOS rows and -1 fill, in one launch per
+    /// 32 items.  tMax >= max(frames) + max(delay); padValue is taken as ApplyAudioDelay takes it and never written.</summary>
+    public void PrefillPack(IntPtr codesPackedDev, long[] frames, int[] delayPattern, long bosValue, long padValue, long tMax, IntPtr outDev, IntPtr hipStream)   // Models/Dia.cs:329-400
+    {
+        ArgumentNullException.ThrowIfNull(frames);
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        fixed (long* pf = frames) fixed (int* pd = delayPattern)
+            NcMi355x.Check(NcMi355x.nc_dia_prefill_pack_dev(NcMi355x.DeviceIndex(_config.Device), (long*)codesPackedDev, frames.Length, pf, delayPattern.Length,
+                                                            pd, bosValue, padValue, tMax, (int*)outDev, (void*)hipStream));
+    }
+
+    /// <summary>Dia.LoadAudio's mono mix, Dia.Encode of every prompt and Dia.PrepareAudioPrompt on host arrays: pcmPacked holds prompt b behind
+    /// prompt b-1, lengths[b] frames of channels[b] interleaved samples (0: no prompt; channels null: all mono); lengths.Length is
+    /// PrepareAudioPrompt's batch.  Returns the delayed prefill int32 [B, tMax, C] and the prefill steps.  The prompts are not resampled:
+    /// the reference discards its resampled copy (Models/Dia.cs:870-874).</summary>
+    public int[] EncodeDiaPrompts(float[] pcmPacked, long[] lengths, int[]? channels, int[] delayPattern, int bosValue, out int[] prefillSteps,
+                                  out long tMax, int padValue = -1)   // Models/Dia.cs:329-400
+    {
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        ArgumentNullException.ThrowIfNull(lengths);
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        int B = lengths.Length, C = delayPattern.Length;
+        prefillSteps = new int[B];
+        long t;
+        fixed (int* pd = delayPattern) fixed (long* pl = lengths)
+            NcMi355x.Check(NcMi355x.nc_dia_prompt_query(_h, B, C, pd, pl, null, null, &t));
+        tMax = t;
+        var prefill = new int[(long)B * t * C];
+        fixed (float* pp = pcmPacked) fixed (long* pl = lengths) fixed (int* pc = channels, pd = delayPattern, po = prefill, ps = prefillSteps)
+            NcMi355x.Check(NcMi355x.nc_dia_encode_prompts(_h, pp, B, pl, pc, C, pd, bosValue, padValue, po, ps));
+        return prefill;
+    }
+
     /// <summary>AudioUtils.RevertAudioDelay with the cut and the mask of Dia.GenerateOutput on DEVICE arrays: [B, T, C] -> [B, T - max(delay), C].</summary>
     public void RevertAudioDelay(IntPtr codesDev, int B, long T, int[] delayPattern, IntPtr outDev, IntPtr hipStream, long minValid = 0, long maxValid = 1023)
     {

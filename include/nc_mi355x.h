@@ -659,6 +659,57 @@ NC_API int64_t nc_dia_adjust_speed_len(int64_t L, float speed);
 NC_API nc_status nc_dia_adjust_speed_dev(int device_index, const float* pcm_packed, int32_t B, const int64_t* lens, const float* speed,
                                          float* out_packed, void* hip_stream);
 
+/* -------------------------------------------------------------------------------------- Dia prompt stage
+ * What Dia runs between its voice prompts and the language model's delayed prefill, as device kernels (csrc/nc_dia.hip): the
+ * prompts of a batch are mixed to mono, encoded as ONE ragged batch and written as the delayed prefill without leaving HBM.
+ *   pcm_packed   prompt b behind prompt b-1: lengths[b] frames of channels[b] interleaved samples ([n][ch]; channels NULL: all mono)
+ *   lengths[]    samples per channel of every prompt; 0: no prompt (a null entry of the reference's list, or an item past its end)
+ *   delay[]      C non-negative steps (DataConfig.DelayPattern), maxd = max(delay); C = the model's n_codebooks, at most 32
+ *   prefill_out  int32 [B, T_max, C], Dia's layout (C fastest), T_max = max_b F_b + maxd with F_b the model's frames of prompt b (the
+ *                length rule of nc_dac_ragged_query; 0 without a prompt).  With s = t - delay[c]:
+ *                  prefill[b, t, c] = bos for s <= 0, codes_b[c][s - 1] for 1 <= s <= F_b, -1 behind it
+ *                -1 is the torch.full value of Dia.cs:354-358, not `pad`.  `pad` is taken as ApplyAudioDelay takes it and never written:
+ *                its mask `t - delay[c] >= T` cannot fire for delay >= 0.
+ *   steps_out    int32 [B], a HOST array in both forms (nullable): the prefill steps F_b + 1, 1 without a prompt
+ * lengths[], channels[] and delay[] are HOST arrays in both forms, as in the ragged calls.  Every value is a fixed bit pattern: the mix
+ * spells out the rounding of its binary32 sum and division, the encode is nc_dac_encode_ragged_dev unchanged (prompt b's codes are those of
+ * nc_dac_encode on it alone, bit for bit), the prefill moves integers.
+ * NO RESAMPLING.  Dia.LoadAudio calls ResampleLinear where the file's rate differs from the model's and DISCARDS the result (Dia.cs:870-874):
+ * the prompt is encoded at its own rate as if it were the model's.  These calls do the same and take no rate; a caller who wants the
+ * obvious intent runs nc_audio_resample_linear_dev on the prompt first.
+ * NC_EINVAL, before anything is launched (the handle stays usable): B <= 0; a null pointer (channels and steps_out excepted; pcm_packed may
+ * be NULL when every length is 0); C != n_codebooks or C outside [1, 32]; a negative delay; a negative length or one above 2^30;
+ * channels[b] <= 0; T_max == 0 (no prompt and no delay: nothing holds the BOS row); bos or pad outside int32; a grid that does not fit.
+ * NC_ESTATE without weights.
+ *
+ * replaces: Dia.LoadAudio's mono mix                 Models/Dia.cs:851-864 (one launch per 32 prompts, only where a prompt has channels > 1),
+ *           Dia.Encode of every prompt at its own length  Models/Dia.cs:988-1001 (the ragged encode over the prompts with F_b > 0, all C
+ *           codebooks; with no prompt at all nothing is encoded),
+ *           Dia.PrepareAudioPrompt                   Models/Dia.cs:329-400 with BuildDelayIndices / ApplyAudioDelay (Modules/Dia/
+ *           AudioUtils.cs:19-94): one launch per 32 items writes every step of the prefill, the -1 fill included.
+ *           B is PrepareAudioPrompt's `batch` = max(batchSize, prompts.Count) (Dia.cs:348).  With maxd == 0 the reference throws on its
+ *           own copy (rows 1..F_b of a tensor of max F_b rows); here the closed form holds and the longest prompt's last frame is cut.
+ * nc_dia_prompt_query (host arithmetic: nothing is launched): frames_out[b] = F_b, steps_out[b] = F_b + 1, *T_max_out; outputs nullable. */
+NC_API nc_status nc_dia_prompt_query(const nc_codec* h, int32_t B, int32_t C, const int32_t* delay, const int64_t* lengths, int64_t* frames_out,
+                                     int32_t* steps_out, int64_t* T_max_out);
+NC_API nc_status nc_dia_encode_prompts(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, const int32_t* channels, int32_t C,
+                                       const int32_t* delay, int64_t bos, int64_t pad, int32_t* prefill_out, int32_t* steps_out);
+NC_API nc_status nc_dia_encode_prompts_dev(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, const int32_t* channels,
+                                           int32_t C, const int32_t* delay, int64_t bos, int64_t pad, int32_t* prefill_out, int32_t* steps_out);
+/* The pieces on their own: device pointers, asynchronous on `hip_stream` (NULL = null stream), no handle.
+ * replaces: Dia.PrepareAudioPrompt on codes that exist already: codes_packed as nc_dac_encode_ragged writes them (item b as [C, frames[b]]
+ *           row-major, int64, item after item; frames[] a HOST array, 0: no prompt; NULL allowed when every frames[b] is 0) -> out int32
+ *           [B, T_max, C] by the closed form above.  Any 1 <= C <= 32; T_max >= max(frames) + maxd and > 0: steps past a prompt follow the
+ *           closed form (-1, or bos up to delay[c]).  Codes are narrowed as `prompt.to(torch.int32)` narrows them (the low 32 bits). */
+NC_API nc_status nc_dia_prefill_pack_dev(int device_index, const int64_t* codes_packed, int32_t B, const int64_t* frames, int32_t C,
+                                         const int32_t* delay, int64_t bos, int64_t pad, int64_t T_max, int32_t* out, void* hip_stream);
+/* replaces: Dia.LoadAudio's mono mix                 Models/Dia.cs:851-864 over a packed ragged batch: prompt b is n_frames[b] frames of
+ *           channels[b] interleaved samples -> n_frames[b] samples, prompt after prompt (HOST arrays; n_frames[b] >= 0, channels[b] >= 1).
+ *           A binary32 running sum in channel order, one division by (float)channels, as nc_audio_mix_to_mono_dev; a prompt of one channel
+ *           is copied bit for bit.  out_packed must not overlap in_packed. */
+NC_API nc_status nc_audio_mix_to_mono_ragged_dev(int device_index, const float* in_packed, int32_t B, const int64_t* n_frames,
+                                                 const int32_t* channels, float* out_packed, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE

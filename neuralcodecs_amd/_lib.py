@@ -219,6 +219,11 @@ SYMBOLS = [
     ("nc_dia_revert_pack_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("nc_dia_adjust_speed_len", C.c_int64, [C.c_int64, C.c_float]),
     ("nc_dia_adjust_speed_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_dia_prompt_query", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    ("nc_dia_encode_prompts", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_encode_prompts_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_dia_prefill_pack_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_audio_mix_to_mono_ragged_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P, _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),

@@ -4,6 +4,10 @@
 //   decode               item by item at its own length (Dia.cs:1055-1058) == nc_dac_decode_codes_ragged_dev on the packed layout
 //   speed                Dia.AdjustSpeed (Dia.cs:947-966) through TorchUtils.Interp (Utils/TorchUtils.cs:58-82)
 //   delay                BuildDelayIndices / ApplyAudioDelay (AudioUtils.cs:19-94)
+// and its prompt stage ("Dia prompt stage"): what runs between the voice prompts and the language model's delayed prefill.
+//   mono mix             Dia.LoadAudio (Dia.cs:851-864) over a packed ragged batch of interleaved prompts
+//   encode               prompt by prompt at its own length (Dia.Encode, Dia.cs:988-1001) == nc_dac_encode_ragged_dev on the packed layout
+//   prefill              Dia.PrepareAudioPrompt (Dia.cs:329-400): full(-1), BOS row, copy, ApplyAudioDelay -- one closed form, one launch
 // The code kernels only move integers; the speed kernel is binary32 with the rounding of every operation written out (__fmul_rn /
 // __fadd_rn / __fmaf_rn: the same bits whatever the unit is built with), so every result is a fixed bit pattern.
 // The reference's pad masks are dead.  RevertAudioDelay masks `t_idx >= T` AFTER t_idx was clamped to T - 1 (minimum(t + delay, T - 1),
@@ -26,6 +30,7 @@ constexpr int kDiaTile = 64;      // steps of one [t-tile, C] block of the rever
 
 struct DiaDelay { int32_t d[kDiaMaxC]; };
 struct DiaPackItems { int64_t off[kDiaItems], F[kDiaItems]; };             // item k: [C, F] row-major at out + off
+struct DiaMixItems { int64_t in_off[kDiaItems], out_off[kDiaItems + 1]; int32_t ch[kDiaItems]; };   // prompt k: [n][ch] at in + in_off -> n frames at out_off[k]
 struct DiaSpeedRows { int64_t in_off[kDiaItems], L[kDiaItems], out_off[kDiaItems + 1]; };   // row k: L samples -> out_off[k + 1] - out_off[k]
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
@@ -107,6 +112,55 @@ __global__ void dia_adjust_speed_kernel(const float* __restrict__ in, int n_rows
     const float offset = __fsub_rn(fp[idx + 1], f0);
     const float slope = __fsub_rn(f0, __fmul_rn(offset, (float)idx));
     out[o] = __fadd_rn(__fmul_rn(offset, x), slope);
+}
+
+// The delayed prefill of Dia.PrepareAudioPrompt in closed form (the transpose of dia_revert_pack_kernel): item b0 + blockIdx.y as
+// [C, F] row-major at in + off -> out [B, T, C] (C fastest, int32).  With s = t - delay[c]:
+//   out[b, t, c] = bos for s <= 0 (row 0 of the prefill and ApplyAudioDelay's BOS mask), codes[c][s - 1] for 1 <= s <= F, -1 behind it.
+// The -1 is the torch.full value of Dia.cs:354-358.  ApplyAudioDelay's `pad` is NOT among the arguments: its mask t - delay[c] >= T cannot
+// fire (see the head of this file), so the callers take a pad, as the reference does, and nothing ever writes it.
+// A block stages kDiaTile steps x C channels through LDS (int32, row stride C | 1 words: odd, so the t-fastest stores of one channel fall on
+// distinct banks): the reads run t-fastest along each packed channel row (8-byte elements on consecutive addresses), the writes C-fastest
+// over the nt * C consecutive int32 of the tile's rows.  Every step of [0, T) is written by this launch, whatever F: rows behind
+// F + delay[c] and items with F = 0 (no prompt) take the fill and the BOS from the same closed form and read nothing.
+__global__ __launch_bounds__(256) void dia_prompt_prefill_kernel(const int64_t* __restrict__ in, int b0, int64_t T, int C, DiaDelay dl, DiaPackItems it,
+                                                                 int32_t bos, int32_t* __restrict__ out) {
+    __shared__ int32_t tile[kDiaTile * (kDiaMaxC + 1)];
+    const int k = blockIdx.y, Cs = C | 1;
+    const int64_t F = it.F[k], t0 = (int64_t)blockIdx.x * kDiaTile;
+    if (t0 >= T) return;   // (the grid is exactly the tiles of T: never taken)
+    const int nt = (int)(T - t0 < kDiaTile ? T - t0 : kDiaTile);
+    const int64_t* __restrict__ src = in + it.off[k];
+    for (int e = threadIdx.x; e < nt * C; e += 256) {
+        const int c = e / nt, t = e - c * nt;
+        const int64_t s = t0 + t - dl.d[c];
+        int32_t v = -1;
+        if (s <= 0) v = bos;
+        else if (s <= F) v = (int32_t)src[(int64_t)c * F + (s - 1)];   // `prompt.to(torch.int32)`: the low 32 bits
+        tile[t * Cs + c] = v;
+    }
+    __syncthreads();
+    int32_t* __restrict__ dst = out + ((int64_t)(b0 + k) * T + t0) * C;
+    for (int e = threadIdx.x; e < nt * C; e += 256) {
+        const int t = e / C, c = e - t * C;
+        dst[e] = tile[t * Cs + c];
+    }
+}
+
+// Dia.LoadAudio's mono mix (Dia.cs:851-864) over a packed ragged batch, one thread per output frame: prompt k is [n][ch] interleaved at
+// in + in_off[k].  The arithmetic of mix_to_mono_kernel (nc_audio.hip) with the rounding written out: a binary32 running sum from 0 in
+// channel order, then one division by (float)ch.  A prompt of one channel is copied bit for bit (LoadAudio mixes only for channels > 1).
+__global__ void dia_mix_ragged_kernel(const float* __restrict__ in, int n_items, DiaMixItems it, float* __restrict__ out) {
+    const int64_t o = it.out_off[0] + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= it.out_off[n_items]) return;
+    int k = 0;
+    while (k + 1 < n_items && o >= it.out_off[k + 1]) ++k;
+    const int ch = it.ch[k];
+    const float* __restrict__ x = in + it.in_off[k] + (o - it.out_off[k]) * ch;
+    if (ch == 1) { out[o] = x[0]; return; }
+    float sum = 0.0f;
+    for (int c = 0; c < ch; ++c) sum = __fadd_rn(sum, x[c]);
+    out[o] = __fdiv_rn(sum, (float)ch);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -274,6 +328,144 @@ void decode_output_dev(nc_codec* h, DacModel& m, const int64_t* codes_delayed, i
     if (P.stretch) launch_adjust_speed(decoded, B, P.L.data(), P.T.data(), pcm_packed, m.stream, &m.prof);
 }
 
+// ---- prompt stage ----------------------------------------------------------------------------------------------------------------
+int32_t as_i32(int64_t v, const char* what) {
+    if (v < INT32_MIN || v > INT32_MAX) fail(NC_EINVAL, "%s = %lld does not fit the int32 prefill", what, (long long)v);
+    return (int32_t)v;
+}
+
+// the grid of launch_prefill (the tiles of T_max, the same for every item group) and the size of its output, refused before anything is launched
+void check_prefill_grid(int B, int64_t T_max, int C) {
+    if (T_max <= 0) fail(NC_EINVAL, "T_max = %lld: with no prompt and no delay nothing holds the BOS row", (long long)T_max);
+    if ((T_max + kDiaTile - 1) / kDiaTile > 0x7fffffff || T_max > ((int64_t)1 << 60) / ((int64_t)B * C)) fail(NC_EINVAL, "too many steps for one launch");
+}
+
+// packed codes (item b as [C, F[b]], F[b] = 0: no prompt) -> out int32 [B, T_max, C]: one launch per kDiaItems items, each over every step of its items
+void launch_prefill(const int64_t* codes, int B, const int64_t* F, int C, const DiaDelay& dl, int32_t bos, int64_t T_max, int32_t* out, hipStream_t s,
+                    Profiler* prof) {
+    int64_t off = 0;
+    const int64_t tiles = (T_max + kDiaTile - 1) / kDiaTile;
+    for (int b0 = 0; b0 < B; b0 += kDiaItems) {
+        const int n = std::min(kDiaItems, B - b0);
+        DiaPackItems it{};
+        int64_t elems = 0;
+        for (int k = 0; k < n; ++k) {
+            it.off[k] = off;
+            it.F[k] = F[b0 + k];
+            off += (int64_t)C * it.F[k];
+            elems += (int64_t)C * it.F[k];
+        }
+        ProfScope ps(prof, s, NC_KC_ELEM, 0.0, 8.0 * (double)elems + 4.0 * (double)n * (double)T_max * C);
+        hipLaunchKernelGGL(dia_prompt_prefill_kernel, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, s, codes, b0, T_max, C, dl, it, bos, out);
+        NC_HIP(hipGetLastError());
+    }
+}
+
+// the frame totals of launch_mix's groups, refused before anything is launched
+void check_mix_grids(int B, const int64_t* n_frames) {
+    for (int b0 = 0; b0 < B; b0 += kDiaItems) {
+        int64_t total = 0;
+        for (int b = b0; b < std::min(B, b0 + kDiaItems); ++b) total += n_frames[b];
+        (void)grid_for(total);
+    }
+}
+
+// prompt b: [n_frames[b]][channels[b]] interleaved, packed -> n_frames[b] mono samples, packed; a group without a frame launches nothing
+void launch_mix(const float* in, int B, const int64_t* n_frames, const int32_t* channels, float* out, hipStream_t s, Profiler* prof) {
+    int64_t in_off = 0, out_off = 0;
+    for (int b0 = 0; b0 < B; b0 += kDiaItems) {
+        const int n = std::min(kDiaItems, B - b0);
+        DiaMixItems it{};
+        it.out_off[0] = out_off;
+        const int64_t in0 = in_off;
+        for (int k = 0; k < n; ++k) {
+            it.in_off[k] = in_off;
+            it.ch[k] = channels[b0 + k];
+            in_off += n_frames[b0 + k] * channels[b0 + k];
+            out_off += n_frames[b0 + k];
+            it.out_off[k + 1] = out_off;
+        }
+        const int64_t total = out_off - it.out_off[0];
+        if (total == 0) continue;
+        ProfScope ps(prof, s, NC_KC_ELEM, 0.0, 4.0 * (double)(in_off - in0 + total));
+        hipLaunchKernelGGL(dia_mix_ragged_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, n, it, out);
+        NC_HIP(hipGetLastError());
+    }
+}
+
+// Everything nc_dia_prompt_query refuses; n[b] samples per channel, F_b the model's frames of them (0: no prompt)
+struct DiaPromptPlan {
+    DiaDelay dl{};
+    int64_t maxd = 0, T_max = 0;
+    std::vector<int64_t> n, F;
+    std::vector<int32_t> ch;
+    bool mix = false;               // some prompt has more than one channel
+    int64_t in_samples = 0;         // floats of the packed input
+};
+
+DiaPromptPlan plan_prompts(const DacModel& m, int B, int C, const int32_t* delay, const int64_t* lengths, const int32_t* channels) {
+    DiaPromptPlan P;
+    if (B <= 0 || !lengths) fail(NC_EINVAL, "B must be positive and lengths must not be null");
+    if (C != m.cfg.n_codebooks) fail(NC_EINVAL, "a prefill of %d channels for a model of %d codebooks", C, m.cfg.n_codebooks);
+    P.maxd = check_delay(C, delay, P.dl);
+    P.n.assign(lengths, lengths + B);
+    P.F.resize((size_t)B);
+    P.ch.assign((size_t)B, 1);
+    int64_t maxF = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0) fail(NC_EINVAL, "prompt %d has length %lld", b, (long long)lengths[b]);
+        if (lengths[b] > (int64_t)1 << 30) fail(NC_EINVAL, "prompt %d: clip too long", b);   // as nc_dac_encode_ragged
+        if (channels) {
+            if (channels[b] <= 0) fail(NC_EINVAL, "prompt %d has %d channels", b, channels[b]);
+            P.ch[(size_t)b] = channels[b];
+            P.mix = P.mix || (channels[b] > 1 && lengths[b] > 0);
+        }
+        P.F[(size_t)b] = lengths[b] > 0 ? m.frames(lengths[b]) : 0;   // the length rule of nc_dac_ragged_query
+        maxF = std::max(maxF, P.F[(size_t)b]);
+        P.in_samples += lengths[b] * P.ch[(size_t)b];
+    }
+    P.T_max = maxF + P.maxd;
+    check_prefill_grid(B, P.T_max, C);
+    return P;
+}
+
+// what an encode call refuses behind plan_prompts: with both passed, nothing behind the first launch finds anything to refuse
+void check_encode_prompts(const DacModel& m, int B, const DiaPromptPlan& P, const void* pcm, const void* prefill, int64_t bos, int64_t pad) {
+    if (!prefill || (!pcm && P.in_samples > 0)) fail(NC_EINVAL, "nc_dia_encode_prompts: null pointer");
+    (void)as_i32(bos, "bos");
+    (void)as_i32(pad, "pad");
+    if (!m.loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
+    if (P.mix) check_mix_grids(B, P.n.data());
+}
+
+// pcm_packed and prefill_out are device pointers; async on m.stream; the caller has run check_encode_prompts
+void encode_prompts_dev(nc_codec* h, DacModel& m, const float* pcm_packed, int B, int C, const DiaPromptPlan& P, int32_t bos, int32_t* prefill_out) {
+    m.use_device();
+    const float* mono = pcm_packed;
+    if (P.mix) {
+        m.dia_pcm.reserve((size_t)sum_of(P.n) * 4);
+        launch_mix(pcm_packed, B, P.n.data(), P.ch.data(), m.dia_pcm.as<float>(), m.stream, &m.prof);
+        mono = m.dia_pcm.as<float>();
+    }
+    std::vector<int64_t> lens;   // the prompts that exist: one without samples takes no room in either packed layout
+    for (int b = 0; b < B; ++b)
+        if (P.n[(size_t)b] > 0) lens.push_back(P.n[(size_t)b]);
+    if (!lens.empty()) {
+        m.dia_codes.reserve((size_t)((int64_t)C * sum_of(P.F)) * 8);
+        const nc_status st = nc_dac_encode_ragged_dev(h, mono, (int32_t)lens.size(), lens.data(), m.cfg.sample_rate, C, m.dia_codes.as<int64_t>());
+        if (st != NC_OK) {
+            const std::string msg = get_last_error();
+            fail(st, "%s", msg.c_str());
+        }
+    }
+    launch_prefill(m.dia_codes.as<int64_t>(), B, P.F.data(), C, P.dl, bos, P.T_max, prefill_out, m.stream, &m.prof);
+}
+
+void write_steps(int B, const DiaPromptPlan& P, int32_t* steps_out) {
+    if (!steps_out) return;
+    for (int b = 0; b < B; ++b) steps_out[b] = (int32_t)(P.F[(size_t)b] + 1);
+}
+
 }  // namespace
 
 }  // namespace nc
@@ -396,6 +588,85 @@ nc_status nc_dia_adjust_speed_dev(int device_index, const float* pcm_packed, int
         check_speed_grids(B, T.data());
         set_device(device_index);
         launch_adjust_speed(pcm_packed, B, lens, T.data(), out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
+    });
+}
+
+// ---- prompt stage ----------------------------------------------------------------------------------------------------------------
+nc_status nc_dia_prompt_query(const nc_codec* h, int32_t B, int32_t C, const int32_t* delay, const int64_t* lengths, int64_t* frames_out, int32_t* steps_out,
+                              int64_t* T_max_out) {
+    return guard([&] {
+        const DiaPromptPlan P = plan_prompts(as<DacModel>(h), B, C, delay, lengths, nullptr);
+        for (int b = 0; b < B; ++b)
+            if (frames_out) frames_out[b] = P.F[(size_t)b];
+        write_steps(B, P, steps_out);
+        if (T_max_out) *T_max_out = P.T_max;
+    });
+}
+
+nc_status nc_dia_encode_prompts_dev(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, const int32_t* channels, int32_t C,
+                                    const int32_t* delay, int64_t bos, int64_t pad, int32_t* prefill_out, int32_t* steps_out) {
+    return guard([&] {
+        DacModel& m = as<DacModel>(h);
+        const DiaPromptPlan P = plan_prompts(m, B, C, delay, lengths, channels);
+        check_encode_prompts(m, B, P, pcm_packed, prefill_out, bos, pad);
+        encode_prompts_dev(h, m, pcm_packed, B, C, P, (int32_t)bos, prefill_out);
+        write_steps(B, P, steps_out);
+    });
+}
+
+// host pointers: the packed prompts are staged whole, the prefill comes back behind the last launch; complete on return
+nc_status nc_dia_encode_prompts(nc_codec* h, const float* pcm_packed, int32_t B, const int64_t* lengths, const int32_t* channels, int32_t C,
+                                const int32_t* delay, int64_t bos, int64_t pad, int32_t* prefill_out, int32_t* steps_out) {
+    return guard([&] {
+        DacModel& m = as<DacModel>(h);
+        const DiaPromptPlan P = plan_prompts(m, B, C, delay, lengths, channels);
+        check_encode_prompts(m, B, P, pcm_packed, prefill_out, bos, pad);
+        OwnStreamScope own(m);
+        const size_t n_in = (size_t)P.in_samples * 4, n_out = (size_t)((int64_t)B * P.T_max * C) * 4;
+        m.rg_in.reserve(std::max<size_t>(n_in, 4));
+        m.rg_out.reserve(n_out);
+        if (n_in) NC_HIP(hipMemcpyAsync(m.rg_in.p, pcm_packed, n_in, hipMemcpyHostToDevice, m.stream));
+        encode_prompts_dev(h, m, m.rg_in.as<float>(), B, C, P, (int32_t)bos, m.rg_out.as<int32_t>());
+        NC_HIP(hipMemcpyAsync(prefill_out, m.rg_out.p, n_out, hipMemcpyDeviceToHost, m.stream));
+        NC_HIP(hipStreamSynchronize(m.stream));
+        write_steps(B, P, steps_out);
+    });
+}
+
+nc_status nc_dia_prefill_pack_dev(int device_index, const int64_t* codes_packed, int32_t B, const int64_t* frames, int32_t C, const int32_t* delay,
+                                  int64_t bos, int64_t pad, int64_t T_max, int32_t* out, void* hip_stream) {
+    return guard([&] {
+        if (!frames || !out) fail(NC_EINVAL, "null pointer");
+        if (B <= 0) fail(NC_EINVAL, "B must be positive");
+        DiaDelay dl;
+        const int64_t maxd = check_delay(C, delay, dl);
+        int64_t maxF = 0;
+        for (int b = 0; b < B; ++b) {
+            if (frames[b] < 0 || frames[b] > (int64_t)1 << 40) fail(NC_EINVAL, "item %d has %lld frames", b, (long long)frames[b]);
+            maxF = std::max(maxF, frames[b]);
+        }
+        if (!codes_packed && maxF > 0) fail(NC_EINVAL, "null pointer");
+        const int32_t bos32 = as_i32(bos, "bos");
+        (void)as_i32(pad, "pad");   // PrepareAudioPrompt's padValue: taken and never written
+        if (T_max < maxF + maxd) fail(NC_EINVAL, "T_max = %lld is below max(frames) + max(delay) = %lld", (long long)T_max, (long long)(maxF + maxd));
+        check_prefill_grid(B, T_max, C);
+        set_device(device_index);
+        launch_prefill(codes_packed, B, frames, C, dl, bos32, T_max, out, static_cast<hipStream_t>(hip_stream), nullptr);
+    });
+}
+
+nc_status nc_audio_mix_to_mono_ragged_dev(int device_index, const float* in_packed, int32_t B, const int64_t* n_frames, const int32_t* channels,
+                                          float* out_packed, void* hip_stream) {
+    return guard([&] {
+        if (!in_packed || !out_packed || !n_frames || !channels) fail(NC_EINVAL, "null pointer");
+        if (B <= 0) fail(NC_EINVAL, "B must be positive");
+        for (int b = 0; b < B; ++b) {
+            if (n_frames[b] < 0 || n_frames[b] > (int64_t)1 << 40) fail(NC_EINVAL, "prompt %d has %lld frames", b, (long long)n_frames[b]);
+            if (channels[b] <= 0) fail(NC_EINVAL, "prompt %d has %d channels", b, channels[b]);
+        }
+        check_mix_grids(B, n_frames);
+        set_device(device_index);
+        launch_mix(in_packed, B, n_frames, channels, out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
     });
 }
 

@@ -373,6 +373,14 @@ class DAC(_lib.ProfileMixin):
         from .dia import decode_dia_output
         return decode_dia_output(self, codes_delayed, lengths, delay_pattern, speed, valid_range)
 
+    def encode_dia_prompts(self, prompts, batch_size=None, delay_pattern=(0, 8, 9, 10, 11, 12, 13, 14, 15), bos=1026, pad=-1, channels=None):
+        """Dia.LoadAudio's mono mix, Dia.Encode and Dia.PrepareAudioPrompt (Models/Dia.cs:827-877, 988-1001, 329-400): a list of 1-D voice
+        prompts (None: no prompt) -> (delayed prefill int32 [B, T_max, C], prefill steps), B = max(batch_size, len(prompts)).  All prompts
+        encode as one ragged batch, each at its own length, and one launch writes the prefill with its BOS rows and -1 fill; device
+        tensors stay on the device.  The prompts are not resampled, as in the reference (neuralcodecs_amd/dia.py)."""
+        from .dia import encode_dia_prompts
+        return encode_dia_prompts(self, prompts, batch_size, delay_pattern, bos, pad, channels)
+
     @staticmethod
     def decode_one_frame(model: "DAC", audio_codes):
         """Modules/Dia/AudioUtils.cs:189-199: exactly one [1, n_q, T] frame -> FromCodes -> Decode."""

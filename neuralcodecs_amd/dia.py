@@ -6,6 +6,10 @@ Mirror of the reference's helpers (same argument meaning):
                                                        + the cut and the mask of Dia.GenerateOutput      Models/Dia.cs:1039-1044
     adjust_speed(rows, speed)                          Dia.AdjustSpeed / TorchUtils.Interp               Models/Dia.cs:947-966
     DAC.decode_dia_output(...)                         Dia.GenerateOutput                                Models/Dia.cs:1010-1093
+and of the prompt stage in front of the language model:
+    mix_to_mono_ragged(prompts, channels)              Dia.LoadAudio's mono mix                          Models/Dia.cs:851-864
+    dia_prefill_pack(codes, delay_pattern, bos, pad)   Dia.PrepareAudioPrompt (+ ApplyAudioDelay)        Models/Dia.cs:329-400
+    DAC.encode_dia_prompts(...)                        LoadAudio's mix, Dia.Encode, PrepareAudioPrompt   Models/Dia.cs:827-877, 988-1001, 329-400
 
 torch device tensors stay on the device (zero-copy, torch's current stream); numpy arrays are copied in and out, as in audio.py.  There
 is no CPU implementation here: without the HIP library and a GPU every call raises.
@@ -188,3 +192,102 @@ def decode_dia_output(dac, codes_delayed, lengths, delay_pattern, speed=None, va
         pcm = np.empty(sum(out_lens), np.float32)
         _lib.check(L.nc_dia_decode_output(dac._h, c.ctypes.data, *args, pcm.ctypes.data))
     return _lib.split_packed(pcm, out_lens)
+
+
+# ---- prompt stage: voice prompts -> the delayed prefill (nc_dia.hip) -------------------------------------------------------
+# DataConfig.DelayPattern / AudioBosValue of the reference's DiaConfig; PrepareAudioPrompt passes padValue -1 (Dia.cs:393-397)
+DELAY_PATTERN = (0, 8, 9, 10, 11, 12, 13, 14, 15)
+AUDIO_BOS = 1026
+
+
+def prompt_query(dac, lengths, delay_pattern=DELAY_PATTERN):
+    """nc_dia_prompt_query: (frames F_b, prefill steps F_b + 1, T_max = max F_b + max(delay)) for prompts of these lengths in samples
+    (0: no prompt) -- host arithmetic."""
+    B = len(lengths)
+    fr, st, tm = (C.c_int64 * max(1, B))(), (C.c_int32 * max(1, B))(), C.c_int64()
+    _lib.check(_lib.lib().nc_dia_prompt_query(dac._h, B, len(delay_pattern), _i32_array(delay_pattern), _lib.i64_array(lengths), fr, st, C.byref(tm)))
+    return list(fr)[:B], list(st)[:B], int(tm.value)
+
+
+def mix_to_mono_ragged(prompts, channels):
+    """Dia.LoadAudio's mono mix on a list of interleaved 1-D prompts ([n][ch] flattened; channels: one count per prompt): a binary32
+    running sum in channel order, one division; a prompt of one channel comes back as a copy.  One launch per 32 prompts."""
+    rs = list(prompts)
+    ch = [int(c) for c in channels]
+    if not rs or len(ch) != len(rs) or any(r.ndim != 1 for r in rs):
+        raise ValueError("a list of 1-D prompts and one channel count per prompt")
+    if any(c <= 0 or int(r.shape[0]) % c for r, c in zip(rs, ch)):
+        raise ValueError("every prompt holds whole frames of a positive channel count")
+    n = [int(r.shape[0]) // c for r, c in zip(rs, ch)]
+    torch = _torch()
+    was_torch = _is_torch(rs[0])
+    if was_torch:
+        flat = torch.cat([r.to(torch.float32) for r in rs]).contiguous()
+        flat = flat if flat.is_cuda else flat.cuda()
+    else:
+        flat = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(r, np.float32) for r in rs]))).cuda()
+    out = torch.empty(max(1, sum(n)), dtype=torch.float32, device=flat.device)
+    stream = torch.cuda.current_stream(flat.device).cuda_stream
+    _lib.check(_lib.lib().nc_audio_mix_to_mono_ragged_dev(flat.device.index or 0, flat.data_ptr(), len(rs), _lib.i64_array(n), _i32_array(ch),
+                                                          out.data_ptr(), stream))
+    return _lib.split_packed(_hand_back(out, was_torch), n)
+
+
+def dia_prefill_pack(codes, delay_pattern=DELAY_PATTERN, bos: int = AUDIO_BOS, pad: int = -1, T_max=None):
+    """Dia.PrepareAudioPrompt on codes that exist: a list of int64 [C, F_b] (None or F_b = 0: no prompt) -> int32 [B, T_max, C] with
+    out[b, t, c] = bos where t <= delay[c], codes_b[c][t - delay[c] - 1] up to F_b steps behind it, -1 from there on.  T_max defaults to
+    max F_b + max(delay); `pad` is taken as the reference takes it and never written."""
+    items = list(codes)
+    Cn = len(delay_pattern)
+    if not items or any(c is not None and (c.ndim != 2 or int(c.shape[0]) != Cn) for c in items):
+        raise ValueError("a list of codes [C, F] with one delay per channel")
+    frames = [0 if c is None else int(c.shape[1]) for c in items]
+    T = max(frames) + max(int(d) for d in delay_pattern) if T_max is None else int(T_max)
+    torch = _torch()
+    some = [c for c in items if c is not None and c.shape[1] > 0]
+    was_torch = bool(some) and _is_torch(some[0])
+    if was_torch:
+        flat = torch.cat([c.reshape(-1).to(torch.int64) for c in some]).contiguous()
+        flat = flat if flat.is_cuda else flat.cuda()
+    else:
+        host = np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in some]) if some else np.zeros(1, np.int64)
+        flat = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+    out = torch.empty((len(items), max(T, 0), Cn), dtype=torch.int32, device=flat.device)
+    stream = torch.cuda.current_stream(flat.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_prefill_pack_dev(flat.device.index or 0, flat.data_ptr(), len(items), _lib.i64_array(frames), Cn,
+                                                  _i32_array(delay_pattern), int(bos), int(pad), T, out.data_ptr(), stream))
+    return _hand_back(out, was_torch)
+
+
+def encode_dia_prompts(dac, prompts, batch_size=None, delay_pattern=DELAY_PATTERN, bos: int = AUDIO_BOS, pad: int = -1, channels=None):
+    """Dia.LoadAudio's mix, Dia.Encode of every prompt and Dia.PrepareAudioPrompt in one call (nc_dia_encode_prompts[_dev]): a list of
+    1-D waveforms (None: no prompt; with channels[b] > 1 interleaved [n][ch] flattened) -> (prefill int32 [B, T_max, C], prefill steps),
+    B = max(batch_size, len(prompts)).  The prompts are NOT resampled: the reference discards its resampled copy (Dia.cs:870-874)."""
+    ps = [] if prompts is None else list(prompts)
+    B = max(int(batch_size or 0), len(ps))
+    ps += [None] * (B - len(ps))
+    if any(p is not None and p.ndim != 1 for p in ps):
+        raise ValueError("every prompt must be 1-D (or None)")
+    ch = [1] * B if channels is None else [int(c) for c in channels] + [1] * (B - len(channels))
+    if len(ch) != B:
+        raise ValueError("one channel count per prompt")
+    if any(c > 0 and p is not None and int(p.shape[0]) % c for p, c in zip(ps, ch)):
+        raise ValueError("every prompt holds whole frames of its channel count")
+    lens = [0 if p is None else int(p.shape[0]) // max(c, 1) for p, c in zip(ps, ch)]
+    Cn = len(delay_pattern)
+    _, _, T_max = prompt_query(dac, lens, delay_pattern)          # (every refusal that is host arithmetic is raised here)
+    some = [p for p in ps if p is not None and p.shape[0] > 0]
+    steps = (C.c_int32 * max(1, B))()
+    L = _lib.lib()
+    args = (B, _lib.i64_array(lens), None if channels is None else _i32_array(ch), Cn, _i32_array(delay_pattern), int(bos), int(pad))
+    if some and _is_torch(some[0]):
+        import torch
+        flat = torch.cat([p.to(torch.float32) for p in some]).contiguous()
+        out = torch.empty((B, T_max, Cn), dtype=torch.int32, device=flat.device)
+        dac._bind_torch_stream()
+        _lib.check(L.nc_dia_encode_prompts_dev(dac._h, flat.data_ptr(), *args, out.data_ptr(), steps))
+    else:
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32) for p in some])) if some else None
+        out = np.empty((B, T_max, Cn), np.int32)
+        _lib.check(L.nc_dia_encode_prompts(dac._h, None if flat is None else flat.ctypes.data, *args, out.ctypes.data, steps))
+    return out, list(steps)[:B]
