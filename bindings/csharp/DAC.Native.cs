@@ -311,6 +311,84 @@ public sealed unsafe class DACNative : INeuralCodec
     /// <summary>`(int)(L / speed)` with AdjustSpeed's early returns: the samples AdjustSpeed yields for a row of L.</summary>
     public static long AdjustSpeedLen(long L, float speed) => NcMi355x.nc_dia_adjust_speed_len(L, speed);
 
+    private static NcDiaSampleParams SampleParams(float cfgScale, float temperature, float topP, int topK, int eosValue, int padValue) =>
+        new NcDiaSampleParams { cfg_scale = cfgScale, temperature = temperature, top_p = topP, top_k = topK, eos = eosValue, pad = padValue };
+
+    /// <summary>Dia.DecoderStep from the logits on (guidance, masks, SampleNextToken) on HOST arrays, no device: logits float32 [2B, C, V]
+    /// (row 2b unconditional, 2b + 1 conditional), uniform [B, C] in [0, 1) the draw of every row -> tokens [B, C]; bad[b] != 0: a row of
+    /// item b has no token (-1).  The same bits as SampleNextTokenDevice.</summary>
+    public static long[] SampleNextTokenHost(float[] logits, int B, int C, int V, float[] uniform, float cfgScale, float temperature, float topP,
+                                             int topK, int eosValue, out int[] bad)   // Models/Dia.cs:424-501
+    {
+        ArgumentNullException.ThrowIfNull(logits);
+        ArgumentNullException.ThrowIfNull(uniform);
+        if (B <= 0 || C <= 0 || V <= 0 || logits.LongLength != 2L * B * C * V || uniform.LongLength != (long)B * C)
+            throw new ArgumentException("logits must be [2B, C, V] and uniform [B, C]");
+        var tokens = new long[(long)B * C];
+        bad = new int[B];
+        var p = SampleParams(cfgScale, temperature, topP, topK, eosValue, eosValue + 1);
+        fixed (float* pl = logits, pu = uniform) fixed (long* pt = tokens) fixed (int* pb = bad)
+            NcMi355x.Check(NcMi355x.nc_dia_sample_host(pl, B, C, V, p, pu, pt, pb));
+        return tokens;
+    }
+
+    /// <summary>The same on DEVICE arrays in one launch (asynchronous on hipStream): tokensDev int64 [B, C], badDev int32 [B].</summary>
+    public void SampleNextTokenDevice(IntPtr logitsDev, int B, int C, int V, IntPtr uniformDev, float cfgScale, float temperature, float topP, int topK,
+                                      int eosValue, IntPtr tokensDev, IntPtr badDev, IntPtr hipStream)   // Models/Dia.cs:530-560
+    {
+        var p = SampleParams(cfgScale, temperature, topP, topK, eosValue, eosValue + 1);
+        NcMi355x.Check(NcMi355x.nc_dia_sample_dev(NcMi355x.DeviceIndex(_config.Device), (float*)logitsDev, B, C, V, p, (float*)uniformDev,
+                                                  (long*)tokensDev, (int*)badDev, (void*)hipStream));
+    }
+
+    /// <summary>The per-item EOS state of a generation, DEVICE int64 [3, B]: detected 0, countdown -1, finished -1 (Dia.cs:667-669).</summary>
+    public void GenerateStateInit(int B, IntPtr stateDev, IntPtr hipStream)   // Models/Dia.cs:667-669
+    {
+        NcMi355x.Check(NcMi355x.nc_dia_generate_state_init_dev(NcMi355x.DeviceIndex(_config.Device), B, (long*)stateDev, (void*)hipStream));
+    }
+
+    /// <summary>One generation step behind the language model in ONE launch: sampling, the EOS countdown of Dia.Generate and
+    /// DecoderOutput.UpdateOne into generatedDev int32 [B, L, C] at `step` (the reference's currentStepIdx); applyMask = !bosOver.
+    /// activeDev int32 [B] receives countdown != 0; badDev int32 [B] is ORed into (zero it first).  No synchronisation.</summary>
+    public void GenerateStep(IntPtr logitsDev, int B, int V, IntPtr uniformDev, int[] delayPattern, float cfgScale, float temperature, float topP, int topK,
+                             int eosValue, int padValue, long step, long maxTokens, bool applyMask, IntPtr stateDev, IntPtr generatedDev, long L,
+                             IntPtr activeDev, IntPtr badDev, IntPtr hipStream)   // Models/Dia.cs:688-756
+    {
+        ArgumentNullException.ThrowIfNull(delayPattern);
+        var p = SampleParams(cfgScale, temperature, topP, topK, eosValue, padValue);
+        fixed (int* pd = delayPattern)
+            NcMi355x.Check(NcMi355x.nc_dia_generate_step_dev(NcMi355x.DeviceIndex(_config.Device), (float*)logitsDev, B, delayPattern.Length, V, p,
+                                                             (float*)uniformDev, pd, step, maxTokens, applyMask ? 1 : 0, (long*)stateDev,
+                                                             (int*)generatedDev, L, (int*)activeDev, (int*)badDev, (void*)hipStream));
+    }
+
+    /// <summary>The lengths of Dia.Generate from a host copy of the finished steps (the third row of the state): host arithmetic.</summary>
+    public static long[] GenerateLengths(long[] finished, int[] prefillSteps, long finalStep, long maxDelay, out long tGen)   // Models/Dia.cs:775-782
+    {
+        ArgumentNullException.ThrowIfNull(finished);
+        ArgumentNullException.ThrowIfNull(prefillSteps);
+        if (finished.Length != prefillSteps.Length) throw new ArgumentException("one finished step and one prefill step per item");
+        var lengths = new long[finished.Length];
+        long t = 0;
+        fixed (long* pf = finished, pl = lengths) fixed (int* pp = prefillSteps)
+            NcMi355x.Check(NcMi355x.nc_dia_generate_lengths(finished.Length, pf, pp, finalStep, maxDelay, pl, &t));
+        tGen = t;
+        return lengths;
+    }
+
+    /// <summary>The copy into generatedCodes on DEVICE arrays: generatedDev int32 [B, L, C] -> outDev int64 [B, max(lengths) + maxDelay, C],
+    /// the codesDelayed of DecodeDiaOutput with these lengths.</summary>
+    public void GenerateCollect(IntPtr generatedDev, long L, int C, int[] prefillSteps, long[] lengths, long maxDelay, long padValue, IntPtr outDev,
+                                IntPtr hipStream)   // Models/Dia.cs:786-801
+    {
+        ArgumentNullException.ThrowIfNull(prefillSteps);
+        ArgumentNullException.ThrowIfNull(lengths);
+        if (lengths.Length != prefillSteps.Length) throw new ArgumentException("one length and one prefill step per item");
+        fixed (int* pp = prefillSteps) fixed (long* pl = lengths)
+            NcMi355x.Check(NcMi355x.nc_dia_generate_collect_dev(NcMi355x.DeviceIndex(_config.Device), (int*)generatedDev, lengths.Length, L, C, pp, pl,
+                                                                maxDelay, padValue, (long*)outDev, (void*)hipStream));
+    }
+
     /// <summary>Codes pushed as a model emits them (Dia): every push returns the PCM that became final; concatenated, the pieces are
     /// Decode(FromCodes(all codes)), bit for bit.  Dispose the session before the model.</summary>
     public NcSession DecodeSession(int batch, int? nQuantizers = null)

@@ -710,6 +710,80 @@ NC_API nc_status nc_dia_prefill_pack_dev(int device_index, const int64_t* codes_
 NC_API nc_status nc_audio_mix_to_mono_ragged_dev(int device_index, const float* in_packed, int32_t B, const int64_t* n_frames,
                                                  const int32_t* channels, float* out_packed, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------ Dia sampling stage
+ * What Dia runs once per generated frame between its language model's logits and the next row of the delayed code matrix, as ONE launch
+ * (csrc/nc_dia.hip).  With the two stages above: prompt -> [caller's LM] -> next code row -> PCM, no host work in between.
+ *   logits     float32 [2B, C, V], row 2b unconditional, row 2b + 1 conditional (the view of Dia.cs:531-535); 1 <= C <= 32, V <= 4096.
+ *              fp32 ONLY: a caller with bf16 logits converts first.  The reference converts before sampling too (Dia.cs:553) but runs
+ *              the guidance and the masks in the compute dtype; that arithmetic is NOT reproduced, the guidance here is binary32.
+ *   uniform    float32 [B, C] in [0, 1): the draw of every row, SUPPLIED by the caller (deviation 1: the reference's multinomial on
+ *              torch's generator is not reproducible; a supplied uniform is).  Required, also when temperature selects the greedy path.
+ *   tokens     int64 [B, C];  bad int32 [B]
+ * Per row (b, c), every value one fixed bit pattern (fl = one binary32 rounding; the unit is built with -ffp-contract=off):
+ *   1 guidance   g = cond + fl(cfg_scale * fl(cond - uncond))                                                        Dia.cs:538
+ *   2 masks      v > eos: -inf;  c >= 1 and v >= eos: -inf;  on channel 0 g[eos] = fl(g[eos] * 0.8f)                 Dia.cs:541-548
+ *   3 greedy     temperature < 1e-5f: the token is argmax(g) in ATen's order (first maximum; a NaN beats every number, first NaN
+ *                wins: nc_argmax_before, nc_math.h) and the row is done                                             Dia.cs:434-437
+ *   4 EOS rule   if that argmax is not eos, g[eos] = -inf                                                            Dia.cs:439-448
+ *   5            x = fl(g / temperature), a true IEEE division                                                       Dia.cs:451
+ *   6 survivors  the top_k largest x > -inf, ordered by (value descending, index ascending); 1 <= top_k <= 64.  ATen leaves the order
+ *                of topk / sort among equal values open: this order is the project's definition (deviation 2).  -inf is never a
+ *                survivor (nc_expf clamps its argument at -87 and would not map it to 0)                              Dia.cs:454-466
+ *   7 nucleus    only if top_p < 1: e_j = nc_expf(x_j - x_0); S = e_0 + e_1 + ... added in survivor order; p_j = fl(e_j / S) with
+ *                the cumulative c_j added in the same order; survivor j >= 1 is removed when c_{j-1} > top_p         Dia.cs:468-494
+ *   8 draw       S' = the kept e_j added in survivor order, q_j = fl(e_j / S') with the cumulative d_j; the token is the first kept j
+ *                with u < d_j, the last kept one if rounding leaves none                                             Dia.cs:497-499
+ *   9 bad rows   a NaN among the masked g of a sampled row, no survivor, or a survivor of +inf: token -1 and bad[b] != 0 (the reference
+ *                throws inside multinomial there).  nc_dia_sample_* write bad[b] = 0 or 1; the step ORs into it (the caller zeroes it).
+ * nc_dia_sample_params: cfg_scale, temperature, top_p finite, temperature >= 0, top_p > 0 (>= 1: no nucleus); eos in [0, V); pad is what
+ * the step writes behind EOS.  Reference defaults (Dia.Generate, Dia.cs:615-624): 3.0, 1.2, 0.95, top_k 45; eos / pad 1024 / 1025.
+ * NC_EINVAL, before anything is launched, for: a null pointer; B <= 0; C < 1 or C > 32; eos < 0 or eos >= V; V > 4096; top_k outside
+ * [1, 64]; temperature, top_p or cfg_scale not finite; temperature < 0; top_p <= 0; by the step also a negative delay, step < 0 or
+ * step >= L, max_tokens > L.
+ *
+ * replaces: Dia.DecoderStep from the logits on        Models/Dia.cs:530-560 with SampleNextToken (Dia.cs:424-501): nc_dia_sample_dev
+ *           (device pointers, asynchronous on `hip_stream`, no handle) and nc_dia_sample_host -- the same arithmetic as plain serial
+ *           C++ on HOST pointers, no device: for a CPU caller and for checking a device result (written independently of the kernel;
+ *           the two share nc_math.h and nothing else, and agree bit for bit). */
+typedef struct nc_dia_sample_params {
+    float cfg_scale, temperature, top_p;
+    int32_t top_k, eos, pad;
+} nc_dia_sample_params;
+NC_API nc_status nc_dia_sample_dev(int device_index, const float* logits, int32_t B, int32_t C, int32_t V, const nc_dia_sample_params* params,
+                                   const float* uniform, int64_t* tokens, int32_t* bad, void* hip_stream);
+NC_API nc_status nc_dia_sample_host(const float* logits, int32_t B, int32_t C, int32_t V, const nc_dia_sample_params* params, const float* uniform,
+                                    int64_t* tokens, int32_t* bad);
+/* replaces: the EOS countdown of Dia.Generate         Models/Dia.cs:706-746 and DecoderOutput.UpdateOne (Modules/Dia/DecoderOutput.cs:
+ *           71-86) behind the sampling above, sampling + bookkeeping + write in ONE launch, no .item() round trip.
+ *   state      DEVICE int64 [3, B]: detected (0 / 1), countdown (-1 idle, > 0 running, 0 done), finished (-1 none);
+ *              nc_dia_generate_state_init_dev writes 0 / -1 / -1 (Dia.cs:667-669)
+ *   generated  DEVICE int32 [B, L, C]: DecoderOutput.GeneratedTokens, the buffer nc_dia_encode_prompts prefilled (-1: not written)
+ *   delay[]    HOST, C non-negative steps, D = max(delay);  step = the reference's currentStepIdx s;  M = max_tokens
+ * Per item, with tok[] the sampled row:
+ *   active = countdown != 0;  trigger = active && ((!detected && tok[0] == eos) || s >= M - D);  detected |= trigger
+ *   trigger && countdown < 0:  countdown = D, finished = s
+ *   countdown > 0:  a = D - countdown; tok[c] = eos where a == delay[c], pad where a > delay[c];  countdown -= 1
+ *   generated[b, s, c] = (int32)tok[c] -- with apply_mask != 0 only where the slot still holds -1 (UpdateOne's mask; the caller
+ *   computes !bosOver on the host from the prefill steps, Dia.cs:749-755).  Items whose countdown is 0 are still sampled and written, as
+ *   in the reference.  active_out[b] (DEVICE int32 [B]) = countdown != 0 after the step: poll it whenever, no per-step synchronisation. */
+NC_API nc_status nc_dia_generate_state_init_dev(int device_index, int32_t B, int64_t* state, void* hip_stream);
+NC_API nc_status nc_dia_generate_step_dev(int device_index, const float* logits, int32_t B, int32_t C, int32_t V, const nc_dia_sample_params* params,
+                                          const float* uniform, const int32_t* delay, int64_t step, int64_t max_tokens, int32_t apply_mask,
+                                          int64_t* state, int32_t* generated, int64_t L, int32_t* active_out, int32_t* bad, void* hip_stream);
+/* replaces: the lengths of Dia.Generate               Models/Dia.cs:775-782 (host arithmetic, no device): finished[] is a HOST copy of the
+ *           third row of `state`; a finished of -1 becomes final_step - maxd; lengths_out[b] = max(0, finished - prefill_steps[b]);
+ *           *T_gen_out = max(lengths_out) + maxd.  NC_EINVAL for a null pointer (T_gen_out excepted), B <= 0 or maxd < 0.
+ * replaces: the copy into generatedCodes              Models/Dia.cs:786-801, one launch per 32 items: out int64 [B, T_gen, C], T_gen =
+ *           max(lengths) + maxd, out[b, t, c] = generated[b, prefill_steps[b] + t, c] for t < lengths[b] + maxd, `pad` behind it --
+ *           exactly the codes_delayed nc_dia_decode_output_dev takes, with these lengths.  prefill_steps[] and lengths[] are HOST arrays.
+ *           NC_EINVAL for a null pointer, B <= 0, C outside [1, 32], maxd < 0, a negative entry, T_gen == 0 (nothing was generated) or
+ *           prefill_steps[b] + lengths[b] + maxd > L. */
+NC_API nc_status nc_dia_generate_lengths(int32_t B, const int64_t* finished, const int32_t* prefill_steps, int64_t final_step, int64_t maxd,
+                                         int64_t* lengths_out, int64_t* T_gen_out);
+NC_API nc_status nc_dia_generate_collect_dev(int device_index, const int32_t* generated, int32_t B, int64_t L, int32_t C,
+                                             const int32_t* prefill_steps, const int64_t* lengths, int64_t maxd, int64_t pad, int64_t* out,
+                                             void* hip_stream);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE

@@ -92,6 +92,11 @@ class NcSessionStep(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("w0", "w1", "k0", "k1", "resident")]
 
 
+class NcDiaSampleParams(C.Structure):
+    _fields_ = [("cfg_scale", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("eos", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
 
 _lib = None
@@ -224,6 +229,13 @@ SYMBOLS = [
     ("nc_dia_encode_prompts_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P]),
     ("nc_dia_prefill_pack_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     ("nc_audio_mix_to_mono_ragged_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_dia_sample_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NcDiaSampleParams), _P, _P, _P, _P]),
+    ("nc_dia_sample_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NcDiaSampleParams), _P, _P, _P]),
+    ("nc_dia_generate_state_init_dev", C.c_int, [C.c_int, C.c_int32, _P, _P]),
+    ("nc_dia_generate_step_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NcDiaSampleParams), _P, _P, C.c_int64, C.c_int64,
+                                           C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    ("nc_dia_generate_lengths", C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    ("nc_dia_generate_collect_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),

@@ -8,6 +8,11 @@
 //   mono mix             Dia.LoadAudio (Dia.cs:851-864) over a packed ragged batch of interleaved prompts
 //   encode               prompt by prompt at its own length (Dia.Encode, Dia.cs:988-1001) == nc_dac_encode_ragged_dev on the packed layout
 //   prefill              Dia.PrepareAudioPrompt (Dia.cs:329-400): full(-1), BOS row, copy, ApplyAudioDelay -- one closed form, one launch
+// and its sampling stage ("Dia sampling stage"): what runs once per frame between the language model's logits and the next row.
+//   sample               Dia.DecoderStep from the logits on and SampleNextToken (Dia.cs:530-560, 424-501), binary32, a supplied uniform
+//   bookkeeping + write  the EOS countdown of Dia.Generate (Dia.cs:706-746) and DecoderOutput.UpdateOne -- in the same launch
+//   collect              the copy into generatedCodes (Dia.cs:786-801): what nc_dia_decode_output_dev takes
+// (the host twin of the sampler, nc_dia_sample_host, is csrc/nc_dia_sample_host.hip: written apart from the kernel on purpose)
 // The code kernels only move integers; the speed kernel is binary32 with the rounding of every operation written out (__fmul_rn /
 // __fadd_rn / __fmaf_rn: the same bits whatever the unit is built with), so every result is a fixed bit pattern.
 // The reference's pad masks are dead.  RevertAudioDelay masks `t_idx >= T` AFTER t_idx was clamped to T - 1 (minimum(t + delay, T - 1),
@@ -19,6 +24,7 @@
 #include <cmath>
 
 #include "nc_guard.h"
+#include "nc_math.h"
 
 namespace nc {
 
@@ -161,6 +167,195 @@ __global__ void dia_mix_ragged_kernel(const float* __restrict__ in, int n_items,
     float sum = 0.0f;
     for (int c = 0; c < ch; ++c) sum = __fadd_rn(sum, x[c]);
     out[o] = __fdiv_rn(sum, (float)ch);
+}
+
+// ---- sampling stage -------------------------------------------------------------------------------------------------
+// Dia.DecoderStep from the logits on (Dia.cs:530-560), SampleNextToken (Dia.cs:424-501), the EOS countdown of Generate (Dia.cs:706-746) and
+// DecoderOutput.UpdateOne in one launch.  The definition, step by step, is in include/nc_mi355x.h ("Dia sampling stage").
+// One workgroup per item, one wavefront per (item, channel) row (C > kSampleWaves, or a V whose rows do not fit the LDS budget: a wave
+// takes every n_waves-th row).  A wave stages its row once into LDS with guidance and masks applied, element v in lane v & 63: every lane
+// reads and writes only its own elements afterwards, so nothing a wave does to its row needs a barrier.  Survivors are selected one at a
+// time: every lane holds the best of its own elements, a butterfly over the wave finds the best of those by (value descending, index
+// ascending), the lane that owned it strikes it out and looks again.  Survivor j lives in lane j.  The sums of steps 7 and 8 are added in
+// survivor order by every lane alike (v_readlane of lane j's term): sequential, never a tree.  Plain vector loads and stores, no atomics.
+constexpr int kSampleMaxV = 4096, kSampleMaxK = 64, kSampleWaves = 16;
+constexpr int kSampleLdsFloats = 15 * 1024;   // rows of all waves: 60 KiB of the 64 KiB a launch gets without asking for more
+
+struct DiaStepArgs {          // the bookkeeping of one generation step; state == nullptr: sampling alone
+    int64_t step, max_tokens, maxd, L;
+    int32_t apply_mask;
+    int64_t* state;
+    int32_t* generated;
+    int32_t* active_out;
+};
+
+__device__ __forceinline__ float lane_f(float x, int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), j)); }
+
+// the token of row (b, c), the same in every lane; bad: the row has no token (-1)
+__device__ int dia_sample_row(const float* __restrict__ uncond, const float* __restrict__ cond, float* __restrict__ row, int V, int c,
+                              const nc_dia_sample_params& p, float u, int lane, bool& bad) {
+    const float ninf = -__builtin_inff();
+    float bg = ninf;
+    int bi = 0x7fffffff;
+    bool nan = false;
+    for (int v = lane; v < V; v += 64) {
+        const float cd = cond[v];
+        float g = __fadd_rn(cd, __fmul_rn(p.cfg_scale, __fsub_rn(cd, uncond[v])));
+        if (v > p.eos || (c >= 1 && v >= p.eos)) g = ninf;
+        else if (v == p.eos) g = __fmul_rn(g, 0.8f);   // (channel 0: the line above took every other channel's)
+        row[v] = g;
+        nan = nan || g != g;
+        if (nc_argmax_before(g, v, bg, bi)) { bg = g; bi = v; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const float og = __shfl_xor(bg, off);
+        const int oi = __shfl_xor(bi, off);
+        if (nc_argmax_before(og, oi, bg, bi)) { bg = og; bi = oi; }
+    }
+    bad = false;
+    if (p.temperature < 1e-5f) return bi;
+    bad = true;
+    if (__ballot(nan) != 0) return -1;
+    if (bi != p.eos && lane == (p.eos & 63)) row[p.eos] = ninf;
+    float lx = ninf;          // the best of this lane's elements: ascending scan, an equal value never replaces the lower index
+    int li = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) {
+        const float x = __fdiv_rn(row[v], p.temperature);
+        row[v] = x;
+        if (x > lx) { lx = x; li = v; }
+    }
+    float sx = ninf;          // survivor `lane`
+    int si = -1, n = 0;
+    for (int j = 0; j < p.top_k; ++j) {
+        float bx = lx;
+        int bj = li;
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ox = __shfl_xor(bx, off);
+            const int oj = __shfl_xor(bj, off);
+            if (ox > bx || (ox == bx && oj < bj)) { bx = ox; bj = oj; }
+        }
+        if (!(bx > ninf)) break;   // nothing above -inf is left (the same in every lane)
+        if (lane == j) { sx = bx; si = bj; }
+        n = j + 1;
+        if ((bj & 63) == lane) {
+            row[bj] = ninf;
+            lx = ninf;
+            li = 0x7fffffff;
+#pragma unroll 8
+            for (int v = lane; v < V; v += 64) {
+                const float x = row[v];
+                if (x > lx) { lx = x; li = v; }
+            }
+        }
+    }
+    if (n == 0) return -1;
+    const float x0 = lane_f(sx, 0);
+    if (x0 == __builtin_inff()) return -1;
+    bad = false;
+    const float e = lane < n ? nc_expf(__fsub_rn(sx, x0)) : 0.0f;
+    unsigned long long keep = n == 64 ? ~0ull : (1ull << n) - 1;
+    if (p.top_p < 1.0f) {
+        float S = 0.0f;
+        for (int j = 0; j < n; ++j) S = __fadd_rn(S, lane_f(e, j));
+        const float pj = __fdiv_rn(e, S);
+        float cum = 0.0f, before = 0.0f;   // before: c_{lane - 1}
+        for (int j = 0; j < n; ++j) {
+            if (lane == j) before = cum;
+            cum = __fadd_rn(cum, lane_f(pj, j));
+        }
+        keep = __ballot(lane < n && (lane == 0 || !(before > p.top_p)));
+    }
+    float S2 = 0.0f;
+    for (int j = 0; j < n; ++j)
+        if ((keep >> j) & 1) S2 = __fadd_rn(S2, lane_f(e, j));
+    const float q = __fdiv_rn(e, S2);
+    float d = 0.0f;
+    int pick = -1, last = 0;
+    for (int j = 0; j < n; ++j) {
+        if (!((keep >> j) & 1)) continue;
+        d = __fadd_rn(d, lane_f(q, j));
+        last = j;
+        if (pick < 0 && u < d) pick = j;
+    }
+    return __builtin_amdgcn_readlane(si, pick < 0 ? last : pick);
+}
+
+// grid: one workgroup per item; block: n_waves * 64 threads; dynamic LDS: n_waves rows of Vp floats, then tok[32] and rbad[32]
+__global__ __launch_bounds__(kSampleWaves * 64) void dia_sample_kernel(const float* __restrict__ logits, int B, int C, int V, int Vp,
+                                                                        nc_dia_sample_params p, const float* __restrict__ uniform, DiaDelay dl,
+                                                                        DiaStepArgs st, int64_t* __restrict__ tokens, int32_t* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) float sample_lds[];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    float* row = sample_lds + (size_t)w * Vp;
+    int32_t* tok = reinterpret_cast<int32_t*>(sample_lds + (size_t)n_waves * Vp);
+    int32_t* rbad = tok + kDiaMaxC;
+    for (int c = w; c < C; c += n_waves) {
+        const float* uncond = logits + ((int64_t)(2 * b) * C + c) * V;
+        bool row_bad;
+        const int t = dia_sample_row(uncond, uncond + (int64_t)C * V, row, V, c, p, uniform[(int64_t)b * C + c], lane, row_bad);
+        if (lane == 0) {
+            tok[c] = t;
+            rbad[c] = row_bad;
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    int any_bad = 0;
+    for (int c = 0; c < C; ++c) any_bad |= rbad[c];
+    int64_t t = lane < C ? tok[lane] : 0;
+    if (!st.state) {
+        if (lane < C) tokens[(int64_t)b * C + lane] = t;
+        if (lane == 0) bad[b] = any_bad;
+        return;
+    }
+    // lane 0 owns the item's state: it alone reads and writes it; the others take its values
+    int64_t det = 0, cdn = 0, fin = 0;
+    if (lane == 0) {
+        det = st.state[b];
+        cdn = st.state[(int64_t)B + b];
+        fin = st.state[2 * (int64_t)B + b];
+    }
+    det = __shfl(det, 0);
+    cdn = __shfl(cdn, 0);
+    const bool trigger = cdn != 0 && ((det == 0 && tok[0] == p.eos) || st.step >= st.max_tokens - st.maxd);
+    if (trigger) det = 1;
+    if (trigger && cdn < 0) {
+        cdn = st.maxd;
+        fin = st.step;
+    }
+    if (cdn > 0) {
+        const int64_t a = st.maxd - cdn, dc = lane < C ? dl.d[lane] : 0;
+        if (a == dc) t = p.eos;
+        else if (a > dc) t = p.pad;
+        cdn -= 1;
+    }
+    if (lane < C) {
+        int32_t* slot = st.generated + ((int64_t)b * st.L + st.step) * C + lane;
+        if (!st.apply_mask || *slot == -1) *slot = (int32_t)t;
+    }
+    if (lane == 0) {
+        st.state[b] = det;
+        st.state[(int64_t)B + b] = cdn;
+        st.state[2 * (int64_t)B + b] = fin;
+        st.active_out[b] = cdn != 0;
+        bad[b] = bad[b] | any_bad;
+    }
+}
+
+__global__ void dia_state_init_kernel(int64_t* __restrict__ state, int B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 3 * B) state[i] = i < B ? 0 : -1;
+}
+
+// Dia.cs:786-801: item b0 + blockIdx.y of generated [B, L, C] from its prefill step on -> out [B, T_gen, C], `pad` behind its own length
+struct DiaCollectItems { int64_t start[kDiaItems], n[kDiaItems]; };   // item k: rows [start, start + n) of generated, n = length + maxd
+__global__ void dia_collect_kernel(const int32_t* __restrict__ generated, int b0, int64_t L, int C, int64_t T_gen, DiaCollectItems it, int64_t pad,
+                                   int64_t* __restrict__ out) {
+    const int k = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T_gen * C) return;
+    const int64_t t = i / C;
+    out[(int64_t)(b0 + k) * T_gen * C + i] = t < it.n[k] ? (int64_t)generated[((int64_t)(b0 + k) * L + it.start[k]) * C + i] : pad;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -466,6 +661,31 @@ void write_steps(int B, const DiaPromptPlan& P, int32_t* steps_out) {
     for (int b = 0; b < B; ++b) steps_out[b] = (int32_t)(P.F[(size_t)b] + 1);
 }
 
+// ---- sampling stage --------------------------------------------------------------------------------------------------------------
+// everything nc_dia_sample_dev refuses about the shape and the parameters
+void check_sample(int B, int C, int V, const nc_dia_sample_params* p) {
+    if (!p) fail(NC_EINVAL, "params must not be null");
+    if (B <= 0) fail(NC_EINVAL, "B must be positive");
+    if (C < 1 || C > kDiaMaxC) fail(NC_EINVAL, "a row set has 1 to %d channels, not %d", kDiaMaxC, C);
+    if (V > kSampleMaxV) fail(NC_EINVAL, "V = %d is above %d", V, kSampleMaxV);
+    if (p->eos < 0 || p->eos >= V) fail(NC_EINVAL, "eos = %d is not in [0, V = %d)", p->eos, V);
+    if (p->top_k < 1 || p->top_k > kSampleMaxK) fail(NC_EINVAL, "top_k = %d is not in [1, %d]", p->top_k, kSampleMaxK);
+    if (!std::isfinite(p->temperature) || !std::isfinite(p->top_p) || !std::isfinite(p->cfg_scale))
+        fail(NC_EINVAL, "temperature, top_p and cfg_scale must be finite");
+    if (p->temperature < 0.0f) fail(NC_EINVAL, "temperature must not be negative");
+    if (p->top_p <= 0.0f) fail(NC_EINVAL, "top_p must be positive");
+}
+
+// ONE launch: B workgroups of min(C, 16, what the LDS budget holds) waves
+void launch_sample(const float* logits, int B, int C, int V, const nc_dia_sample_params& p, const float* uniform, const DiaDelay& dl, const DiaStepArgs& st,
+                   int64_t* tokens, int32_t* bad, hipStream_t s) {
+    const int Vp = (V + 3) & ~3;
+    const int n_waves = std::min(std::min(C, kSampleWaves), kSampleLdsFloats / Vp);
+    const size_t lds = ((size_t)n_waves * Vp + 2 * kDiaMaxC) * 4;
+    hipLaunchKernelGGL(dia_sample_kernel, dim3((unsigned)B), dim3((unsigned)n_waves * 64), lds, s, logits, B, C, V, Vp, p, uniform, dl, st, tokens, bad);
+    NC_HIP(hipGetLastError());
+}
+
 }  // namespace
 
 }  // namespace nc
@@ -667,6 +887,98 @@ nc_status nc_audio_mix_to_mono_ragged_dev(int device_index, const float* in_pack
         check_mix_grids(B, n_frames);
         set_device(device_index);
         launch_mix(in_packed, B, n_frames, channels, out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
+    });
+}
+
+// ---- sampling stage --------------------------------------------------------------------------------------------------------------
+nc_status nc_dia_sample_dev(int device_index, const float* logits, int32_t B, int32_t C, int32_t V, const nc_dia_sample_params* params,
+                            const float* uniform, int64_t* tokens, int32_t* bad, void* hip_stream) {
+    return guard([&] {
+        if (!logits || !uniform || !tokens || !bad) fail(NC_EINVAL, "null pointer");
+        check_sample(B, C, V, params);
+        set_device(device_index);
+        launch_sample(logits, B, C, V, *params, uniform, DiaDelay{}, DiaStepArgs{}, tokens, bad, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+nc_status nc_dia_generate_state_init_dev(int device_index, int32_t B, int64_t* state, void* hip_stream) {
+    return guard([&] {
+        if (!state) fail(NC_EINVAL, "null pointer");
+        if (B <= 0) fail(NC_EINVAL, "B must be positive");
+        set_device(device_index);
+        hipLaunchKernelGGL(dia_state_init_kernel, dim3(grid_for(3 * (int64_t)B)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), state, B);
+        NC_HIP(hipGetLastError());
+    });
+}
+
+nc_status nc_dia_generate_step_dev(int device_index, const float* logits, int32_t B, int32_t C, int32_t V, const nc_dia_sample_params* params,
+                                   const float* uniform, const int32_t* delay, int64_t step, int64_t max_tokens, int32_t apply_mask, int64_t* state,
+                                   int32_t* generated, int64_t L, int32_t* active_out, int32_t* bad, void* hip_stream) {
+    return guard([&] {
+        if (!logits || !uniform || !state || !generated || !active_out || !bad) fail(NC_EINVAL, "null pointer");
+        check_sample(B, C, V, params);
+        DiaDelay dl;
+        DiaStepArgs st{};
+        st.maxd = check_delay(C, delay, dl);
+        if (step < 0 || step >= L) fail(NC_EINVAL, "step = %lld is not in [0, L = %lld)", (long long)step, (long long)L);
+        if (max_tokens > L) fail(NC_EINVAL, "max_tokens = %lld is above L = %lld", (long long)max_tokens, (long long)L);
+        st.step = step;
+        st.max_tokens = max_tokens;
+        st.L = L;
+        st.apply_mask = apply_mask;
+        st.state = state;
+        st.generated = generated;
+        st.active_out = active_out;
+        set_device(device_index);
+        launch_sample(logits, B, C, V, *params, uniform, dl, st, nullptr, bad, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+nc_status nc_dia_generate_lengths(int32_t B, const int64_t* finished, const int32_t* prefill_steps, int64_t final_step, int64_t maxd, int64_t* lengths_out,
+                                  int64_t* T_gen_out) {
+    return guard([&] {
+        if (!finished || !prefill_steps || !lengths_out) fail(NC_EINVAL, "null pointer");
+        if (B <= 0 || maxd < 0) fail(NC_EINVAL, "B must be positive and maxd must not be negative");
+        int64_t longest = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t f = finished[b] == -1 ? final_step - maxd : finished[b];
+            lengths_out[b] = std::max<int64_t>(0, f - prefill_steps[b]);
+            longest = std::max(longest, lengths_out[b]);
+        }
+        if (T_gen_out) *T_gen_out = longest + maxd;
+    });
+}
+
+nc_status nc_dia_generate_collect_dev(int device_index, const int32_t* generated, int32_t B, int64_t L, int32_t C, const int32_t* prefill_steps,
+                                      const int64_t* lengths, int64_t maxd, int64_t pad, int64_t* out, void* hip_stream) {
+    return guard([&] {
+        if (!generated || !prefill_steps || !lengths || !out) fail(NC_EINVAL, "null pointer");
+        if (B <= 0) fail(NC_EINVAL, "B must be positive");
+        if (C < 1 || C > kDiaMaxC) fail(NC_EINVAL, "1 to %d channels, not %d", kDiaMaxC, C);
+        if (maxd < 0 || maxd > (int64_t)1 << 40 || L <= 0 || L > (int64_t)1 << 40) fail(NC_EINVAL, "maxd and L must fit a code matrix");
+        int64_t longest = 0;
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 0 || prefill_steps[b] < 0) fail(NC_EINVAL, "item %d: negative length or prefill step", b);
+            if (lengths[b] > L || prefill_steps[b] + lengths[b] + maxd > L)
+                fail(NC_EINVAL, "item %d: steps %lld + %lld + %lld run past L = %lld", b, (long long)prefill_steps[b], (long long)lengths[b], (long long)maxd,
+                     (long long)L);
+            longest = std::max(longest, lengths[b]);
+        }
+        const int64_t T_gen = longest + maxd;
+        if (T_gen <= 0) fail(NC_EINVAL, "nothing was generated (T_gen = 0)");
+        const unsigned grid = grid_for(T_gen * C);
+        set_device(device_index);
+        for (int b0 = 0; b0 < B; b0 += kDiaItems) {
+            const int n = std::min(kDiaItems, B - b0);
+            DiaCollectItems it{};
+            for (int k = 0; k < n; ++k) {
+                it.start[k] = prefill_steps[b0 + k];
+                it.n[k] = lengths[b0 + k] + maxd;
+            }
+            hipLaunchKernelGGL(dia_collect_kernel, dim3(grid, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(hip_stream), generated, b0, L, C, T_gen, it,
+                               pad, out);
+            NC_HIP(hipGetLastError());
+        }
     });
 }
 

@@ -30,6 +30,12 @@ NC_HD bool nc_argmin_before(float d, int i, float bd, int bi) {
     return (dn || bn) ? (dn && (!bn || i < bi)) : (d < bd || (d == bd && i < bi));
 }
 NC_HD bool nc_argmin_scan(float d, float bd) { return !(d >= bd) && bd == bd; }
+// The mirror for ATen's argmax (Dia.SampleNextToken's greedy path and its EOS rule, Models/Dia.cs:436, 442): a NaN beats every number,
+// and among equal values (and among NaNs) the LOWER index wins.  nc_argmax_before: (d, i) precedes (bd, bi) in that order.
+NC_HD bool nc_argmax_before(float d, int i, float bd, int bi) {
+    const bool dn = d != d, bn = bd != bd;
+    return (dn || bn) ? (dn && (!bn || i < bi)) : (d > bd || (d == bd && i < bi));
+}
 
 NC_HD float nc_sinf(float x) {
     float n = __builtin_rintf(x * 0x1.45f306p-2f);  // x * fl(1/pi)

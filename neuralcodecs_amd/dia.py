@@ -10,6 +10,10 @@ and of the prompt stage in front of the language model:
     mix_to_mono_ragged(prompts, channels)              Dia.LoadAudio's mono mix                          Models/Dia.cs:851-864
     dia_prefill_pack(codes, delay_pattern, bos, pad)   Dia.PrepareAudioPrompt (+ ApplyAudioDelay)        Models/Dia.cs:329-400
     DAC.encode_dia_prompts(...)                        LoadAudio's mix, Dia.Encode, PrepareAudioPrompt   Models/Dia.cs:827-877, 988-1001, 329-400
+and of the sampling stage behind the language model:
+    dia_sample_next_token(logits, uniform, ...)        Dia.DecoderStep from the logits on, SampleNextToken  Models/Dia.cs:530-560, 424-501
+    dia_sample_host(logits, uniform, ...)              the same bits in serial C++ on the host -- the one call here that needs no device
+    DiaGeneration(...).step / .finish                  the loop of Dia.Generate around a caller's model     Models/Dia.cs:664-801
 
 torch device tensors stay on the device (zero-copy, torch's current stream); numpy arrays are copied in and out, as in audio.py.  There
 is no CPU implementation here: without the HIP library and a GPU every call raises.
@@ -291,3 +295,164 @@ def encode_dia_prompts(dac, prompts, batch_size=None, delay_pattern=DELAY_PATTER
         out = np.empty((B, T_max, Cn), np.int32)
         _lib.check(L.nc_dia_encode_prompts(dac._h, None if flat is None else flat.ctypes.data, *args, out.ctypes.data, steps))
     return out, list(steps)[:B]
+
+
+# ---- sampling stage: guided logits -> the next row of the delayed code matrix (nc_dia.hip) ------------------------------
+# DataConfig.AudioEosValue / AudioPadValue of the reference's DiaConfig; the sampling defaults of Dia.Generate (Dia.cs:615-624)
+AUDIO_EOS, AUDIO_PAD = 1024, 1025
+
+
+def _sample_params(cfg_scale, temperature, top_p, top_k, eos, pad):
+    return _lib.NcDiaSampleParams(float(cfg_scale), float(temperature), float(top_p), int(top_k), int(eos), int(pad))
+
+
+def _logits_shape(logits):
+    if logits is None or logits.ndim != 3 or int(logits.shape[0]) % 2 or int(logits.shape[0]) == 0:
+        raise ValueError("logits must be [2B, C, V]: row 2b unconditional, row 2b + 1 conditional")
+    return int(logits.shape[0]) // 2, int(logits.shape[1]), int(logits.shape[2])
+
+
+def dia_sample_host(logits, uniform, cfg_scale=3.0, temperature=1.2, top_p=0.95, top_k=45, eos=AUDIO_EOS, pad=AUDIO_PAD):
+    """nc_dia_sample_host: Dia.DecoderStep from the logits on (guidance, masks, SampleNextToken) in serial C++ on the host, no device.
+    logits float32 [2B, C, V], uniform float32 [B, C] in [0, 1) -> (tokens int64 [B, C], bad int32 [B]), numpy.  The same bits as
+    dia_sample_next_token."""
+    B, Cn, V = _logits_shape(logits)
+    x = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    u = np.ascontiguousarray(np.asarray(uniform, dtype=np.float32))
+    if u.shape != (B, Cn):
+        raise ValueError("uniform must be [B, C]")
+    tokens, bad = np.empty((B, Cn), np.int64), np.empty(B, np.int32)
+    p = _sample_params(cfg_scale, temperature, top_p, top_k, eos, pad)
+    _lib.check(_lib.lib().nc_dia_sample_host(x.ctypes.data, B, Cn, V, C.byref(p), u.ctypes.data, tokens.ctypes.data, bad.ctypes.data))
+    return tokens, bad
+
+
+def _uniform_on(uniform, B, Cn, device):
+    """the draws of a step on the device: the caller's [B, C], or torch.rand"""
+    torch = _torch()
+    if uniform is None:
+        return torch.rand((B, Cn), dtype=torch.float32, device=device)
+    u, _ = _on_device(uniform, np.float32, "float32")
+    if tuple(u.shape) != (B, Cn):
+        raise ValueError("uniform must be [B, C]")
+    return u.to(device)
+
+
+def dia_sample_next_token(logits, uniform=None, cfg_scale=3.0, temperature=1.2, top_p=0.95, top_k=45, eos=AUDIO_EOS, pad=AUDIO_PAD):
+    """nc_dia_sample_dev: Dia.DecoderStep from the logits on in ONE launch.  logits float32 [2B, C, V] -> (tokens int64 [B, C], bad
+    int32 [B]); bad[b] != 0: a row of item b has no token (-1).  uniform [B, C] in [0, 1) is the draw of every row (None: torch.rand on the
+    device).  The order among equal logits is (value descending, index ascending)."""
+    B, Cn, V = _logits_shape(logits)
+    x, was_torch = _on_device(logits, np.float32, "float32")
+    torch = _torch()
+    u = _uniform_on(uniform, B, Cn, x.device)
+    tokens = torch.empty((B, Cn), dtype=torch.int64, device=x.device)
+    bad = torch.empty(B, dtype=torch.int32, device=x.device)
+    p = _sample_params(cfg_scale, temperature, top_p, top_k, eos, pad)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _lib.check(_lib.lib().nc_dia_sample_dev(x.device.index or 0, x.data_ptr(), B, Cn, V, C.byref(p), u.data_ptr(), tokens.data_ptr(), bad.data_ptr(),
+                                            stream))
+    if was_torch:
+        return tokens, bad
+    torch.cuda.synchronize(x.device)
+    return tokens.cpu().numpy(), bad.cpu().numpy()
+
+
+def generate_lengths(finished, prefill_steps, final_step: int, maxd: int):
+    """nc_dia_generate_lengths (Dia.cs:775-782, host arithmetic): (lengths, T_gen) from a host copy of the finished steps."""
+    B = len(prefill_steps)
+    out, tg = (C.c_int64 * max(1, B))(), C.c_int64()
+    _lib.check(_lib.lib().nc_dia_generate_lengths(B, _lib.i64_array(finished), _i32_array(prefill_steps), int(final_step), int(maxd), out, C.byref(tg)))
+    return list(out)[:B], int(tg.value)
+
+
+class DiaGeneration:
+    """The generation loop of Dia.Generate (Dia.cs:664-801) around a caller's language model, everything but the model on the device:
+
+        gen = DiaGeneration(B, delay_pattern, max_tokens, prefill, prefill_steps)      # the two outputs of DAC.encode_dia_prompts
+        while not gen.exhausted and gen.active().any():                                # (poll as rarely as you like)
+            logits = lm(gen.tokens())                                                  # float32 [2B, C, V] on the device
+            gen.step(logits)                                                           # ONE launch: sample, EOS bookkeeping, write
+        codes_delayed, lengths = gen.finish()                                          # what DAC.decode_dia_output takes
+
+    generated is DecoderOutput.GeneratedTokens, int32 [B, audio_length, C] with the prefill copied in; state, active and bad live on the
+    device.  numpy in (the prefill), numpy out of finish(); torch device tensors in, tensors out.
+    audio_length defaults to max_tokens, the reference's buffer.  A step writes row dec_step + 1, so the last step that fits is the one
+    with dec_step + 1 == audio_length - 1: `exhausted` turns true behind it (or at dec_step == max_tokens) and step() raises ValueError.
+    With a delay pattern of zeros only, an item that never emits EOS is first cut by the length rule at row max_tokens, which the
+    reference's own buffer does not hold either (its loop indexes past it); pass audio_length = max_tokens + 1 to take that step."""
+
+    def __init__(self, B, delay_pattern, max_tokens, prefill, prefill_steps, cfg_scale=3.0, temperature=1.2, top_p=0.95, top_k=45,
+                 eos=AUDIO_EOS, pad=AUDIO_PAD, audio_length=None):
+        torch = _torch()
+        self.B, self.delay = int(B), [int(d) for d in delay_pattern]
+        self.C, self.maxd, self.max_tokens = len(self.delay), max(self.delay), int(max_tokens)
+        self.L = self.max_tokens if audio_length is None else int(audio_length)
+        self.prefill_steps = [int(s) for s in prefill_steps]
+        self.params = _sample_params(cfg_scale, temperature, top_p, top_k, eos, pad)
+        self.pad = int(pad)
+        self._delay_arr = _i32_array(self.delay)
+        pre, self._torch_out = _on_device(prefill, np.int32, "int32")
+        if pre.ndim != 3 or int(pre.shape[0]) != self.B or int(pre.shape[2]) != self.C or len(self.prefill_steps) != self.B:
+            raise ValueError("prefill must be [B, T, C] with one prefill step per item and one delay per channel")
+        if int(pre.shape[1]) > self.L or self.max_tokens > self.L:
+            raise ValueError("the prefill and max_tokens must fit audio_length")
+        dev = pre.device
+        self.device = dev
+        self.generated = torch.full((self.B, self.L, self.C), -1, dtype=torch.int32, device=dev)         # DecoderOutput.New / Prefill
+        self.generated[:, :pre.shape[1], :] = pre
+        self.state = torch.empty((3, self.B), dtype=torch.int64, device=dev)
+        self._active = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self._bad = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().nc_dia_generate_state_init_dev(dev.index or 0, self.B, self.state.data_ptr(), self._stream()))
+        self.dec_step = min(self.prefill_steps) - 1                                                     # Dia.cs:664
+        self._bos_over = False
+
+    def _stream(self):
+        return _torch().cuda.current_stream(self.device).cuda_stream
+
+    @property
+    def exhausted(self):
+        """no further step fits: max_tokens steps are taken (Dia.cs:681), or row dec_step + 1 lies behind the buffer"""
+        return self.dec_step >= self.max_tokens or self.dec_step + 1 >= self.L
+
+    def tokens(self):
+        """DecoderOutput.GetTokensAt(decStep): the row the language model reads next, int32 [B, C] (a view of `generated`)"""
+        return self.generated[:, self.dec_step, :]
+
+    def step(self, logits, uniform=None):
+        """One pass of the loop body behind the language model (Dia.cs:688-756): logits float32 [2B, C, V] -> generated[:, dec_step + 1]."""
+        B, Cn, V = _logits_shape(logits)
+        if (B, Cn) != (self.B, self.C):
+            raise ValueError("logits must be [2B, C, V] of this generation")
+        if self.exhausted:
+            raise ValueError(f"no step left: dec_step = {self.dec_step}, max_tokens = {self.max_tokens}, audio_length = {self.L}")
+        x, _ = _on_device(logits, np.float32, "float32")
+        u = _uniform_on(uniform, B, Cn, self.device)
+        s = self.dec_step + 1
+        if not self._bos_over:                                                                          # Dia.cs:749-753
+            self._bos_over = all(self.dec_step - p > self.maxd for p in self.prefill_steps)
+        _lib.check(_lib.lib().nc_dia_generate_step_dev(self.device.index or 0, x.data_ptr(), B, Cn, V, C.byref(self.params), u.data_ptr(),
+                                                       self._delay_arr, s, self.max_tokens, 0 if self._bos_over else 1,
+                                                       self.state.data_ptr(), self.generated.data_ptr(), self.L, self._active.data_ptr(),
+                                                       self._bad.data_ptr(), self._stream()))
+        self.dec_step += 1
+
+    def active(self):
+        """countdown != 0 per item after the last step, bool [B] on the host (this synchronises; the loop ends when none is left)"""
+        return self._active.cpu().numpy() != 0
+
+    def bad(self):
+        """items that had a row without a token (-1 written) in some step, bool [B] on the host"""
+        return self._bad.cpu().numpy() != 0
+
+    def finish(self):
+        """Dia.cs:775-801: (codes_delayed int64 [B, T_gen, C], lengths) -- the arguments of DAC.decode_dia_output."""
+        torch = _torch()
+        finished = self.state[2].cpu().numpy().tolist()
+        lengths, T_gen = generate_lengths(finished, self.prefill_steps, self.dec_step + 1, self.maxd)
+        out = torch.empty((self.B, max(T_gen, 0), self.C), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().nc_dia_generate_collect_dev(self.device.index or 0, self.generated.data_ptr(), self.B, self.L, self.C,
+                                                          _i32_array(self.prefill_steps), _lib.i64_array(lengths), self.maxd, self.pad,
+                                                          out.data_ptr(), self._stream()))
+        return _hand_back(out, self._torch_out), lengths
