@@ -194,6 +194,88 @@ public sealed unsafe class EncodecNative : INeuralCodec
         return pcm;
     }
 
+    // ---- stream pool: PCM or frames that arrive over time (segmented models; nc_encodec_stream_pool_*) ---------------------------------
+    /// <summary>nSlots live streams on this model, one direction, stepped together; what a slot emits, end to end, is Encode / Decode
+    /// (with DSP.LinearOverlapAdd) on the whole stream, bit for bit.  The one-stream session is a pool with one slot.  The pool borrows
+    /// the model: destroy it first.  nQ (decode): codebooks in the pushed codes, 0 = the bandwidth in force.</summary>
+    public IntPtr CreateStreamPool(bool decode, int nSlots, int nQ = 0)
+    {
+        NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_create(_h, decode ? 1 : 0, nSlots, nQ, out IntPtr p));
+        return p;
+    }
+
+    public static void DestroyStreamPool(IntPtr pool) => NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_destroy(pool));
+
+    public static void ResetStreamSlot(IntPtr pool, int slot) => NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_reset_slot(pool, slot));
+
+    public static long StreamPending(IntPtr pool, int slot)
+    {
+        long n;
+        NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_pending(pool, slot, &n));
+        return n;
+    }
+
+    /// <summary>The rows a step would run under the pool's current state, in launch order (clip: the entry's index): per entry its
+    /// segments, their offsets in the stream and their code frames.  frameLens: decode pools only.</summary>
+    public static NcEncodecRaggedRow[] StreamPlan(IntPtr pool, int[] slots, long[] nIn, int[] flush, long[]? frameLens, out NcEncodecRaggedPlan plan)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        NcEncodecRaggedPlan p;
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pl = frameLens)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_plan(pool, slots.Length, ps, pi, pf, pl, &p, null, 0));
+        var rows = new NcEncodecRaggedRow[Math.Max(1, (int)p.n_rows)];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pl = frameLens) fixed (NcEncodecRaggedRow* pr = rows)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_plan(pool, slots.Length, ps, pi, pf, pl, &p, pr, p.n_rows));
+        plan = p;
+        return rows;
+    }
+
+    /// <summary>One step of an encode pool: entry i pushes nIn[i] samples of slot slots[i] ([Channels, nIn[i]], packed entry after entry)
+    /// and ends the stream where flush[i] != 0.  Returns the packed codes of the segments that became complete -- per entry nFrames[i]
+    /// segments with codeFrames[i] code frames in all, each laid out as EncodeHost(B = 1) lays it out -- and one scale per segment.</summary>
+    public long[] StreamEncodeStep(IntPtr pool, int[] slots, long[] nIn, int[] flush, float[] pcmPacked, out int[] nFrames, out long[] codeFrames,
+                                   out float[] scalesPacked)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        nFrames = new int[slots.Length];
+        codeFrames = new long[slots.Length];
+        int nf, nQ;
+        long dec;
+        NcMi355x.Check(NcMi355x.nc_encodec_query(_h, 1, &nf, &nQ, null, 0, &dec));                    // n_q of the bandwidth in force
+        fixed (int* ps = slots, pf = flush, pn = nFrames) fixed (long* pi = nIn, pc = codeFrames)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_query(pool, slots.Length, ps, pi, pf, null, pn, pc, null));
+        var codes = new long[Math.Max(1, nQ * codeFrames.Sum())];
+        scalesPacked = new float[Math.Max(1, nFrames.Sum())];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pc = codes) fixed (float* pp = pcmPacked, psc = scalesPacked)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_step(pool, slots.Length, ps, pi, pf, null, pp, null, pc, psc, null, codes.Length, null, null));
+        return codes;
+    }
+
+    /// <summary>One step of a decode pool: entry i pushes nIn[i] frames of slot slots[i] -- codes [nQ, frameLens[..]] end to end and one
+    /// scale per frame, packed entry after entry -- and ends the stream where flush[i] != 0 (its last one or two frames may then be the
+    /// clip's short tail).  Returns the packed PCM, [Channels, nSamples[i]] per entry: the samples that became final.</summary>
+    public float[] StreamDecodeStep(IntPtr pool, int[] slots, long[] nIn, int[] flush, long[] frameLens, long[] codesPacked, float[]? scalesPacked,
+                                    out long[] nSamples)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        ArgumentNullException.ThrowIfNull(frameLens);
+        ArgumentNullException.ThrowIfNull(codesPacked);
+        nSamples = new long[slots.Length];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pl = frameLens, pn = nSamples)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_query(pool, slots.Length, ps, pi, pf, pl, null, null, pn));
+        var pcm = new float[Math.Max(1, Channels * nSamples.Sum())];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pl = frameLens, pc = codesPacked) fixed (float* psc = scalesPacked, pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_encodec_stream_pool_step(pool, slots.Length, ps, pi, pf, pl, pc, Normalize ? psc : null, pp, null, null, pcm.Length, null, null));
+        return pcm;
+    }
+
     // ---- the reference's members, signature for signature ---------------------------------------------------------------------------
     public Tensor Decode(List<EncodedFrame> encodedFrames)                          // Models/Encodec.cs:213-235
     {

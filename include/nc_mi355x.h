@@ -383,8 +383,9 @@ NC_API nc_status nc_session_schedule(const nc_halo* halo, int32_t decode, int32_
  * session reads (0 = all; SNAC and encode sessions ignore it: an encode session writes every codebook).  Several sessions may live on one
  * handle: they share its arena and stream, and the caller serialises their calls like every other call on the handle.  A session
  * BORROWS its handle: destroy the sessions first.  Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; the
- * 24 kHz LSTM has unbounded context, so no window stands for the clip).
- *   decode sessions   in: DAC codes [B, n_q, n]; SNAC every level at its own rate, [B, sum_i n / vq_strides[i]] as nc_snac_decode takes
+ * 24 kHz LSTM has unbounded context, so no window stands for the clip; segmented Encodec models stream through
+ * nc_encodec_stream_pool_* below).
+ *   decode sessions  in: DAC codes [B, n_q, n]; SNAC every level at its own rate, [B, sum_i n / vq_strides[i]] as nc_snac_decode takes
  *                     them (n a multiple of align).  n_in = n frames.  out: PCM rows [B, out_cap], the first *n_out samples of a row valid.
  *                     SNAC with NoiseBlocks: `noise` holds the caller's noise for the pushed frames, one [B, 1, n * S_i] block per decoder
  *                     stage laid end to end (S_i = the product of the first i + 1 decoder rates); the session keeps the part that belongs
@@ -564,6 +565,74 @@ NC_API nc_status nc_encodec_decode_ragged(nc_codec* h, const int64_t* codes_pack
                                           const int64_t* lengths, int32_t n_q, float* pcm_packed);
 NC_API nc_status nc_encodec_decode_ragged_dev(nc_codec* h, const int64_t* codes_packed, const float* scales_packed, int32_t B,
                                               const int64_t* lengths, int32_t n_q, float* pcm_packed);
+
+/* ------------------------------------------------------------------------- Encodec stream pool
+ * replaces: Encodec.Encode / Encodec.Decode (Models/Encodec.cs:259-285, 213-235) and DSP.LinearOverlapAdd (AudioTools/AudioTensorDSP.cs:
+ * 161-261) for a caller whose PCM or frames ARRIVE over time.  Segmented models only (segment_length > 0: the 48 kHz preset): a segment
+ * depends on nothing outside itself, so a stream is encoded segment by segment as its samples arrive and decoded frame by frame, and what
+ * a slot emits, laid end to end, is bit for bit what nc_encodec_encode / nc_encodec_decode (B = 1) give on the whole stream.
+ * The latency is one segment, by the codec's own design.  A model without segmentation (the 24 kHz preset: its LSTM runs over the whole
+ * clip) answers NC_EUNSUPPORTED at create.
+ * A pool is n_slots independent streams of `channels` channels on one handle, one direction; the one-stream session is a pool with one
+ * slot.  A step is n entries (slots[i], n_in[i], flush[i]) naming distinct slots (flush == NULL: nobody flushes).  Rows of equal key
+ * (Encode: samples, Decode: code frames) from any slots run through the unchanged launch sequences in batches of at most the handle's
+ * ragged max_rows (nc_encodec_set_ragged_rows), keys in descending order: a lock-step step of n streams is one n-row launch sequence.
+ *   encode pool (decode == 0)   an entry pushes n_in >= 0 samples, [channels, n_in], packed entry after entry in in_packed.  A stream
+ *       that has received T_s samples has emitted, once each and in order, every segment k with k * stride + segment_length <= T_s; the
+ *       samples from the next segment's start on (fewer than segment_length) stay in the slot; a push that completes no segment only
+ *       appends.  flush != 0 (after the entry's last n_in samples) emits the remaining segments of the T_s-sample clip -- up to two short
+ *       ones -- and ends the slot until nc_encodec_stream_pool_reset_slot.  Every emitted segment comes as nc_encodec_encode(B = 1) lays
+ *       it out: out_packed int64 codes [n_q, T'_f] end to end (n_q: the handle's bandwidth), scales_out one float per segment (written
+ *       when the model normalises; nullable), emb_packed (nullable test hook) [dimension, T'_f] end to end; entry after entry.
+ *       scales_in and frame_lens are ignored.
+ *   decode pool (decode != 0; n_q fixed at create, 0 = the handle's bandwidth)   an entry pushes n_in >= 0 frames: in_packed their int64
+ *       codes [n_q, F] end to end, scales_in one float per frame (models that normalise), entry after entry.  frame_lens (HOST array,
+ *       nullable) holds F of every frame of every entry in the same order; NULL: every frame is a full segment's F_full.  Without a flush
+ *       every frame must be F_full long and the entry emits [channels, n_in * stride] samples: after frames 0..k the samples
+ *       [0, (k + 1) * stride) are final.  A flush entry's frames may end in the one or two short frames of the clip's tail; the whole
+ *       list is validated as nc_encodec_clip_length validates a layout, the entry emits the rest and the slot is ended.  out_packed:
+ *       float [channels, n_out[i]] entry after entry.  scales_out and emb_packed are ignored.
+ * n_frames[i] (nullable): segments emitted | frames consumed; n_out[i] (nullable): code frames emitted | samples per channel emitted.
+ * Both are host arithmetic: nc_encodec_stream_pool_query gives them for the pool's current state (n_samples: Decode the samples per
+ * channel the entry emits, Encode the samples the slot keeps afterwards), so out_packed can be sized first; out_cap is its capacity in
+ * elements (Encode: n_q * the code frames of all entries; Decode: channels * the samples of all entries).  The *_dev form takes device
+ * pointers for the packed tensors, host arrays for slots / n_in / flush / frame_lens, and enqueues on the handle's stream; the plain
+ * form takes host pointers and is synchronous.  nc_encodec_stream_pool_pending: Encode the samples the slot holds, Decode the decoded
+ * samples per channel not yet emitted.
+ * Everything is decided before anything is launched, names the slot, and leaves every slot as it was -- NC_EINVAL: a null pointer,
+ * n <= 0, a slot out of range or named twice, n_in < 0, a push to an ended slot, a flush of a slot that has received nothing, a decode
+ * push whose frame is not F_full long, tail frames that no clip length produces, out_cap below the query, and whatever the one-clip
+ * call answers for a tail segment (one too short for the residual blocks, for instance); NC_ESTATE without weights.  A pool BORROWS its
+ * handle: destroy it first; the caller serialises its calls with every other call on the handle.
+ * nc_encodec_stream_plan states a step as a host function (no handle, no device), like nc_encodec_ragged_rows: stream i has received
+ * pushed[i] samples (Decode: frames) and emitted emitted[i] segments (Decode: samples per channel) and now brings n_in[i] / flush[i] /
+ * frame_lens; rows (nullable, the first `cap`) are the rows that would run, in launch order, `clip` being the stream's index i and
+ * `offset` the segment's first sample in the stream; n_frames / code_frames / n_samples (nullable) as the query gives them. */
+typedef struct nc_encodec_stream_pool nc_encodec_stream_pool;
+NC_API nc_status nc_encodec_stream_plan(const nc_encodec_config* cfg, int32_t decode, int32_t n, const int64_t* pushed, const int64_t* emitted,
+                                        const int64_t* n_in, const int32_t* flush, const int64_t* frame_lens, int32_t max_rows,
+                                        nc_encodec_ragged_plan* out, nc_encodec_ragged_row* rows, int64_t cap, int32_t* n_frames,
+                                        int64_t* code_frames, int64_t* n_samples);
+NC_API nc_status nc_encodec_stream_pool_create(nc_codec* h, int32_t decode, int32_t n_slots, int32_t n_q, nc_encodec_stream_pool** out);
+NC_API nc_status nc_encodec_stream_pool_destroy(nc_encodec_stream_pool* p);
+NC_API nc_status nc_encodec_stream_pool_reset_slot(nc_encodec_stream_pool* p, int32_t slot);
+NC_API nc_status nc_encodec_stream_pool_pending(const nc_encodec_stream_pool* p, int32_t slot, int64_t* n);
+NC_API nc_status nc_encodec_stream_pool_query(const nc_encodec_stream_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                              const int32_t* flush, const int64_t* frame_lens, int32_t* n_frames, int64_t* code_frames,
+                                              int64_t* n_samples);
+/* the rows the step would run under the pool's current state and the handle's max_rows, as nc_encodec_stream_plan reports them (`clip`:
+ * the entry's index; rows nullable, the first `cap` in launch order): per entry its segments with their code frames */
+NC_API nc_status nc_encodec_stream_pool_plan(const nc_encodec_stream_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                             const int32_t* flush, const int64_t* frame_lens, nc_encodec_ragged_plan* out,
+                                             nc_encodec_ragged_row* rows, int64_t cap);
+NC_API nc_status nc_encodec_stream_pool_step(nc_encodec_stream_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                             const int32_t* flush, const int64_t* frame_lens, const void* in_packed, const float* scales_in,
+                                             void* out_packed, float* scales_out, float* emb_packed, int64_t out_cap, int32_t* n_frames,
+                                             int64_t* n_out);
+NC_API nc_status nc_encodec_stream_pool_step_dev(nc_encodec_stream_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                                 const int32_t* flush, const int64_t* frame_lens, const void* in_packed,
+                                                 const float* scales_in, void* out_packed, float* scales_out, float* emb_packed,
+                                                 int64_t out_cap, int32_t* n_frames, int64_t* n_out);
 
 /* ------------------------------------------------------------------------------- code containers
  * Device-side bit packing of code tensors: the wire layout of the reference's BitPacker / BitUnpacker

@@ -204,6 +204,16 @@ SYMBOLS = [
     ("nc_encodec_encode_ragged_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("nc_encodec_decode_ragged", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P]),
     ("nc_encodec_decode_ragged_dev", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("nc_encodec_stream_plan", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
+                                         C.POINTER(NcEncodecRaggedPlan), _P, C.c_int64, _P, _P, _P]),
+    ("nc_encodec_stream_pool_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("nc_encodec_stream_pool_destroy", C.c_int, [_P]),
+    ("nc_encodec_stream_pool_reset_slot", C.c_int, [_P, C.c_int32]),
+    ("nc_encodec_stream_pool_pending", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nc_encodec_stream_pool_query", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("nc_encodec_stream_pool_plan", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(NcEncodecRaggedPlan), _P, C.c_int64]),
+    ("nc_encodec_stream_pool_step", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    ("nc_encodec_stream_pool_step_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("nc_packed_bytes", C.c_int64, [C.c_int64, C.c_int32]),
     ("nc_pack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     ("nc_unpack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <map>
 
+#include "nc_encodec_rows.h"
 #include "nc_guard.h"
 #include "nc_ragged.h"
 
@@ -28,42 +29,7 @@ namespace nc {
 
 namespace {
 
-// the best measured value of profiles/encodec_ragged_bench.json
-constexpr int32_t kDefaultRaggedRows = 128;
-
-// ---- overlap-add over all clips ----------------------------------------------------------------------------------------------------
-struct OlaClip {             // one (clip, channel) of the output
-    int64_t out, total;      // first element in pcm_packed, samples
-    int64_t first;           // the clip's frame 0 in the frame table
-    int64_t L0;              // length of frame 0: the clip's window (a clip shorter than a segment has its own)
-    int32_t nfr, ch;
-    float eps;               // AudioTensorDSP.cs:246-252: 1e-10f where some weight sum is <= 1e-10f, else 0
-    int32_t pad_;
-};
-struct OlaFrame { int64_t off, len; };   // row [channels][len] of a decoded frame in the arena (elements)
-
-// DSP.LinearOverlapAdd for sample t of one (clip, channel): the arithmetic of ola_tables + overlap_add_kernel (nc_encodec.hip), operation
-// for operation -- w[q] = 0.5f - |(float)((q + 1) / (double)(L0 + 1)) - 0.5f|, the weight sum added up in fp32 in ascending frame order
-// from 0.0f, a = a + x * w in the same order, one division.  Only the frames that can cover t are visited: the others add nothing on the
-// host either (no frame is longer than the first, checked before the launch).
-__device__ __forceinline__ float ola_sample(const OlaClip& d, const OlaFrame* __restrict__ fr, const float* __restrict__ frames, int64_t stride, int64_t t) {
-    const int64_t f_lo = t >= d.L0 ? (t - d.L0) / stride + 1 : 0;
-    const int64_t f_hi = min((int64_t)d.nfr - 1, t / stride);
-    const double den = (double)(d.L0 + 1);
-    float a = 0.0f, sw = 0.0f;
-    for (int64_t f = f_lo; f <= f_hi; ++f) {
-        const OlaFrame g = fr[d.first + f];
-        const int64_t q = t - f * stride;
-        if (q >= 0 && q < g.len) {
-            const float tt = (float)((double)(q + 1) / den);
-            const float w = 0.5f - fabsf(tt - 0.5f);
-            a = a + frames[g.off + (int64_t)d.ch * g.len + q] * w;
-            sw = sw + w;
-        }
-    }
-    return a / (sw + d.eps);   // (eps = 0: sw + 0.0f is sw)
-}
-
+// ---- overlap-add over all clips (OlaClip, OlaFrame, ola_sample, ola_eps: nc_encodec_rows.h) -----------------------------------------
 // blockIdx.y = (clip, channel), blockIdx.x strides over its samples.  Memory-bound, no LDS, no atomics; the output row is split at its
 // first 16-byte boundary (scalar head), whole 16-byte stores, scalar tail; the frames are read at any alignment.
 __global__ __launch_bounds__(256) void overlap_add_ragged_kernel(const OlaClip* __restrict__ clips, const OlaFrame* __restrict__ fr,
@@ -88,30 +54,7 @@ __global__ __launch_bounds__(256) void overlap_add_ragged_kernel(const OlaClip* 
     if (tid < total - tail0) o[tail0 + tid] = ola_sample(d, fr, frames, stride, tail0 + tid);
 }
 
-// The host's `+ 1e-10` branch (ola_tables): taken when some weight sum is <= 1e-10f.  The window is unimodal (t rises with i and both
-// roundings are monotone), so every value is >= the smaller of its two ends; where every sample is covered (no frame but the last is
-// shorter than the stride) a weight sum is a sum of at least one such value.  Only where that bound does not decide it -- windows of
-// more than 2^25 samples, whose ends round to zero, or frames that leave gaps -- are the sums added up as the host does.
-float ola_eps(const std::vector<int64_t>& flen, int64_t stride, int64_t total) {
-    const int64_t L0 = flen[0];
-    auto w = [&](int64_t i) {
-        const float t = (float)((double)(i + 1) / (double)(L0 + 1));
-        return 0.5f - std::fabs(t - 0.5f);
-    };
-    bool covered = true;
-    for (size_t f = 0; f + 1 < flen.size(); ++f) covered = covered && flen[f] >= stride;
-    if (covered && std::min(w(0), w(L0 - 1)) > 1e-10f) return 0.0f;
-    std::vector<float> sw((size_t)total, 0.0f);
-    for (size_t f = 0; f < flen.size(); ++f)
-        for (int64_t i = 0; i < flen[f]; ++i) sw[(size_t)((int64_t)f * stride + i)] = sw[(size_t)((int64_t)f * stride + i)] + w(i);
-    float mn = INFINITY;
-    for (float v : sw) mn = std::min(mn, v);
-    return mn <= 1e-10f ? 1e-10f : 0.0f;
-}
-
 // ---- planner -----------------------------------------------------------------------------------------------------------------------
-struct ErRow { int32_t clip, seg; int64_t off, len, frames, key; };
-struct ErBatch { int64_t key; size_t first, count; };
 struct ErPlan {
     std::vector<ErRow> rows;          // launch order
     std::vector<ErBatch> batches;
@@ -143,18 +86,7 @@ ErPlan make_plan(const EncodecModel& m, bool decode, int B, const int64_t* lengt
         P.total_frames += fr;
         P.total_decoded += P.decoded.back();
     }
-    std::stable_sort(P.rows.begin(), P.rows.end(), [](const ErRow& a, const ErRow& b) {
-        if (a.key != b.key) return a.key > b.key;
-        if (a.seg != b.seg) return a.seg < b.seg;
-        return a.clip < b.clip;
-    });
-    for (size_t r = 0; r < P.rows.size();) {
-        size_t e = r;
-        while (e < P.rows.size() && P.rows[e].key == P.rows[r].key) ++e;
-        ++P.n_keys;
-        for (; r < e; r += (size_t)P.max_rows) P.batches.push_back({P.rows[r].key, r, std::min<size_t>((size_t)P.max_rows, e - r)});
-        r = e;
-    }
+    P.n_keys = er_batches(P.rows, P.max_rows, P.batches);
     return P;
 }
 
@@ -169,45 +101,6 @@ void report(const EncodecModel& m, const ErPlan& P, nc_encodec_ragged_plan* out,
             const ErRow& w = P.rows[r];
             rows[r] = {w.clip, w.seg, (int32_t)bi, (int32_t)(r - P.batches[bi].first), w.off, w.len, w.frames};
         }
-}
-
-// What the stacks would raise on a row ("segment too short": a residual block whose branch outgrows its shortcut), decided on the pad
-// plans alone, per distinct key; the first clip in index order that holds such a row is named.
-void check_rows(const EncodecModel& m, const ErPlan& P, bool decode) {
-    std::map<int64_t, std::pair<nc_status, std::string>> verdict;
-    int bad_clip = -1;
-    const std::pair<nc_status, std::string>* bad = nullptr;
-    for (const ErRow& w : P.rows) {
-        auto it = verdict.find(w.key);
-        if (it == verdict.end()) {
-            std::pair<nc_status, std::string> v{NC_OK, std::string()};
-            try {
-                int C = 0; int64_t L = 0;
-                m.trace_shape(decode, w.key, m.trace_taps() - 1, &C, &L);
-                if (decode && L != w.len) fail(NC_ESTATE, "internal: %lld frames decode to %lld samples, planned %lld", (long long)w.key, (long long)L, (long long)w.len);
-            } catch (const Error& e) { v = {e.code, e.what()}; }
-            it = verdict.emplace(w.key, v).first;
-        }
-        if (it->second.first != NC_OK && (bad_clip < 0 || w.clip < bad_clip)) { bad_clip = w.clip; bad = &it->second; }
-    }
-    if (bad) fail(bad->first, "clip %d: %s", bad_clip, bad->second.c_str());
-}
-
-// Lanes: every batch goes to the stream with the least work so far, the work of a batch being its dependent LSTM steps (the chain the
-// call is bound by; a launch of the persistent kernel holds 32 rows) -- the first, largest batch lands on the handle's stream.
-std::vector<int> assign_lanes(const ErPlan& P) {
-    static const bool no_overlap = env_flag("NC_ENCODEC_NO_OVERLAP");
-    std::vector<int> lanes;
-    int64_t load[3] = {0, 0, 0};
-    for (const ErBatch& b : P.batches) {
-        int l = 0;
-        if (!no_overlap)
-            for (int i = 1; i < 3; ++i)
-                if (load[i] < load[l]) l = i;
-        load[l] += P.rows[b.first].frames * (int64_t)((b.count + 31) / 32) + 8;
-        lanes.push_back(l);
-    }
-    return lanes;
 }
 
 struct Offsets { std::vector<int64_t> samples, frames, rows, decoded; std::vector<int64_t> before; };   // prefix sums per clip; frames before a row within its clip
@@ -230,12 +123,6 @@ Offsets offsets_of(const ErPlan& P, int B, const int64_t* lengths) {
     return o;
 }
 
-struct LaneScope {   // the pool in three lanes for the length of a ragged call
-    EncodecModel& m;
-    explicit LaneScope(EncodecModel& m_) : m(m_) { m.pool_lanes = 3; m.pool_lane = 0; m.pool_i = 0; }
-    ~LaneScope() { m.pool_lanes = 1; m.pool_lane = 0; m.pool_i = 0; }
-};
-
 }  // namespace
 
 // ===================================================================================================================== Encode
@@ -244,7 +131,7 @@ void EncodecModel::encode_ragged_dev(const float* pcm, int B, const int64_t* len
     if (!pcm || !codes || !lengths) fail(NC_EINVAL, "%s: null pointer", what);
     const ErPlan P = make_plan(*this, false, B, lengths, ragged_rows, what);
     if (!loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
-    check_rows(*this, P, false);
+    er_check_rows(*this, P.rows, false, "clip", nullptr);
     const int C = cfg.channels, D = cfg.dimension, nq = n_q;
     const bool want_sc = cfg.normalize && scales;
     const Offsets o = offsets_of(P, B, lengths);
@@ -285,7 +172,7 @@ void EncodecModel::encode_ragged_dev(const float* pcm, int B, const int64_t* len
     check_async_errors();   // an earlier device-pointer call on this handle may have timed out unnoticed
     LaneScope lanes(*this);
     rg_upload(*this, t);
-    run_batches(assign_lanes(P), true, [&](size_t i) {
+    run_batches(er_assign_lanes(P.rows, P.batches), true, [&](size_t i) {
         const ErBatch& bt = P.batches[i];
         const int N = (int)bt.count;
         const int64_t L = bt.key, Tz = P.rows[bt.first].frames;
@@ -310,7 +197,7 @@ void EncodecModel::decode_ragged_dev(const int64_t* codes, const float* scales, 
     if (!loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
     if (nq <= 0 || nq > cfg.n_codebooks) fail(NC_EINVAL, "codes carry %d codebooks; the model has %d", nq, cfg.n_codebooks);
     if (cfg.normalize && !scales) fail(NC_EINVAL, "this model normalises frames: scales must be given");
-    check_rows(*this, P, true);
+    er_check_rows(*this, P.rows, true, "clip", nullptr);
     const int C = cfg.channels;
     const bool segmented = cfg.segment_length > 0;
     const int64_t stride = cfg.segment_stride;
@@ -343,7 +230,7 @@ void EncodecModel::decode_ragged_dev(const int64_t* codes, const float* scales, 
             arena_off.push_back(arena);
             for (int64_t r = 0; r < N; ++r) {
                 const ErRow& w = P.rows[bt.first + (size_t)r];
-                ftab[(size_t)(o.rows[(size_t)w.clip] + w.seg)] = {arena + r * C * Lo, Lo};
+                ftab[(size_t)(o.rows[(size_t)w.clip] + w.seg)] = {arena + r * C * Lo, Lo, Lo};
             }
             arena += N * C * Lo;
         }
@@ -376,7 +263,7 @@ void EncodecModel::decode_ragged_dev(const int64_t* codes, const float* scales, 
     LaneScope lanes(*this);
     if (segmented) rg_frames.reserve((size_t)arena * 4);
     const char* extra = rg_upload(*this, t);
-    run_batches(assign_lanes(P), true, [&](size_t i) {
+    run_batches(er_assign_lanes(P.rows, P.batches), true, [&](size_t i) {
         const ErBatch& bt = P.batches[i];
         const int N = (int)bt.count;
         const int64_t Tz = bt.key, Lo = P.rows[bt.first].len;
@@ -409,21 +296,6 @@ void EncodecModel::decode_ragged_dev(const int64_t* codes, const float* scales, 
 using namespace nc;
 
 namespace {
-
-// A host-pointer call on the handle's own stream, as encodec_host_call of nc_api.hip: a persistent-LSTM timeout left behind by an earlier
-// device-pointer call is noted and is not this call's failure; a timeout of this call's own switches the handle to the step-wise kernels
-// and the launches run once more.
-template <class Run>
-void host_run(EncodecModel& m, Run&& run) {
-    m.lstm.note_timeout();
-    for (int attempt = 0;; ++attempt) {
-        run();
-        NC_HIP(hipStreamSynchronize(m.stream));
-        if (!m.lstm.timed_out() || attempt) break;
-        try { m.check_async_errors(); } catch (const Error&) {}
-    }
-    m.check_async_errors();
-}
 
 void h2d(DevBuf& d, const void* h, size_t n, hipStream_t s) {
     d.reserve(std::max<size_t>(n, 16));
@@ -489,7 +361,7 @@ nc_status nc_encodec_encode_ragged(nc_codec* h, const float* pcm_packed, int32_t
         if (!pcm_packed || !codes_packed || !lengths) fail(NC_EINVAL, "%s: null pointer", what);
         const ErPlan P = make_plan(m, false, B, lengths, m.ragged_rows, what);
         if (!m.loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
-        check_rows(m, P, false);   // every refusal before the first copy
+        er_check_rows(m, P.rows, false, "clip", nullptr);   // every refusal before the first copy
         int64_t samples = 0;
         for (int b = 0; b < B; ++b) samples += lengths[b];
         const size_t n_in = (size_t)m.cfg.channels * samples * 4, n_codes = (size_t)m.n_q * P.total_frames * 8, n_sc = P.rows.size() * 4,
@@ -499,7 +371,7 @@ nc_status nc_encodec_encode_ragged(nc_codec* h, const float* pcm_packed, int32_t
         m.rg_out.reserve(n_codes); m.ck_b.reserve(n_sc);
         if (emb_packed) m.ck_out.reserve(n_emb);
         h2d(m.rg_in, pcm_packed, n_in, m.stream);
-        host_run(m, [&] {
+        encodec_host_run(m, [&] {
             m.encode_ragged_dev(m.rg_in.as<float>(), B, lengths, m.rg_out.as<int64_t>(), m.ck_b.as<float>(), emb_packed ? m.ck_out.as<float>() : nullptr);
         });
         NC_HIP(hipMemcpyAsync(codes_packed, m.rg_out.p, n_codes, hipMemcpyDeviceToHost, m.stream));
@@ -519,14 +391,14 @@ nc_status nc_encodec_decode_ragged(nc_codec* h, const int64_t* codes_packed, con
         if (!m.loaded) fail(NC_ESTATE, "weights not loaded (call nc_codec_load_weights first)");
         if (n_q <= 0 || n_q > m.cfg.n_codebooks) fail(NC_EINVAL, "codes carry %d codebooks; the model has %d", n_q, m.cfg.n_codebooks);
         if (m.cfg.normalize && !scales_packed) fail(NC_EINVAL, "this model normalises frames: scales must be given");
-        check_rows(m, P, true);
+        er_check_rows(m, P.rows, true, "clip", nullptr);
         const size_t n_codes = (size_t)n_q * P.total_frames * 8, n_sc = P.rows.size() * 4, n_out = (size_t)m.cfg.channels * P.total_decoded * 4;
         m.use_device();
         OwnStreamScope own(m);
         m.rg_out.reserve(n_out);
         h2d(m.rg_in, codes_packed, n_codes, m.stream);
         if (scales_packed) h2d(m.ck_a, scales_packed, n_sc, m.stream);
-        host_run(m, [&] {
+        encodec_host_run(m, [&] {
             m.decode_ragged_dev(m.rg_in.as<int64_t>(), scales_packed ? m.ck_a.as<float>() : nullptr, B, lengths, n_q, m.rg_out.as<float>());
         });
         NC_HIP(hipMemcpyAsync(pcm_packed, m.rg_out.p, n_out, hipMemcpyDeviceToHost, m.stream));

@@ -369,6 +369,8 @@ struct EncodecModel : Codec {
     DevBuf rg_frames;               // decoded frames of all batches of a ragged decode, alive until its one overlap-add launch
     void encode_ragged_dev(const float* pcm, int B, const int64_t* lengths, int64_t* codes, float* scales, float* emb);
     void decode_ragged_dev(const int64_t* codes, const float* scales, int B, const int64_t* lengths, int nq, float* pcm);
+    // Stream pool (nc_encodec_stream.hip): segments of live streams pooled into the same batches; its steps call encode_batch / decode_batch
+    friend struct ::nc_encodec_stream_pool;
     float* alloc(size_t n_floats);   // the next buffer of the pool (of the running batch's lane), grown to n_floats
     // Test hook (nc_op_encodec_trace).  A tap is every activation view the driver holds between launches, numbered in the order the
     // driver produces them: encoder = first conv | per stage: shortcut s, branch h, branch y, down-conv | LSTM | last conv; decoder =

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from .config import EncodecConfig
+from .session import FLUSH
 from .weights import save_blob
 
 
@@ -380,3 +381,230 @@ class Encodec(_lib.ProfileMixin):
             _lib.check(_lib.lib().nc_encodec_decode_ragged(self._h, codes.ctypes.data, scales.ctypes.data if scales is not None else None,
                                                            B, larr, nq, out.ctypes.data))
         return [p.reshape(Cn, -1) for p in _lib.split_packed(out, [Cn * d for d in dls])]
+
+    # ---- stream pool (PCM or frames that arrive over time; segmented models) ----------------------
+    def encode_pool(self, n_slots: int) -> "EncodecStreamPool":
+        """nc_encodec_stream_pool_create(decode = 0): n_slots live streams encoded segment by segment as their samples arrive."""
+        return EncodecStreamPool(self, False, n_slots, None)
+
+    def decode_pool(self, n_slots: int, n_q: Optional[int] = None) -> "EncodecStreamPool":
+        """nc_encodec_stream_pool_create(decode = 1): n_slots live streams decoded frame by frame (n_q: codebooks in the pushed codes;
+        None = the handle's bandwidth)."""
+        return EncodecStreamPool(self, True, n_slots, n_q)
+
+    def encode_session(self) -> "EncodecStreamSession":
+        return EncodecStreamSession(self.encode_pool(1))
+
+    def decode_session(self, n_q: Optional[int] = None) -> "EncodecStreamSession":
+        return EncodecStreamSession(self.decode_pool(1, n_q))
+
+
+def encodec_stream_plan(config: EncodecConfig, pushed, emitted, n_in, flush=None, frame_lens=None, decode: bool = False, max_rows: int = 0):
+    """nc_encodec_stream_plan: one step of a stream pool from a config alone, no device needed.  Stream i has received pushed[i] samples
+    (decode: frames) and emitted emitted[i] segments (decode: samples per channel); it now brings n_in[i] more and flushes where flush[i].
+    -> (plan dict, rows in launch order -- `clip` is the stream's index --, per stream {n_frames, code_frames, n_samples})."""
+    c = _c_config(config)
+    n = len(n_in)
+    pu, em, ni = _lib.i64_array(pushed), _lib.i64_array(emitted), _lib.i64_array(n_in)
+    fl = (C.c_int32 * max(1, n))(*[int(bool(f)) for f in flush]) if flush is not None else None
+    fr = _lib.i64_array(frame_lens) if frame_lens is not None else None
+    nf, cf, ns = (C.c_int32 * max(1, n))(), (C.c_int64 * max(1, n))(), (C.c_int64 * max(1, n))()
+    p = _lib.NcEncodecRaggedPlan()
+    call = lambda rows, cap: _lib.lib().nc_encodec_stream_plan(C.byref(c), 1 if decode else 0, n, pu, em, ni, fl, fr, int(max_rows), C.byref(p), rows, cap, nf, cf, ns)  # noqa: E731
+    _lib.check(call(None, 0))
+    rows = (_lib.NcEncodecRaggedRow * max(1, int(p.n_rows)))()
+    _lib.check(call(rows, int(p.n_rows)))
+    plan = {k: int(getattr(p, k)) for k, _ in _lib.NcEncodecRaggedPlan._fields_}
+    return (plan, [{k: int(getattr(rows[i], k)) for k, _ in _lib.NcEncodecRaggedRow._fields_} for i in range(int(p.n_rows))],
+            [{"n_frames": int(nf[i]), "code_frames": int(cf[i]), "n_samples": int(ns[i])} for i in range(n)])
+
+
+class EncodecStreamPool:
+    """n_slots independent live streams on one segmented Encodec model, one direction, stepped together (nc_encodec_stream_pool_*).
+
+        out = pool.step({slot: x | FLUSH | (x, FLUSH), ...})
+
+    encode pool: x is PCM [channels, n] (any n >= 0); out[slot] is the list of EncodedFrame (leading batch of 1) of the segments the push
+    completed -- often empty.  decode pool: x is a list of EncodedFrame [1, n_q, F]; out[slot] is PCM [channels, n_out].  FLUSH ends the
+    slot's stream (after the last x of a tuple) and emits the rest; reset_slot() makes the slot new.  Everything a slot emitted, end to
+    end, equals encode() / decode() on the whole stream, bit for bit.  numpy in, numpy out (host API); torch device tensors in, device
+    tensors out on torch's current stream."""
+
+    def __init__(self, model: Encodec, decode: bool, n_slots: int, n_q: Optional[int]):
+        self.model, self.decode, self.n_slots = model, bool(decode), int(n_slots)
+        self._p = C.c_void_p()
+        self._torch = False
+        _lib.check(_lib.lib().nc_encodec_stream_pool_create(model._h, 1 if decode else 0, int(n_slots), int(n_q or 0), C.byref(self._p)))
+        self.n_q = int(n_q) if n_q else model.query(1)[1]
+
+    def close(self) -> None:
+        if getattr(self, "_p", None) is not None and self._p.value:
+            try:
+                _lib.lib().nc_encodec_stream_pool_destroy(self._p)
+            finally:
+                self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset_slot(self, slot: int) -> None:
+        _lib.check(_lib.lib().nc_encodec_stream_pool_reset_slot(self._p, int(slot)))
+
+    def pending(self, slot: int) -> int:
+        n = C.c_int64()
+        _lib.check(_lib.lib().nc_encodec_stream_pool_pending(self._p, int(slot), C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _split(v):
+        """an entry's value -> (data or None, flush)"""
+        if v is FLUSH:
+            return None, True
+        if isinstance(v, tuple) and len(v) == 2 and v[1] is FLUSH:
+            return v[0], True
+        if v is None:
+            raise ValueError("the pushed data must not be null (FLUSH ends a stream)")
+        return v, False
+
+    def _entries(self, entries: dict):
+        if not entries:
+            raise ValueError("a step needs at least one entry")
+        slots, data, flush = [], [], []
+        for s, v in entries.items():
+            d, f = self._split(v)
+            slots.append(int(s)); data.append(d); flush.append(f)
+        Cn = self.model.config.channels
+        if self.decode:
+            data = [[] if d is None else list(d) for d in data]
+            for fl in data:
+                for f in fl:
+                    if f.codes is None or f.codes.ndim != 3 or f.codes.shape[0] != 1 or f.codes.shape[1] != self.n_q:
+                        raise ValueError(f"Invalid frame codes: every frame must be [1, {self.n_q}, T']")
+            n_in = [len(d) for d in data]
+            lens = [int(f.codes.shape[-1]) for fl in data for f in fl]
+            some = [f.codes for fl in data for f in fl]
+        else:
+            for d in data:
+                if d is not None and (d.ndim != 2 or d.shape[0] != Cn):
+                    raise ValueError(f"every push must be [{Cn}, n]")
+            n_in = [0 if d is None else int(d.shape[1]) for d in data]
+            lens = None
+            some = [d for d in data if d is not None]
+        if some:
+            self._torch = _is_torch(some[0])
+        return slots, data, flush, n_in, lens
+
+    def query(self, entries: dict) -> dict:
+        """{slot: (n_frames, code_frames, n_samples)} of the step these entries would be (nc_encodec_stream_pool_query)."""
+        slots, _, flush, n_in, lens = self._entries(entries)
+        return dict(zip(slots, zip(*self._query(slots, flush, n_in, lens))))
+
+    def _query(self, slots, flush, n_in, lens):
+        n = len(slots)
+        nf, cf, ns = (C.c_int32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+        _lib.check(_lib.lib().nc_encodec_stream_pool_query(self._p, n, (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush]),
+                                                           _lib.i64_array(lens) if lens is not None else None, nf, cf, ns))
+        return [int(x) for x in nf], [int(x) for x in cf], [int(x) for x in ns]
+
+    def plan(self, entries: dict):
+        """(plan, rows in launch order) of the step these entries would be under the pool's current state (nc_encodec_stream_pool_plan):
+        as encodec_stream_plan reports them, `clip` being the entry's index."""
+        slots, _, flush, n_in, lens = self._entries(entries)
+        return self._plan(slots, flush, n_in, lens)
+
+    def _plan(self, slots, flush, n_in, lens):
+        n = len(slots)
+        c_slots, c_n_in, c_flush = (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+        c_lens = _lib.i64_array(lens) if lens is not None else None
+        return _ragged_rows(lambda _n, _l, p, rows, cap: _lib.lib().nc_encodec_stream_pool_plan(self._p, n, c_slots, c_n_in, c_flush, c_lens, p, rows, cap),
+                            [], self.decode)
+
+    def step(self, entries: dict, return_emb: bool = False) -> dict:
+        slots, data, flush, n_in, lens = self._entries(entries)
+        n = len(slots)
+        nf, cf, ns = self._query(slots, flush, n_in, lens)                 # every refusal that needs no device, and the sizes
+        L, m = _lib.lib(), self.model
+        Cn, D, nq = m.config.channels, m.config.dimension, (self.n_q if self.decode else m.query(1)[1])
+        c_slots, c_n_in, c_flush = (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+        c_lens = _lib.i64_array(lens) if lens is not None else None
+        seg_frames = None
+        if not self.decode:                                                 # code frames of every segment an entry emits, in segment order
+            seg_frames = [[] for _ in slots]
+            for r in sorted(self._plan(slots, flush, n_in, lens)[1], key=lambda r: (r["clip"], r["segment"])):
+                seg_frames[r["clip"]].append(r["frames"])
+        on_dev = self._torch
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", m.device_index)
+            empty = lambda k, dt: torch.empty((max(1, k),), dtype=dt, device=dev)  # noqa: E731
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            f32, i64 = torch.float32, torch.int64
+            cat = lambda parts, dt: torch.cat([p.reshape(-1).to(dt) for p in parts]).contiguous() if parts else empty(0, dt)  # noqa: E731
+            m._bind_torch_stream()
+            fn = L.nc_encodec_stream_pool_step_dev
+        else:
+            empty = lambda k, dt: np.empty((max(1, k),), dt)  # noqa: E731
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            f32, i64 = np.float32, np.int64
+            cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dt).reshape(-1) for p in parts])) if parts else empty(0, dt)  # noqa: E731
+            fn = L.nc_encodec_stream_pool_step
+        if self.decode:
+            codes = cat([f.codes for fl in data for f in fl], i64)
+            scales = cat([f.scale for fl in data for f in fl], f32) if m.config.normalize else None
+            out = empty(Cn * sum(ns), f32)
+            _lib.check(fn(self._p, n, c_slots, c_n_in, c_flush, c_lens, ptr(codes), ptr(scales), ptr(out), None, None, Cn * sum(ns), None, None))
+            return {s: p.reshape(Cn, -1) for s, p in zip(slots, _lib.split_packed(out, [Cn * k for k in ns]))}
+        pcm = cat([d for d in data if d is not None], f32)
+        codes, scales = empty(nq * sum(cf), i64), empty(sum(nf), f32)
+        emb = empty(D * sum(cf), f32) if return_emb else None
+        _lib.check(fn(self._p, n, c_slots, c_n_in, c_flush, None, ptr(pcm), None, ptr(codes), ptr(scales), ptr(emb), nq * sum(cf), None, None))
+        res, embs, o, osc = {}, {}, 0, 0
+        for s, fr in zip(slots, seg_frames):
+            frames, es = [], []
+            for Tf in fr:
+                frames.append(EncodedFrame(codes[nq * o:nq * (o + Tf)].reshape(1, nq, Tf), scales[osc:osc + 1].reshape(1, 1) if m.config.normalize else None))
+                if return_emb:
+                    es.append(emb[D * o:D * (o + Tf)].reshape(1, D, Tf))
+                o += Tf
+                osc += 1
+            res[s], embs[s] = frames, es
+        return (res, embs) if return_emb else res
+
+
+class EncodecStreamSession:
+    """One live stream: a stream pool with one slot.  push(x) -> what became final; flush([x]) ends the stream; reset() starts anew."""
+
+    def __init__(self, pool: EncodecStreamPool):
+        self.pool = pool
+
+    def push(self, x, **kw):
+        out = self.pool.step({0: x}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def flush(self, x=None, **kw):
+        out = self.pool.step({0: FLUSH if x is None else (x, FLUSH)}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def pending(self) -> int:
+        return self.pool.pending(0)
+
+    def reset(self) -> None:
+        self.pool.reset_slot(0)
+
+    def close(self) -> None:
+        self.pool.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
