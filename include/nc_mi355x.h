@@ -853,6 +853,83 @@ NC_API nc_status nc_dia_generate_collect_dev(int device_index, const int32_t* ge
                                              const int32_t* prefill_steps, const int64_t* lengths, int64_t maxd, int64_t pad, int64_t* out,
                                              void* hip_stream);
 
+/* ------------------------------------------------------------------------------------ round-trip quality
+ * How good a decode is, next to the audio it came from: L1, SI-SDR and the multi-scale mel distance of the DAC paper, with the STFT and the
+ * mel spectrogram they stand on.  Every value is one fixed bit pattern (fl = one binary32 rounding; no libm on the data path; the units
+ * are built with -ffp-contract=off), stated here so that the *_host twins (csrc/nc_quality_host.hip: plain serial C++ on HOST pointers,
+ * no device, sharing nc_math.h and the table builders below with the kernels and nothing else) and the kernels agree bit for bit.
+ *   basis   window W (a power of two, 32..2048), k = 0..W/2, n = 0..W-1, evaluated in binary64 and rounded once:
+ *             C[k][n] = fl(w(n) cos(2 pi ((k n) mod W) / W)),  S[k][n] = fl(-w(n) sin(2 pi ((k n) mod W) / W))
+ *           window NC_WINDOW_HANN: w(n) = 0.5 - 0.5 cos(2 pi n / W) (torch.hann_window, periodic);  NC_WINDOW_ONES: w = 1.
+ *   STFT    center = true: reflect padding of W/2 each side (so n > W/2), hop H (1 <= H <= min(W, 512)), frames = 1 + n / H.
+ *           re[k][t] = ONE chain over n ascending of fmaf(C[k][n], x_pad[t H + n], acc) from acc = 0; im the same with S;
+ *           |X|[k][t] = sqrtf(fl(fl(re re) + fl(im im))).  Output layouts: complex64 [W/2+1][frames] (re, im interleaved).
+ *   mel     fb[m][k] and the support [lo[m], hi[m]) from nc_audio_mel_filterbank (n_fft = W);  mel[m][t] = ONE chain over k = lo..hi-1
+ *           ascending of fmaf(fb[m][k], |X|[k][t], acc) from 0; a band with empty support is 0.  Output float [n_mels][frames].
+ *   rows    a row is one channel of one clip (SISDRLoss.PrepareInputs); x = estimate, y = reference, n = compared samples.
+ *           Sums are binary64, serial: samples ascending within blocks of 128, then the blocks ascending.
+ *             n_bad  = the non-finite samples of x plus those of y;  l1 = fl(sum |fl(x - y)| / n)
+ *             xc = x - sum(x)/n, yc = y - sum(y)/n in binary64;  EPS = (double)1e-8f
+ *             scale = (sum(xc yc) + EPS) / (sum(yc yc) + EPS);  target = scale scale sum(yc yc);  error = sum((xc - scale yc)^2)
+ *             si_sdr_db = fl(10.0f * nc_log10f(fl(min(target / (error + EPS) + EPS, FLT_MAX))))      (the negative of SISDRLoss.forward)
+ *           per scale i, over the n_mels x frames mel values X (of x) and Y (of y): per frame the bands ascending, then the frames
+ *           ascending, in binary64:
+ *             mel_mag[i] = fl(sum |fl(X - Y)| / count);  mel_log[i] = fl(sum |fl(L(X) - L(Y))| / count),  L(v) = nc_log10f(fl(c c)),
+ *             c = max(v, clamp_eps)   (MelSpectrogramLoss.forward with pow = 2)
+ *             mel_distance = fl(sum_i (log_weight mean_log_i + mag_weight mean_mag_i)) on the binary64 means, i ascending
+ *           A row with n_bad != 0 has NaN in l1, si_sdr_db, mel_distance and the n_scales used mel entries; other rows are untouched.
+ * nc_quality_cfg: 1 <= n_scales <= 8; W[i] as above; H[i] = 0 means W[i] / 4; 1 <= n_mels[i] <= 512; fmax[i] = 0 means sample_rate / 2;
+ * clamp_eps >= 1e-18f (its square must be a normal binary32).  Reference defaults: clamp_eps 1e-5f, both weights 1.
+ * off[] / n[] / out_off[] / ref_off[] / est_off[] are HOST arrays of ELEMENT offsets and lengths into the packed buffers: the packed input
+ * of a ragged encode and the packed output of the ragged decode are compared in place.
+ * NC_EINVAL, before anything is launched: a null pointer; B < 1 or B > 32767; n[b] <= W/2 for a requested window; a negative offset; W not
+ * a power of two in 32..2048; H outside [1, min(W, 512)]; n_mels outside [1, 512]; sample_rate <= 0; fmin < 0; fmax <= fmin; an unknown
+ * window; n_scales outside [1, 8]; clamp_eps < 1e-18f or a weight that is not finite.
+ *
+ * replaces: DSP.STFT                                 AudioTools/AudioTensorDSP.cs:716-809 (nc_audio_stft_dev / _host; frames: the last
+ *           dimension of its result, -1 where n <= W/2)
+ * replaces: DSP.MelFilterbank                        AudioTools/AudioTensorDSP.cs:844-894 with HertzToMel / MelToHertz
+ *           (Utils/AudioExtensions.cs:31-44), in binary64, rounded once; fb [n_mels][n_fft/2+1], lo / hi [n_mels] (nullable).  The
+ *           reference builds it for max(W, 2048) (FFTLengths, :920), which its matmul cannot take for W < 2048; here n_fft = W.
+ * replaces: DSP.MelSpectrogram                       AudioTools/AudioTensorDSP.cs:595-669 (hann window)
+ * replaces: L1Loss / SISDRLoss / MelSpectrogramLoss  Modules/DAC/L1Loss.cs, SISDRLoss.cs:100-164, MelSpectrogramLoss.cs:116-137 as
+ *           per-row evaluation metrics: nc_quality_metrics_dev (DEVICE buffers and DEVICE out[B], asynchronous on `hip_stream`),
+ *           nc_quality_metrics (HOST buffers, synchronous) and nc_quality_metrics_host (no device). */
+#define NC_WINDOW_HANN 0
+#define NC_WINDOW_ONES 1
+#define NC_QUALITY_MAX_SCALES 8
+typedef struct nc_quality_cfg {
+    int32_t n_scales;
+    int32_t W[8], H[8], n_mels[8];   /* [NC_QUALITY_MAX_SCALES] each */
+    float fmin[8], fmax[8];
+    float clamp_eps, log_weight, mag_weight;
+} nc_quality_cfg;
+typedef struct nc_quality_row {
+    float l1, si_sdr_db, mel_distance;
+    float mel_log[8], mel_mag[8];    /* [NC_QUALITY_MAX_SCALES] each */
+    int32_t n_bad;
+} nc_quality_row;
+NC_API int64_t nc_audio_stft_frames(int64_t n, int32_t W, int32_t H);
+NC_API nc_status nc_audio_dft_basis(int32_t W, int32_t window, float* C /* [W/2+1][W] */, float* S);
+NC_API nc_status nc_audio_mel_filterbank(int32_t sample_rate, int32_t n_mels, int32_t n_fft, float fmin, float fmax, float* fb, int32_t* lo,
+                                         int32_t* hi);
+NC_API nc_status nc_audio_stft_dev(int device_index, const float* pcm, int32_t B, const int64_t* off, const int64_t* n, int32_t W, int32_t H,
+                                   int32_t window, float* out_c64, const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_stft_host(const float* pcm, int32_t B, const int64_t* off, const int64_t* n, int32_t W, int32_t H, int32_t window,
+                                    float* out_c64, const int64_t* out_off);
+NC_API nc_status nc_audio_mel_spectrogram_dev(int device_index, const float* pcm, int32_t B, const int64_t* off, const int64_t* n,
+                                              int32_t sample_rate, int32_t W, int32_t H, int32_t n_mels, float fmin, float fmax, float* out,
+                                              const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_mel_spectrogram_host(const float* pcm, int32_t B, const int64_t* off, const int64_t* n, int32_t sample_rate, int32_t W,
+                                               int32_t H, int32_t n_mels, float fmin, float fmax, float* out, const int64_t* out_off);
+NC_API nc_status nc_quality_metrics_dev(int device_index, const float* ref, const int64_t* ref_off, const float* est, const int64_t* est_off,
+                                        const int64_t* n, int32_t B, int32_t sample_rate, const nc_quality_cfg* cfg, nc_quality_row* out,
+                                        void* hip_stream);
+NC_API nc_status nc_quality_metrics(int device_index, const float* ref, const int64_t* ref_off, const float* est, const int64_t* est_off,
+                                    const int64_t* n, int32_t B, int32_t sample_rate, const nc_quality_cfg* cfg, nc_quality_row* out);
+NC_API nc_status nc_quality_metrics_host(const float* ref, const int64_t* ref_off, const float* est, const int64_t* est_off, const int64_t* n,
+                                         int32_t B, int32_t sample_rate, const nc_quality_cfg* cfg, nc_quality_row* out);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE
@@ -1010,6 +1087,8 @@ NC_API nc_status nc_op_vq_gather(int device_index, const float* codebook, int32_
  * where *has_stats comes back 1.  out == NULL: only *C_out, *L_out and *n_taps (tap < 0: only *n_taps); nothing is launched. */
 NC_API nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* x, int32_t B, int64_t L, int32_t tap, float* out, float* stats,
                                      int32_t* C_out, int64_t* L_out, int32_t* n_taps, int32_t* has_stats);
+/* nc_log10f (csrc/nc_math.h, the canonical log10 of the quality metrics) on n positive normal binary32 values, evaluated on the host */
+NC_API nc_status nc_op_log10f(const float* x, int64_t n, float* y);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */
 NC_API nc_status nc_op_fold_weight_norm(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
 /* The HBM-bound SNAC kernels, one at a time (host pointers in and out, like nc_op_conv1d).

@@ -97,7 +97,18 @@ class NcDiaSampleParams(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class NcQualityCfg(C.Structure):
+    _fields_ = [("n_scales", C.c_int32), ("W", C.c_int32 * 8), ("H", C.c_int32 * 8), ("n_mels", C.c_int32 * 8), ("fmin", C.c_float * 8),
+                ("fmax", C.c_float * 8), ("clamp_eps", C.c_float), ("log_weight", C.c_float), ("mag_weight", C.c_float)]
+
+
+class NcQualityRow(C.Structure):
+    _fields_ = [("l1", C.c_float), ("si_sdr_db", C.c_float), ("mel_distance", C.c_float), ("mel_log", C.c_float * 8), ("mel_mag", C.c_float * 8),
+                ("n_bad", C.c_int32)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
+NC_WINDOW_HANN, NC_WINDOW_ONES = 0, 1
 
 _lib = None
 
@@ -246,6 +257,17 @@ SYMBOLS = [
                                            C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
     ("nc_dia_generate_lengths", C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, C.POINTER(C.c_int64)]),
     ("nc_dia_generate_collect_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("nc_audio_stft_frames", C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ("nc_audio_dft_basis", C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    ("nc_audio_mel_filterbank", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
+    ("nc_audio_stft_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("nc_audio_stft_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("nc_audio_mel_spectrogram_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P,
+                                               _P, _P]),
+    ("nc_audio_mel_spectrogram_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    ("nc_quality_metrics_dev", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P, _P]),
+    ("nc_quality_metrics", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P]),
+    ("nc_quality_metrics_host", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),
@@ -278,6 +300,7 @@ SYMBOLS = [
     ("nc_op_vq_gather", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _P, C.c_int64]),
     ("nc_op_encodec_trace", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nc_op_log10f", C.c_int, [_P, C.c_int64, _P]),
     ("nc_op_fold_weight_norm", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
     ("nc_op_dwconv1d", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("nc_op_layer_norm", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P]),

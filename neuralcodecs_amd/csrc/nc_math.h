@@ -105,6 +105,29 @@ NC_HD float nc_snakef(float x, float alpha, float inv) {
 NC_HD float nc_eluf(float x) { return x > 0.0f ? x : nc_expf(x) - 1.0f; }
 NC_HD float nc_sigmoidf(float x) { return 1.0f / (1.0f + nc_expf(-x)); }
 
+// log10 of a positive normal binary32 (the quality metrics: MelSpectrogramLoss.cs:128-129 log10, SISDRLoss.cs:141).  x = 2^k m with m in
+// [sqrt(1/2), sqrt(2)), f = m - 1 (exact), s = f / (2 + f), z = s^2: ln m = f - f^2/2 + s (f^2/2 + z G(z)); then ln m / ln 10 and
+// k log10(2), both constants as a binary32 pair.  Zero, subnormals, negatives, inf and NaN are outside the domain (callers clamp first).
+// Measured against binary64 per decade of x: tests/golden/quality_bounds.json.
+NC_HD float nc_log10f(float x) {
+    const uint32_t ix = __builtin_bit_cast(uint32_t, x) - 0x3f3504f3u;
+    const int32_t k = (int32_t)ix >> 23;
+    const float m = __builtin_bit_cast(float, (ix & 0x007fffffu) + 0x3f3504f3u);
+    const float f = m - 1.0f;
+    const float s = f / (2.0f + f);
+    const float z = s * s;
+    float g = 0x1.de41bap-3f;
+    g = nc_fma(g, z, 0x1.245a32p-2f);
+    g = nc_fma(g, z, 0x1.9999f0p-2f);
+    g = nc_fma(g, z, 0x1.555556p-1f);
+    const float h = 0.5f * f * f;
+    const float ln = f - (h - s * nc_fma(z, g, h));
+    float r = nc_fma(ln, 0x1.bcb7b2p-2f, ln * -0x1.5b235ep-27f);
+    const float kf = (float)k;
+    r = nc_fma(kf, -0x1.ec10c0p-27f, r);
+    return nc_fma(kf, 0x1.344136p-2f, r);
+}
+
 #if defined(__HIPCC__)
 // Two-at-a-time forms for the device kernels: the SAME operation sequences on a pair of values, written on 2-vectors so that the
 // multiplies / fmas / adds compile to the packed fp32 instructions of gfx950 (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two

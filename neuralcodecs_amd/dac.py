@@ -290,6 +290,16 @@ class DAC(_lib.ProfileMixin):
             _lib.check(_lib.lib().nc_dac_decode_codes_ragged(self._h, flat.ctypes.data, B, _lib.i64_array(frames), nq, pcm.ctypes.data))
         return _lib.split_packed(pcm, sizes)
 
+    def round_trip_quality(self, pcm_list, n_quantizers: Optional[int] = None, scales=None):
+        """Encode -> decode -> nc_quality_metrics_dev on a list of clips of any lengths, everything on the device: per row (one channel of
+        one clip) l1, si_sdr_db, mel_distance, mel_log / mel_mag and n_bad of the decode against the clip (neuralcodecs_amd/quality.py;
+        scales: a QualityConfig, default the DAC paper's evaluation set).  numpy clips in, numpy out; device tensors in, tensors out."""
+        from . import quality
+        clips, was_torch = quality.on_device(pcm_list)
+        dec = self.decode_codes_ragged(self.encode_ragged(clips, n_quantizers))
+        ref, est = quality.round_trip_rows(clips, dec)
+        return quality.hand_back(quality.quality_metrics(ref, est, sample_rate=self.config.sample_rate, scales=scales), was_torch)
+
     # ---- incremental sessions (codes or PCM pushed as they arrive) ---------------------------------
     def decode_session(self, B: int, n_quantizers: Optional[int] = None):
         """nc_session_create(decode): push codes [B, n_q, n] as a model emits them, get the PCM that became final; the pieces

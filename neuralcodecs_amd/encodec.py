@@ -382,6 +382,16 @@ class Encodec(_lib.ProfileMixin):
                                                            B, larr, nq, out.ctypes.data))
         return [p.reshape(Cn, -1) for p in _lib.split_packed(out, [Cn * d for d in dls])]
 
+    def round_trip_quality(self, pcm_list, scales=None):
+        """Encode -> decode -> nc_quality_metrics_dev on a list of clips of any lengths, everything on the device: per row (one channel of
+        one clip) l1, si_sdr_db, mel_distance, mel_log / mel_mag and n_bad of the decode against the clip (neuralcodecs_amd/quality.py;
+        scales: a QualityConfig, default the DAC paper's evaluation set).  numpy clips in, numpy out; device tensors in, tensors out."""
+        from . import quality
+        clips, was_torch = quality.on_device(pcm_list)
+        dec = self.decode_ragged(self.encode_ragged(clips), lengths=[int(c.shape[-1]) for c in clips])
+        ref, est = quality.round_trip_rows(clips, dec)
+        return quality.hand_back(quality.quality_metrics(ref, est, sample_rate=self.config.sampling_rate, scales=scales), was_torch)
+
     # ---- stream pool (PCM or frames that arrive over time; segmented models) ----------------------
     def encode_pool(self, n_slots: int) -> "EncodecStreamPool":
         """nc_encodec_stream_pool_create(decode = 0): n_slots live streams encoded segment by segment as their samples arrive."""

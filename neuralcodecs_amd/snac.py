@@ -343,6 +343,16 @@ class SNAC(_lib.ProfileMixin):
                                                         seed & 0xFFFFFFFFFFFFFFFF, pcm.ctypes.data))
         return _lib.split_packed(pcm, sizes)
 
+    def round_trip_quality(self, pcm_list, scales=None, seed: int = 0):
+        """Encode -> decode -> nc_quality_metrics_dev on a list of clips of any lengths, everything on the device: per row (one channel of
+        one clip) l1, si_sdr_db, mel_distance, mel_log / mel_mag and n_bad of the decode against the clip (neuralcodecs_amd/quality.py;
+        scales: a QualityConfig, default the DAC paper's evaluation set).  numpy clips in, numpy out; device tensors in, tensors out."""
+        from . import quality
+        clips, was_torch = quality.on_device(pcm_list)
+        dec = self.decode_ragged(self.encode_ragged(clips), seed=seed)
+        ref, est = quality.round_trip_rows(clips, dec)
+        return quality.hand_back(quality.quality_metrics(ref, est, sample_rate=self.config.sample_rate, scales=scales), was_torch)
+
     # ---- incremental sessions (codes or PCM pushed as they arrive) ---------------------------------
     def decode_session(self, B: int, n_quantizers: Optional[int] = None):
         """nc_session_create(decode): push the code levels of the next frames (a multiple of align, each level at its own rate) with

@@ -49,3 +49,14 @@ def sin32(x):
 xs = np.linspace(-40, 40, 2000001)
 err = np.abs(sin32(xs).astype(np.float64) - np.sin(xs.astype(np.float32).astype(np.float64)))
 print("sin max abs err", err.max(), "in ulp(1)=", err.max() / 2 ** -24)
+
+# log10 (nc_log10f): x = 2^k * m, m in [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), z = s^2:
+# ln(1 + f) = 2 s + s z G(z) = f - f^2/2 + s (f^2/2 + z G(z)),  G(z) = (2 atanh(sqrt z) / sqrt z - 2) / z
+def fl(z):
+    r = np.sqrt(z)
+    return (2.0 * np.arctanh(r) / r - 2.0) / z
+cl = show("LOG", fit(fl, 1e-12, ((np.sqrt(2) - 1) / (np.sqrt(2) + 1)) ** 2 * 1.02, 3))
+import math
+for nm, v in (("1/ln10", 1.0 / math.log(10.0)), ("log10(2)", math.log10(2.0))):
+    hi = np.float32(v)
+    print(nm, float(hi).hex() + "f", float(np.float32(v - float(hi))).hex() + "f")

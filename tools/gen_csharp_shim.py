@@ -92,7 +92,9 @@ def parse_result_structs(path=HDR):
             if not decl:
                 continue
             ty, rest = decl.split(" ", 1)
-            fields += [(ty, nm.strip(), 0) for nm in rest.split(",")]
+            for nm in rest.split(","):
+                am = re.match(r"(\w+)\[(\d+)\]$", nm.strip())
+                fields.append((ty, am.group(1), int(am.group(2))) if am else (ty, nm.strip(), 0))
         out.append((m.group(3), fields))
     return out
 
