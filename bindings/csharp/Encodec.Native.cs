@@ -276,6 +276,80 @@ public sealed unsafe class EncodecNative : INeuralCodec
         return pcm;
     }
 
+    // ---- causal streams: PCM or code frames that arrive over time (causal models without segmentation; nc_encodec_causal_pool_*) -----
+    /// <summary>nSlots live streams on this causal, unsegmented model (the 24 kHz preset), one direction, stepped together, the SLSTM's
+    /// state carried from step to step; what a slot emits, end to end, is Encode / Decode on the whole stream, bit for bit.  The pool
+    /// borrows the model: destroy it first.  nQ (decode): codebooks in the pushed codes, 0 = the bandwidth in force.</summary>
+    public IntPtr CreateCausalPool(bool decode, int nSlots, int nQ = 0)
+    {
+        NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_create(_h, decode ? 1 : 0, nSlots, nQ, out IntPtr p));
+        return p;
+    }
+
+    public static void DestroyCausalPool(IntPtr pool) => NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_destroy(pool));
+
+    public static void ResetCausalSlot(IntPtr pool, int slot) => NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_reset_slot(pool, slot));
+
+    public static long CausalPending(IntPtr pool, int slot)
+    {
+        long n;
+        NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_pending(pool, slot, &n));
+        return n;
+    }
+
+    /// <summary>The windows a step would run under the pool's current state, in launch order (entry: the entry's index).</summary>
+    public static NcEncodecCausalRow[] CausalPlan(IntPtr pool, int[] slots, long[] nIn, int[] flush, out long nBatches)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        long nr, nb;
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_plan(pool, slots.Length, ps, pi, pf, null, 0, &nr, &nb));
+        var rows = new NcEncodecCausalRow[Math.Max(1, (int)nr)];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn) fixed (NcEncodecCausalRow* pr = rows)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_plan(pool, slots.Length, ps, pi, pf, pr, nr, &nr, &nb));
+        nBatches = nb;
+        return rows;
+    }
+
+    /// <summary>One step of a causal encode pool: entry i pushes nIn[i] samples of slot slots[i] ([Channels, nIn[i]], packed entry after
+    /// entry) and ends the stream where flush[i] != 0.  Returns the packed codes, [nQ, codeFrames[i]] per entry: the frames that became final.</summary>
+    public long[] CausalEncodeStep(IntPtr pool, int[] slots, long[] nIn, int[] flush, float[] pcmPacked, out long[] codeFrames)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        ArgumentNullException.ThrowIfNull(pcmPacked);
+        codeFrames = new long[slots.Length];
+        int nf, nQ;
+        long dec;
+        NcMi355x.Check(NcMi355x.nc_encodec_query(_h, 1, &nf, &nQ, null, 0, &dec));                    // n_q of the bandwidth in force
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pc = codeFrames)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_query(pool, slots.Length, ps, pi, pf, pc));
+        var codes = new long[Math.Max(1, nQ * codeFrames.Sum())];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pc = codes) fixed (float* pp = pcmPacked)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_step(pool, slots.Length, ps, pi, pf, pp, pc, null, codes.Length, null));
+        return codes;
+    }
+
+    /// <summary>One step of a causal decode pool: entry i pushes nIn[i] code frames of slot slots[i] ([nQ, nIn[i]], packed entry after
+    /// entry) and ends the stream where flush[i] != 0.  Returns the packed PCM, [Channels, nSamples[i]] per entry: the samples that became final.</summary>
+    public float[] CausalDecodeStep(IntPtr pool, int[] slots, long[] nIn, int[] flush, long[] codesPacked, out long[] nSamples)
+    {
+        ArgumentNullException.ThrowIfNull(slots);
+        ArgumentNullException.ThrowIfNull(nIn);
+        ArgumentNullException.ThrowIfNull(flush);
+        ArgumentNullException.ThrowIfNull(codesPacked);
+        nSamples = new long[slots.Length];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pn = nSamples)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_query(pool, slots.Length, ps, pi, pf, pn));
+        var pcm = new float[Math.Max(1, Channels * nSamples.Sum())];
+        fixed (int* ps = slots, pf = flush) fixed (long* pi = nIn, pc = codesPacked) fixed (float* pp = pcm)
+            NcMi355x.Check(NcMi355x.nc_encodec_causal_pool_step(pool, slots.Length, ps, pi, pf, pc, pp, null, pcm.Length, null));
+        return pcm;
+    }
+
     // ---- the reference's members, signature for signature ---------------------------------------------------------------------------
     public Tensor Decode(List<EncodedFrame> encodedFrames)                          // Models/Encodec.cs:213-235
     {

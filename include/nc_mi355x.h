@@ -261,7 +261,8 @@ NC_API nc_status nc_snac_halo(const nc_snac_config* cfg, nc_halo* out);
  *   NC_CHUNK_OFF             never chunk: long clips return NC_EUNSUPPORTED
  * Chunked calls keep device memory independent of the clip length: the arena is sized by chunk + halos, and the host-pointer
  * entry points upload and download per chunk.  nc_snac_encode_tensor*, nc_snac_process_audio and the group calls are never chunked.
- * Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context). */
+ * Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; a window of the 24 kHz model does not stand for the clip
+ * unless the LSTM's state is carried: live 24 kHz streams run through nc_encodec_causal_pool_*, "Encodec causal streams" below). */
 #define NC_CHUNK_AUTO 0
 #define NC_CHUNK_OFF (-1)
 NC_API nc_status nc_codec_set_chunk_frames(nc_codec* h, int64_t chunk_frames);
@@ -295,8 +296,8 @@ NC_API nc_status nc_codec_chunk_plan(const nc_codec* h, int32_t decode, int32_t 
  * for the whole batch; every refusal is decided before anything is launched.
  * Not offered in ragged form: the z / latents / zq outputs, the DAC code-matrix pair (Dia's delayed matrices of unequal valid lengths
  * decode through nc_dia_decode_output, "Dia output stage" below), nc_snac_encode_tensor and the group calls.
- * Encodec clips are never cut into windows (48 kHz is segmented per second already; the 24 kHz LSTM has unbounded context, so no window
- * of a clip stands for the clip): nc_codec_set_ragged_window / nc_codec_ragged_plan return NC_EUNSUPPORTED for Encodec handles.  Encodec
+ * Encodec clips are never cut into windows (48 kHz is segmented per second already; a window of a 24 kHz clip does not stand for the clip
+ * unless the LSTM's state is carried, which "Encodec causal streams" below does for live streams): nc_codec_set_ragged_window / nc_codec_ragged_plan return NC_EUNSUPPORTED for Encodec handles.  Encodec
  * has ragged calls of its own that pool the SEGMENTS of all clips, nc_encodec_*_ragged below ("Encodec ragged batches"). */
 typedef struct nc_ragged_plan {
     int64_t window_frames;     /* W */
@@ -382,9 +383,9 @@ NC_API nc_status nc_session_schedule(const nc_halo* halo, int32_t decode, int32_
 /* A session on a DAC or SNAC handle for B rows; decode != 0: codes in, PCM out, else PCM in, codes out.  n_q: the DAC codebooks a decode
  * session reads (0 = all; SNAC and encode sessions ignore it: an encode session writes every codebook).  Several sessions may live on one
  * handle: they share its arena and stream, and the caller serialises their calls like every other call on the handle.  A session
- * BORROWS its handle: destroy the sessions first.  Encodec handles return NC_EUNSUPPORTED (48 kHz is segmented per second already; the
- * 24 kHz LSTM has unbounded context, so no window stands for the clip; segmented Encodec models stream through
- * nc_encodec_stream_pool_* below).
+ * BORROWS its handle: destroy the sessions first.  Encodec handles return NC_EUNSUPPORTED: segmented Encodec models (48 kHz) stream through
+ * nc_encodec_stream_pool_* below, causal models without segmentation (24 kHz) through nc_encodec_causal_pool_*, which carries the LSTM's
+ * state ("Encodec causal streams").
  *   decode sessions  in: DAC codes [B, n_q, n]; SNAC every level at its own rate, [B, sum_i n / vq_strides[i]] as nc_snac_decode takes
  *                     them (n a multiple of align).  n_in = n frames.  out: PCM rows [B, out_cap], the first *n_out samples of a row valid.
  *                     SNAC with NoiseBlocks: `noise` holds the caller's noise for the pushed frames, one [B, 1, n * S_i] block per decoder
@@ -633,6 +634,84 @@ NC_API nc_status nc_encodec_stream_pool_step_dev(nc_encodec_stream_pool* p, int3
                                                  const int32_t* flush, const int64_t* frame_lens, const void* in_packed,
                                                  const float* scales_in, void* out_packed, float* scales_out, float* emb_packed,
                                                  int64_t out_cap, int32_t* n_frames, int64_t* n_out);
+
+/* ------------------------------------------------------------------------- Encodec causal streams
+ * replaces: Encodec.Encode / Encodec.Decode (Models/Encodec.cs:259-285, 213-235) with SLSTM.forward (Modules/Encodec/SLSTM.cs:40-57) carried
+ * across calls, for a caller whose PCM or code frames ARRIVE over time on a CAUSAL model without segmentation (the 24 kHz preset).  With
+ * causal == 1 no operator looks to the right (SConv1d pads on the left, SConvTranspose1d trims on the right, the SLSTM is
+ * unidirectional), so a stream that carries the LSTM's (h, c) forward never recomputes its past: what a slot emits, laid end to end, is
+ * bit for bit what nc_encodec_encode / nc_encodec_decode (B = 1) give on the whole stream -- codes, the emb hook and PCM.
+ * Admitted: causal != 0, segment_length == 0, normalize == 0, time_group_norm == 0; anything else answers NC_EUNSUPPORTED at create and
+ * names the condition.  Segmented models stream through nc_encodec_stream_pool_* above.
+ * hop = the product of the ratios.  A pool is n_slots independent streams on one handle, one direction; a step is n entries
+ * (slots[i], n_in[i], flush[i]) naming distinct slots (flush == NULL: nobody flushes).
+ *   encode pool (decode == 0)   an entry pushes n_in >= 0 samples, [channels, n_in], packed entry after entry in in_packed.  A stream
+ *       that has received T_s samples has emitted frames 0 .. floor(T_s / hop) - 1 once it holds min_frames_e frames (below that a push
+ *       only appends: the one-clip call's left reflect pad reads the first kernel_size - 1 samples and frames).  A step runs the
+ *       convolutional front on the window that starts halo_e frames before the first new frame (clamped to 0) and drops its first
+ *       halo_e frames, the LSTM on the new frames from the slot's (h, c), the last convolution on the carried last_kernel_size - 1 LSTM
+ *       frames + the new ones, the quantizer on the new frames.  flush != 0 runs the window up to the stream's true end (its right
+ *       reflect pad is then the one-clip call's), emits the remaining frames and ends the slot until ..._reset_slot; a stream flushed
+ *       below min_frames_e runs as the one-clip call on what it holds and answers what that call answers.  out_packed: int64 codes
+ *       [n_q, n_out[i]] entry after entry (n_q: the handle's bandwidth); emb_packed (nullable test hook): [dimension, n_out[i]].
+ *   decode pool (decode != 0; n_q fixed at create, 0 = the handle's bandwidth)   an entry pushes n_in >= 0 code frames: in_packed int64
+ *       [n_q, n_in] entry after entry.  Frames are held until the stream has min_frames_d of them; from then on a push of n frames emits
+ *       [channels, n * hop] samples -- after frames 0..k the samples [0, (k + 1) * hop) are final: no latency.  flush emits what is held
+ *       (as the one-clip call where the stream is shorter than min_frames_d) and ends the slot.  out_packed: float [channels, n_out[i]].
+ * Rows whose window width and number of new frames are equal run as one batch of at most the handle's ragged max_rows rows
+ * (nc_encodec_set_ragged_rows) through the unchanged launch sequences, keys in descending order: a lock-step step of n streams is one
+ * n-row launch sequence.  n_out[i] (nullable): code frames | samples per channel the entry emits; nc_encodec_causal_pool_query gives
+ * them beforehand.  out_cap: capacity of out_packed in elements (n_q * frames | channels * samples of all entries).  The *_dev form takes
+ * device pointers for the packed tensors and enqueues on the handle's stream; the plain form takes host pointers and is synchronous.
+ * nc_encodec_causal_pool_pending: Encode the samples received that no emitted frame covers, Decode the frames held and not yet decoded.
+ * Everything is decided before anything is launched, names the slot, and leaves every slot as it was -- NC_EINVAL: a null pointer,
+ * n <= 0, a slot out of range or named twice, n_in < 0, a push to an ended slot, a flush of a slot that has received nothing, out_cap
+ * below the query; NC_ESTATE without weights.  That guarantee covers the refusals, which are all decided at plan time; a step that fails
+ * AFTER its launches began (a HIP error, NC_EDEVICE) has already written the named slots' device state, so those slots are ended and take
+ * no push until nc_encodec_causal_pool_reset_slot; slots the step did not name are untouched.  A pool BORROWS its handle: destroy it first.
+ * nc_encodec_causal_plan is a host function (no handle, no device): stream i has received received[i] samples (Decode: frames) and
+ * emitted emitted[i] frames (Decode: decoded that many frames) and now brings n_in[i] / flush[i].  info (nullable): the halos and minimum
+ * windows of the config; rows (nullable, the first `cap`, in launch order): the windows that would run; n_out as above. */
+typedef struct nc_encodec_causal_info {
+    int64_t hop;
+    int64_t halo_e;         /* frames of the encoder front recomputed and dropped in front of the new ones */
+    int64_t halo_d;         /* LSTM-output frames the decoder's up-stack recomputes in front of the new ones */
+    int64_t min_frames_e;   /* frames a stream must hold before its first emission (encode) */
+    int64_t min_frames_d;   /* ... (decode) */
+    int64_t carry_e;        /* LSTM-output frames the encode slot carries: last_kernel_size - 1 */
+    int64_t carry_d;        /* code frames the decode slot carries: max(kernel_size - 1, min_frames_d - 1) */
+    int64_t taint_e;        /* samples-deep dependency model: frames at the LSTM input a window's left edge can reach (halo_e before the
+                               minimum-window rule is applied) */
+    int64_t taint_d;        /* decoded samples a window's left edge can reach (halo_d = ceil(taint_d / hop)) */
+} nc_encodec_causal_info;
+typedef struct nc_encodec_causal_row {
+    int32_t entry;          /* index of the entry (plan: of the stream) */
+    int32_t batch;          /* launch batch, in launch order */
+    int32_t row;            /* row within the batch */
+    int32_t one_clip;       /* 1: a stream flushed below the minimum, run as the one-clip call */
+    int64_t start;          /* first sample (Decode: first code frame) of the window in the stream */
+    int64_t width;          /* samples (Decode: code frames) of the window */
+    int64_t new_frames;     /* frames the row emits (Decode: frames it decodes) */
+} nc_encodec_causal_row;
+typedef struct nc_encodec_causal_pool nc_encodec_causal_pool;
+NC_API nc_status nc_encodec_causal_plan(const nc_encodec_config* cfg, int32_t decode, int32_t n, const int64_t* received, const int64_t* emitted,
+                                        const int64_t* n_in, const int32_t* flush, int32_t max_rows, nc_encodec_causal_info* info,
+                                        nc_encodec_causal_row* rows, int64_t cap, int64_t* n_rows, int64_t* n_batches, int64_t* n_out);
+NC_API nc_status nc_encodec_causal_pool_create(nc_codec* h, int32_t decode, int32_t n_slots, int32_t n_q, nc_encodec_causal_pool** out);
+NC_API nc_status nc_encodec_causal_pool_destroy(nc_encodec_causal_pool* p);
+NC_API nc_status nc_encodec_causal_pool_reset_slot(nc_encodec_causal_pool* p, int32_t slot);
+NC_API nc_status nc_encodec_causal_pool_pending(const nc_encodec_causal_pool* p, int32_t slot, int64_t* n);
+NC_API nc_status nc_encodec_causal_pool_query(const nc_encodec_causal_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                              const int32_t* flush, int64_t* n_out);
+NC_API nc_status nc_encodec_causal_pool_plan(const nc_encodec_causal_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                             const int32_t* flush, nc_encodec_causal_row* rows, int64_t cap, int64_t* n_rows,
+                                             int64_t* n_batches);
+NC_API nc_status nc_encodec_causal_pool_step(nc_encodec_causal_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                             const int32_t* flush, const void* in_packed, void* out_packed, float* emb_packed,
+                                             int64_t out_cap, int64_t* n_out);
+NC_API nc_status nc_encodec_causal_pool_step_dev(nc_encodec_causal_pool* p, int32_t n, const int32_t* slots, const int64_t* n_in,
+                                                 const int32_t* flush, const void* in_packed, void* out_packed, float* emb_packed,
+                                                 int64_t out_cap, int64_t* n_out);
 
 /* ------------------------------------------------------------------------------- code containers
  * Device-side bit packing of code tensors: the wire layout of the reference's BitPacker / BitUnpacker
@@ -1087,6 +1166,13 @@ NC_API nc_status nc_op_vq_gather(int device_index, const float* codebook, int32_
  * where *has_stats comes back 1.  out == NULL: only *C_out, *L_out and *n_taps (tap < 0: only *n_taps); nothing is launched. */
 NC_API nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* x, int32_t B, int64_t L, int32_t tap, float* out, float* stats,
                                      int32_t* C_out, int64_t* L_out, int32_t* n_taps, int32_t* has_stats);
+/* One SLSTM stack of a loaded Encodec handle (SLSTM.forward, Modules/Encodec/SLSTM.cs:40-57; decoder == 0: the encoder's, else the
+ * decoder's) on x [N,C,T] from GIVEN state, through the carried-state launcher of the causal streams (one fresh launch per time step;
+ * the state rows are gathered from and scattered to a slot table by index): y [N,C,T] = elu?(x + lstm(x)) as the LSTM tap of
+ * nc_op_encodec_trace, and h_state / c_state [N][layers][C] are read (nullable together: zero state) and overwritten with the state
+ * behind step T - 1.  Host pointers, synchronous.  Splitting T into pieces and carrying the state gives the one-shot result bit for bit. */
+NC_API nc_status nc_op_encodec_lstm_carried(nc_codec* h, int32_t decoder, const float* x, int32_t N, int64_t T, float* h_state, float* c_state,
+                                            float* y);
 /* nc_log10f (csrc/nc_math.h, the canonical log10 of the quality metrics) on n positive normal binary32 values, evaluated on the host */
 NC_API nc_status nc_op_log10f(const float* x, int64_t n, float* y);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */

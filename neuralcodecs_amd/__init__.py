@@ -7,6 +7,7 @@ classes (NeuralCodecs.Torch/Models/{DAC,SNAC,Encodec}.cs).
 from .config import DACConfig, EncodecConfig, SNACConfig  # noqa: F401
 from .dac import DAC, dac_halo, dac_ragged_windows  # noqa: F401
 from .snac import SNAC, snac_halo, snac_ragged_windows  # noqa: F401
+from .encodec import EncodecCausalPool, EncodecCausalSession, encodec_causal_plan  # noqa: F401
 from .encodec import EncodedFrame, Encodec, EncodecStreamPool, EncodecStreamSession, encodec_ragged_rows, encodec_stream_plan  # noqa: F401
 from .session import FLUSH, Session, SessionPool, session_pool_plan, session_schedule  # noqa: F401
 from .dia import (DiaGeneration, adjust_speed, dia_apply_delay, dia_prefill_pack, dia_revert_delay, dia_sample_host,  # noqa: F401
@@ -14,7 +15,7 @@ from .dia import (DiaGeneration, adjust_speed, dia_apply_delay, dia_prefill_pack
 from .quality import QualityConfig, mel_filterbank, mel_spectrogram, quality_metrics, stft  # noqa: F401
 
 __all__ = ["DAC", "SNAC", "Encodec", "EncodedFrame", "DACConfig", "SNACConfig", "EncodecConfig", "dac_halo", "snac_halo", "dac_ragged_windows",
-           "snac_ragged_windows", "encodec_ragged_rows", "encodec_stream_plan", "EncodecStreamPool", "EncodecStreamSession", "Session", "session_schedule", "SessionPool", "FLUSH", "session_pool_plan",
+           "snac_ragged_windows", "encodec_ragged_rows", "encodec_stream_plan", "encodec_causal_plan", "EncodecCausalPool", "EncodecCausalSession", "EncodecStreamPool", "EncodecStreamSession", "Session", "session_schedule", "SessionPool", "FLUSH", "session_pool_plan",
            "adjust_speed", "dia_apply_delay", "dia_revert_delay", "dia_prefill_pack", "mix_to_mono_ragged", "dia_sample_next_token", "dia_sample_host",
            "DiaGeneration", "QualityConfig", "stft", "mel_spectrogram", "mel_filterbank", "quality_metrics"]
 from . import audio  # noqa: F401,E402

@@ -88,6 +88,15 @@ class NcEncodecRaggedRow(C.Structure):
                 ("length", C.c_int64), ("frames", C.c_int64)]
 
 
+class NcEncodecCausalInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("hop", "halo_e", "halo_d", "min_frames_e", "min_frames_d", "carry_e", "carry_d", "taint_e", "taint_d")]
+
+
+class NcEncodecCausalRow(C.Structure):
+    _fields_ = [("entry", C.c_int32), ("batch", C.c_int32), ("row", C.c_int32), ("one_clip", C.c_int32), ("start", C.c_int64),
+                ("width", C.c_int64), ("new_frames", C.c_int64)]
+
+
 class NcSessionStep(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("w0", "w1", "k0", "k1", "resident")]
 
@@ -225,6 +234,16 @@ SYMBOLS = [
     ("nc_encodec_stream_pool_plan", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(NcEncodecRaggedPlan), _P, C.c_int64]),
     ("nc_encodec_stream_pool_step", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("nc_encodec_stream_pool_step_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    ("nc_encodec_causal_plan", C.c_int, [C.POINTER(NcEncodecConfig), C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32,
+                                         C.POINTER(NcEncodecCausalInfo), _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    ("nc_encodec_causal_pool_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("nc_encodec_causal_pool_destroy", C.c_int, [_P]),
+    ("nc_encodec_causal_pool_reset_slot", C.c_int, [_P, C.c_int32]),
+    ("nc_encodec_causal_pool_pending", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nc_encodec_causal_pool_query", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("nc_encodec_causal_pool_plan", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nc_encodec_causal_pool_step", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("nc_encodec_causal_pool_step_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("nc_packed_bytes", C.c_int64, [C.c_int64, C.c_int32]),
     ("nc_pack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     ("nc_unpack_codes_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
@@ -298,6 +317,7 @@ SYMBOLS = [
                                 _P, _P, _P]),
     ("nc_op_rvq_update", C.c_int, [C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     ("nc_op_vq_gather", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _P, C.c_int64]),
+    ("nc_op_encodec_lstm_carried", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("nc_op_encodec_trace", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nc_op_log10f", C.c_int, [_P, C.c_int64, _P]),

@@ -816,7 +816,7 @@ float* EncodecModel::materialize(const Act& a, int N, const float* scale, int mo
 }
 
 // SEANetEncoder.forward (SEANetEncoder.cs:37-148) on N rows
-EncodecModel::Act EncodecModel::encoder_stack(Act cur, int N) {
+EncodecModel::Act EncodecModel::encoder_front(Act cur, int N) {
     cur = sconv(enc_in, cur, nullptr, false, N);
     tap(cur);
     for (int i = 0; i < cfg.n_ratios; ++i) {
@@ -825,6 +825,11 @@ EncodecModel::Act EncodecModel::encoder_stack(Act cur, int N) {
         cur = sconv(enc_down[i], s, &y, true, N);
         tap(cur);
     }
+    return cur;
+}
+
+EncodecModel::Act EncodecModel::encoder_stack(Act cur, int N) {
+    cur = encoder_front(cur, N);
     const float* xl = materialize(cur, N, nullptr, 0);
     // (the ELU in front of the last convolution is applied by the LSTM's output store: once per element instead of once per row tile
     //  of the consumer's staging, and the consumer runs as a plain convolution)
@@ -871,8 +876,13 @@ EncodecModel::Act EncodecModel::decoder_stack(const float* emb, int N, int64_t T
     tap(cur);
     const float* xl = materialize(cur, N, nullptr, 0);
     const bool lstm_elu = lstm_applies_elu(dec_lstm);
-    Act s = dense_act(lstm.run(dec_lstm, xl, N, cur.L, lstm_elu), cur.C, cur.L), y;
+    Act s = dense_act(lstm.run(dec_lstm, xl, N, cur.L, lstm_elu), cur.C, cur.L);
     tap(s, true, lstm_elu);
+    return decoder_tail(s, lstm_elu, N);
+}
+
+EncodecModel::Act EncodecModel::decoder_tail(Act s, bool lstm_elu, int N) {
+    Act y;
     bool dual = false;
     for (int i = 0; i < cfg.n_ratios; ++i) {
         Act u = sconvT(dec_up[i], s, dual ? &y : nullptr, !(i == 0 && lstm_elu), N);

@@ -20,6 +20,12 @@ bool lstm_applies_elu(const Lstm& l);
 // one wanted chunk, a short sequence, or `may_pipe` false).  Host arithmetic only.
 std::vector<int64_t> lstm_chunk_starts(int64_t T, int n_layers, int want_chunks, bool even_chunks, bool may_pipe);
 
+// Steps [0, T) of ONE layer in the step-wise form -- the input projections of `in` [N,C,T], then one fresh launch per time step -- from the
+// state the caller hands in: h0 and cs are [C][N] (unit-major), h1 is the second half of the double-buffered h.  out [N,C,T] receives h_t
+// (+ skip, ELU where asked).  Returns the half (h0 or h1) that holds h_T; cs holds c_T.  Zero state in: SLSTM.forward's own layer.
+float* lstm_layer_steps(EncodecModel& m, LstmLayer& y, int C, const float* in, const float* skip, float* out, float* h0, float* h1, float* cs, int N, int64_t T,
+                        bool elu_out);
+
 // What a handle's LSTM launches own beside the weights.  It reaches the pool allocator, the stream, the profiler, cu_count, lds_per_cu
 // and on_side_group of the model that holds it through `m`.
 struct LstmRuntime {

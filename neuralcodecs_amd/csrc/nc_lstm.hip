@@ -648,7 +648,25 @@ static float* run_persistent(LstmRuntime& r, Lstm& l, const float* x, int N, int
     return c.out[c.nl - 1];
 }
 
-// generic fallback: one launch per time step (block = hidden unit with its 4 weight rows in LDS, thread = clip)
+// One layer of the step-wise form on steps [0, T): the input projections of `in`, then one fresh launch per time step (block = hidden
+// unit with its 4 weight rows in LDS, thread = clip) from the state in (h0, cs) -- [C][N], unit-major; h1 is the other half of the
+// double-buffered h.  Returns the half that holds h_T.  No workgroup waits for another: a step is ordered behind the one before it by
+// the stream alone.  (nc_lstm.h)
+float* lstm_layer_steps(EncodecModel& m, LstmLayer& y, int C, const float* in, const float* skip, float* out, float* h0, float* h1, float* cs, int N, int64_t T,
+                        bool elu_out) {
+    hipStream_t stream = m.stream;
+    float* gi = m.alloc((size_t)N * 4 * C * T);
+    ih_gemm(m, y, in, gi, N, C, T);
+    if (m.prof.on) m.prof.begin(stream, NC_KC_LSTM, 2.0 * 4 * C * C * (double)N * T, 4.0 * 6 * C * (double)N * T);
+    for (int64_t t = 0; t < T; ++t)
+        hipLaunchKernelGGL(lstm_step_kernel, dim3((unsigned)C, (unsigned)((N + 63) / 64)), dim3(64), (size_t)4 * C * sizeof(float), stream,
+                           gi, y.whh.as<float>(), y.bhh.as<float>(), (t & 1) ? h1 : h0, (t & 1) ? h0 : h1, cs, skip, out, N, C, T, t, elu_out ? 1 : 0);
+    NC_HIP(hipGetLastError());
+    if (m.prof.on) m.prof.end(stream);
+    return (T & 1) ? h1 : h0;
+}
+
+// generic fallback: one launch per time step, from the zero state
 static float* run_stepwise(EncodecModel& m, Lstm& l, const float* x, int N, int64_t T, bool elu_out) {
     const int C = l.C, nl = (int)l.layers.size();
     hipStream_t stream = m.stream;
@@ -659,22 +677,14 @@ static float* run_stepwise(EncodecModel& m, Lstm& l, const float* x, int N, int6
     const float* in = x;
     float* out = nullptr;
     for (int li = 0; li < nl; ++li) {
-        LstmLayer& y = *l.layers[li];
-        float* gi = m.alloc((size_t)N * 4 * C * T);
-        ih_gemm(m, y, in, gi, N, C, T);
-        out = m.alloc((size_t)N * C * T);
         const bool last = li + 1 == nl;
-        if (m.prof.on) m.prof.begin(stream, NC_KC_LSTM, 2.0 * 4 * C * C * (double)N * T, 4.0 * 6 * C * (double)N * T);
+        out = m.alloc((size_t)N * C * T);
         float* h0 = m.alloc((size_t)C * N);
         float* h1 = m.alloc((size_t)C * N);
         float* cs = m.alloc((size_t)C * N);
         NC_HIP(hipMemsetAsync(h0, 0, (size_t)C * N * 4, stream));
         NC_HIP(hipMemsetAsync(cs, 0, (size_t)C * N * 4, stream));
-        for (int64_t t = 0; t < T; ++t)
-            hipLaunchKernelGGL(lstm_step_kernel, dim3((unsigned)C, (unsigned)((N + 63) / 64)), dim3(64), (size_t)4 * C * sizeof(float), stream,
-                               gi, y.whh.as<float>(), y.bhh.as<float>(), (t & 1) ? h1 : h0, (t & 1) ? h0 : h1, cs, last ? x : nullptr, out, N, C, T, t, (last && elu_out) ? 1 : 0);
-        NC_HIP(hipGetLastError());
-        if (m.prof.on) m.prof.end(stream);
+        lstm_layer_steps(m, *l.layers[li], C, in, last ? x : nullptr, out, h0, h1, cs, N, T, last && elu_out);
         in = out;
     }
     return out;

@@ -371,6 +371,8 @@ struct EncodecModel : Codec {
     void decode_ragged_dev(const int64_t* codes, const float* scales, int B, const int64_t* lengths, int nq, float* pcm);
     // Stream pool (nc_encodec_stream.hip): segments of live streams pooled into the same batches; its steps call encode_batch / decode_batch
     friend struct ::nc_encodec_stream_pool;
+    // Causal streams (nc_encodec_causal.hip): windows of live streams through encoder_front / decoder_tail, the LSTM from carried state
+    friend struct ::nc_encodec_causal_pool;
     float* alloc(size_t n_floats);   // the next buffer of the pool (of the running batch's lane), grown to n_floats
     // Test hook (nc_op_encodec_trace).  A tap is every activation view the driver holds between launches, numbered in the order the
     // driver produces them: encoder = first conv | per stage: shortcut s, branch h, branch y, down-conv | LSTM | last conv; decoder =
@@ -416,6 +418,8 @@ struct EncodecModel : Codec {
     void encode_batch(const float* x, int N, int64_t L, int64_t Tz, int64_t* codes, float* scale_out, float* emb_out);
     float* decode_batch(const int64_t* codes, int N, int nq, int64_t Tz, const float* scale, int64_t* Lout);
     Act encoder_stack(Act cur, int N);                        // SEANetEncoder.forward on an activation view -> the last conv's pending view
+    Act encoder_front(Act cur, int N);                        // ... its convolutional front: up to the LSTM's input (pending view)
+    Act decoder_tail(Act s, bool lstm_elu, int N);            // SEANetDecoder.forward behind the LSTM: up-stack and last conv on the LSTM's output s
     Act decoder_stack(const float* emb, int N, int64_t Tz);   // SEANetDecoder.forward on dense emb [N,dimension,Tz]
     // the tap of trace_dev: with no trace running (want < 0, every production call) tap() is one compare
     struct TapReached {};

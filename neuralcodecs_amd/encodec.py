@@ -408,6 +408,22 @@ class Encodec(_lib.ProfileMixin):
     def decode_session(self, n_q: Optional[int] = None) -> "EncodecStreamSession":
         return EncodecStreamSession(self.decode_pool(1, n_q))
 
+    # ---- causal streams (PCM or code frames that arrive over time; causal models without segmentation) ----
+    def causal_encode_pool(self, n_slots: int) -> "EncodecCausalPool":
+        """nc_encodec_causal_pool_create(decode = 0): n_slots live streams encoded hop by hop, the LSTM's state carried."""
+        return EncodecCausalPool(self, False, n_slots, None)
+
+    def causal_decode_pool(self, n_slots: int, n_q: Optional[int] = None) -> "EncodecCausalPool":
+        """nc_encodec_causal_pool_create(decode = 1): n_slots live streams decoded frame by frame (n_q: codebooks in the pushed codes;
+        None = the handle's bandwidth)."""
+        return EncodecCausalPool(self, True, n_slots, n_q)
+
+    def causal_encode_session(self) -> "EncodecCausalSession":
+        return EncodecCausalSession(self.causal_encode_pool(1))
+
+    def causal_decode_session(self, n_q: Optional[int] = None) -> "EncodecCausalSession":
+        return EncodecCausalSession(self.causal_decode_pool(1, n_q))
+
 
 def encodec_stream_plan(config: EncodecConfig, pushed, emitted, n_in, flush=None, frame_lens=None, decode: bool = False, max_rows: int = 0):
     """nc_encodec_stream_plan: one step of a stream pool from a config alone, no device needed.  Stream i has received pushed[i] samples
@@ -594,6 +610,188 @@ class EncodecStreamSession:
     """One live stream: a stream pool with one slot.  push(x) -> what became final; flush([x]) ends the stream; reset() starts anew."""
 
     def __init__(self, pool: EncodecStreamPool):
+        self.pool = pool
+
+    def push(self, x, **kw):
+        out = self.pool.step({0: x}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def flush(self, x=None, **kw):
+        out = self.pool.step({0: FLUSH if x is None else (x, FLUSH)}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def pending(self) -> int:
+        return self.pool.pending(0)
+
+    def reset(self) -> None:
+        self.pool.reset_slot(0)
+
+    def close(self) -> None:
+        self.pool.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _causal_rows(call):
+    """rows of one of the two causal planner entry points; call(rows, cap, n_rows, n_batches) -> status"""
+    nr, nb = C.c_int64(), C.c_int64()
+    _lib.check(call(None, 0, C.byref(nr), C.byref(nb)))
+    rows = (_lib.NcEncodecCausalRow * max(1, int(nr.value)))()
+    _lib.check(call(rows, int(nr.value), C.byref(nr), C.byref(nb)))
+    return int(nb.value), [{k: int(getattr(rows[i], k)) for k, _ in _lib.NcEncodecCausalRow._fields_} for i in range(int(nr.value))]
+
+
+def encodec_causal_plan(config: EncodecConfig, received=(0,), emitted=(0,), n_in=(0,), flush=None, decode: bool = False, max_rows: int = 0):
+    """nc_encodec_causal_plan: one step of a causal pool from a config alone, no device needed.  Stream i has received received[i] samples
+    (decode: code frames) and emitted emitted[i] frames (decode: decoded that many); it now brings n_in[i] more and flushes where flush[i].
+    -> (info dict: hop, halo_e, halo_d, min_frames_e, min_frames_d, carry_e, carry_d, taint_e, taint_d; n_batches; rows in launch order --
+    `entry` is the stream's index --; per stream the frames (decode: samples per channel) it emits)."""
+    c = _c_config(config)
+    n = len(n_in)
+    re_, em, ni = _lib.i64_array(received), _lib.i64_array(emitted), _lib.i64_array(n_in)
+    fl = (C.c_int32 * max(1, n))(*[int(bool(f)) for f in flush]) if flush is not None else None
+    info = _lib.NcEncodecCausalInfo()
+    n_out = (C.c_int64 * max(1, n))()
+    call = lambda rows, cap, nr, nb: _lib.lib().nc_encodec_causal_plan(C.byref(c), 1 if decode else 0, n, re_, em, ni, fl, int(max_rows), C.byref(info), rows, cap, nr, nb, n_out)  # noqa: E731
+    n_batches, rows = _causal_rows(call)
+    return {k: int(getattr(info, k)) for k, _ in _lib.NcEncodecCausalInfo._fields_}, n_batches, rows, [int(n_out[i]) for i in range(n)]
+
+
+class EncodecCausalPool:
+    """n_slots independent live streams on one causal Encodec model without segmentation (the 24 kHz preset), one direction, stepped
+    together (nc_encodec_causal_pool_*; Encodec.Encode / Encodec.Decode with SLSTM.forward's state carried).
+
+        out = pool.step({slot: x | FLUSH | (x, FLUSH), ...})
+
+    encode pool: x is PCM [channels, n] (any n >= 0); out[slot] is codes [1, n_q, F] int64 of the frames that became final -- F is often 0.
+    decode pool: x is codes [1, n_q, n] (or [n_q, n]); out[slot] is PCM [channels, n_out].  FLUSH ends the slot's stream (after the x of a
+    tuple) and emits the rest; reset_slot() makes the slot new.  Everything a slot emitted, end to end, equals encode() / decode() on the
+    whole stream, bit for bit.  numpy in, numpy out (host API); torch device tensors in, device tensors out on torch's current stream."""
+
+    def __init__(self, model: Encodec, decode: bool, n_slots: int, n_q: Optional[int]):
+        self.model, self.decode, self.n_slots = model, bool(decode), int(n_slots)
+        self._p = C.c_void_p()
+        self._torch = False
+        _lib.check(_lib.lib().nc_encodec_causal_pool_create(model._h, 1 if decode else 0, int(n_slots), int(n_q or 0), C.byref(self._p)))
+        self.n_q = int(n_q) if n_q else model.query(1)[1]
+
+    def close(self) -> None:
+        if getattr(self, "_p", None) is not None and self._p.value:
+            try:
+                _lib.lib().nc_encodec_causal_pool_destroy(self._p)
+            finally:
+                self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset_slot(self, slot: int) -> None:
+        _lib.check(_lib.lib().nc_encodec_causal_pool_reset_slot(self._p, int(slot)))
+
+    def pending(self, slot: int) -> int:
+        n = C.c_int64()
+        _lib.check(_lib.lib().nc_encodec_causal_pool_pending(self._p, int(slot), C.byref(n)))
+        return n.value
+
+    def _entries(self, entries: dict):
+        if not entries:
+            raise ValueError("a step needs at least one entry")
+        slots, data, flush = [], [], []
+        rows = self.n_q if self.decode else self.model.config.channels
+        for s, v in entries.items():
+            d, f = EncodecStreamPool._split(v)
+            if d is not None:
+                if self.decode and d.ndim == 3 and d.shape[0] == 1:
+                    d = d[0]
+                if d.ndim != 2 or d.shape[0] != rows:
+                    raise ValueError(f"every push must be [{rows}, n]")
+            slots.append(int(s)); data.append(d); flush.append(f)
+        some = [d for d in data if d is not None]
+        if some:
+            self._torch = _is_torch(some[0])
+        return slots, data, flush, [0 if d is None else int(d.shape[1]) for d in data]
+
+    @staticmethod
+    def _c(slots, n_in, flush):
+        n = len(slots)
+        return (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+
+    def query(self, entries: dict) -> dict:
+        """{slot: code frames (decode pool: samples per channel) the entry would emit} (nc_encodec_causal_pool_query)"""
+        slots, _, flush, n_in = self._entries(entries)
+        return dict(zip(slots, self._query(slots, flush, n_in)))
+
+    def _query(self, slots, flush, n_in):
+        n = len(slots)
+        c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
+        n_out = (C.c_int64 * n)()
+        _lib.check(_lib.lib().nc_encodec_causal_pool_query(self._p, n, c_slots, c_n_in, c_flush, n_out))
+        return [int(x) for x in n_out]
+
+    def plan(self, entries: dict):
+        """(n_batches, rows in launch order) of the step these entries would be under the pool's current state
+        (nc_encodec_causal_pool_plan): as encodec_causal_plan reports them, `entry` being the entry's index."""
+        slots, _, flush, n_in = self._entries(entries)
+        n = len(slots)
+        c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
+        return _causal_rows(lambda rows, cap, nr, nb: _lib.lib().nc_encodec_causal_pool_plan(self._p, n, c_slots, c_n_in, c_flush, rows, cap, nr, nb))
+
+    def step(self, entries: dict, return_emb: bool = False):
+        slots, data, flush, n_in = self._entries(entries)
+        n = len(slots)
+        n_out = self._query(slots, flush, n_in)                            # every refusal that needs no device, and the sizes
+        L, m = _lib.lib(), self.model
+        Cn, D = m.config.channels, m.config.dimension
+        nq = self.n_q if self.decode else m.query(1)[1]
+        c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
+        if self._torch:
+            import torch
+            dev = torch.device("cuda", m.device_index)
+            empty = lambda k, dt: torch.empty((max(1, k),), dtype=dt, device=dev)  # noqa: E731
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            f32, i64 = torch.float32, torch.int64
+            cat = lambda parts, dt: torch.cat([p.reshape(-1).to(dt) for p in parts]).contiguous() if parts else empty(0, dt)  # noqa: E731
+            m._bind_torch_stream()
+            fn = L.nc_encodec_causal_pool_step_dev
+        else:
+            empty = lambda k, dt: np.empty((max(1, k),), dt)  # noqa: E731
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            f32, i64 = np.float32, np.int64
+            cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dt).reshape(-1) for p in parts])) if parts else empty(0, dt)  # noqa: E731
+            fn = L.nc_encodec_causal_pool_step
+        some = [d for d in data if d is not None]
+        if self.decode:
+            codes = cat(some, i64)
+            out = empty(Cn * sum(n_out), f32)
+            _lib.check(fn(self._p, n, c_slots, c_n_in, c_flush, ptr(codes), ptr(out), None, Cn * sum(n_out), None))
+            return {s: p.reshape(Cn, -1) for s, p in zip(slots, _lib.split_packed(out, [Cn * k for k in n_out]))}
+        pcm = cat(some, f32)
+        codes = empty(nq * sum(n_out), i64)
+        emb = empty(D * sum(n_out), f32) if return_emb else None
+        _lib.check(fn(self._p, n, c_slots, c_n_in, c_flush, ptr(pcm), ptr(codes), ptr(emb), nq * sum(n_out), None))
+        res = {s: p.reshape(1, nq, -1) for s, p in zip(slots, _lib.split_packed(codes, [nq * k for k in n_out]))}
+        if not return_emb:
+            return res
+        return res, {s: p.reshape(1, D, -1) for s, p in zip(slots, _lib.split_packed(emb, [D * k for k in n_out]))}
+
+
+class EncodecCausalSession:
+    """One live causal stream: a causal pool with one slot.  push(x) -> what became final; flush([x]) ends the stream; reset() starts anew."""
+
+    def __init__(self, pool: EncodecCausalPool):
         self.pool = pool
 
     def push(self, x, **kw):

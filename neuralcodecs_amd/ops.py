@@ -130,6 +130,21 @@ def encodec_trace(model, x, tap, decoder=False):
     return out, (st if hs.value else None)
 
 
+def encodec_lstm_carried(model, x, state=None, decoder=False):
+    """nc_op_encodec_lstm_carried: one SLSTM stack of a loaded Encodec model on x [N,C,T] from `state` = (h, c), each [N,layers,C]
+    (None: the zero state) -> (y [N,C,T] = elu?(x + lstm(x)) as the LSTM tap, (h, c) behind the last step)."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, Cc, T = x.shape
+    nl = model.config.lstm_layers
+    if state is None:
+        h, c = np.zeros((N, nl, Cc), np.float32), np.zeros((N, nl, Cc), np.float32)
+    else:
+        h, c = (np.array(s, dtype=np.float32, order="C", copy=True).reshape(N, nl, Cc) for s in state)
+    y = np.empty_like(x)
+    _lib.check(_lib.lib().nc_op_encodec_lstm_carried(model._h, int(bool(decoder)), x.ctypes.data, N, T, h.ctypes.data, c.ctypes.data, y.ctypes.data))
+    return y, (h, c)
+
+
 def fold_weight_norm(v, g):
     v = np.ascontiguousarray(v, np.float32); g = np.ascontiguousarray(g, np.float32).reshape(-1)
     w = np.empty_like(v)

@@ -28,7 +28,7 @@ OUT = os.path.join(ROOT, "bindings", "csharp")
 
 SCALARS = {"int": "int", "int32_t": "int", "int64_t": "long", "uint64_t": "ulong", "uint32_t": "uint", "size_t": "nuint", "float": "float", "double": "double",
            "int16_t": "short", "uint8_t": "byte", "nc_status": "NcStatus"}
-OPAQUE = {"nc_codec", "nc_group", "nc_session", "nc_session_pool", "nc_encodec_stream_pool"}
+OPAQUE = {"nc_codec", "nc_group", "nc_session", "nc_session_pool", "nc_encodec_stream_pool", "nc_encodec_causal_pool"}
 
 
 def strip_comments(src):
