@@ -1009,6 +1009,101 @@ NC_API nc_status nc_quality_metrics(int device_index, const float* ref, const in
 NC_API nc_status nc_quality_metrics_host(const float* ref, const int64_t* ref_off, const float* est, const int64_t* est_off, const int64_t* n,
                                          int32_t B, int32_t sample_rate, const nc_quality_cfg* cfg, nc_quality_row* out);
 
+/* ------------------------------------------------------------------------------------ loudness
+ * ITU-R BS.1770 K-weighting, gated integrated loudness (LUFS), normalisation to a target level and the gain that restores a stored
+ * level.  Every value is one fixed bit pattern (fl = one binary32 rounding; binary64 operations are single IEEE operations, never fused;
+ * no libm on the data path; the units are built with -ffp-contract=off), stated here so that the *_host twins (csrc/nc_loudness_host.hip:
+ * plain serial C++ on HOST pointers, no device, sharing nc_math.h, the table builder and the argument checks with the kernels and
+ * nothing else) and the kernels (csrc/nc_loudness.hip) agree bit for bit.
+ *   clips   a clip has C channels, 1 <= C <= 5, with weights G = {1, 1, 1, 1.41f, 1.41f} (LoudnessMeter.cs:36), one length n[b] and C
+ *           ELEMENT offsets off[b C + c] into a packed float buffer: any planar layout, the packed buffers of the ragged calls in place.
+ *           off[] / n[] / out_off[] / db[] are HOST arrays.  B C <= 32767 (nc_audio_kweight: R rows <= 32767).
+ *   coeffs  nc_loudness_cfg.filter = NC_KWEIGHT_REFERENCE: the binary32 literals of LoudnessMeter.cs:41-52, widened, at ANY sample rate (as
+ *           the reference does);  NC_KWEIGHT_DESIGNED: per rate, in binary64, the analog prototypes of the BS.1770 constants through the
+ *           bilinear transform, K = tan(pi f0 / rate), every stage normalised by a0 = 1 + K/Q + K^2:
+ *             high shelf  f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20), Vb = Vh^0.4996667741545416:
+ *                         b = (Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2) / a0,  a = (1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0)
+ *             high pass   f0 = 38.13547087602444, Q = 0.5003270373238773: b = (1, -2, 1) (not normalised, as in the recommendation), a as above
+ *           At 48 kHz this gives the constants back (to 1e-15 of their decimal form, 6e-8 of the binary32 literals).  A round-number design
+ *           (RBJ shelf +4 dB / 1500 Hz / Q 1/sqrt(2), RBJ high pass 38 Hz / Q 0.5) does not: it misses them by 1.1e-4 and, in the high
+ *           pass's normalised numerator, by 1e-2.
+ *           nc_audio_kweight_coeffs exports b[2][3], a[2][3] (stage 0 = shelf, 1 = high pass; a[s][0] = 1).
+ *   filter  the cascade shelf -> high pass, each biquad in transposed direct form II, zero initial state, as a 4-state system
+ *           s' = A s + B x, y = C s + D x (s0, s1: the shelf's registers; s2, s3: the high pass's), A, B, C, D in binary64.
+ *   tables  block length L = 64; in binary64, powers by repeated left multiplication (A^(k+1) B = A (A^k B), C A^(r+1) = (C A^r) A,
+ *           A^(k+1) = A A^k), every dot product summed in ascending index from the first product:
+ *             h[0] = D, h[k] = C (A^(k-1) B);  Hm[r][j] = fl(h[r - j]) for j <= r, else 0;  Cm[i][j] = fl((A^(L-1-j) B)[i]);
+ *             Gs[r] = C A^r (1 x 4) and M = A^L (4 x 4) stay binary64.        (nc_audio_kweight_tables)
+ *   block q of a row, x = 0 past the row end, s_0 = 0:
+ *             u[r] = ONE chain over j = 0..63 ascending of fmaf(Hm[r][j], x[64 q + j], acc) from acc = 0;  v[i] the same with Cm[i]
+ *             y[64 q + r] = fl((double)u[r] + g),  g = ((Gs[r][0] s_q[0] + Gs[r][1] s_q[1]) + Gs[r][2] s_q[2]) + Gs[r][3] s_q[3]
+ *             s_{q+1}[i] = m + (double)v[i],       m = ((M[i][0] s_q[0] + M[i][1] s_q[1]) + M[i][2] s_q[2]) + M[i][3] s_q[3]
+ *   energy  N = (int)(0.4f rate), S = (int)((0.4f rate) 0.25f) in binary32 (LoudnessMeter.cs:140-141); J = (n - N) / S + 1 blocks for
+ *           n >= N, else 0.  Cell i = samples [i S, (i + 1) S): the binary64 sum of fl(y y), samples ascending within sub-blocks of 128
+ *           counted from the cell's start, then the sub-blocks ascending.  Block j = ((cell j + cell j+1) + cell j+2) + cell j+3, then
+ *           the N - 4 S samples [(j + 4) S, j S + N) added one by one;  z[c][j] = sum / (double)N;  W_j = sum_c (double)G_c z[c][j],
+ *           c ascending.
+ *   gates   on the binary64 sums.  Absolute: block j passes iff W_j > Ka = 0x1.f791ec6e1d5aap-24 (the binary64 nearest 10^-6.9309, i.e.
+ *           -0.691 + 10 log10 W > -70).  za[c] = (sum of z[c][j] over the passing j, ascending) / max(count, 1);  Wa = sum_c G_c za[c].
+ *           Relative: block j passes iff it passes the absolute gate and W_j > 0.1 Wa;  zr[c] and Wr likewise.
+ *   result  lufs = max(fl(-0.691f + fl(10.0f nc_log10f(fl(Wr)))), -70.0f); -70.0f where fl(Wr) is below the smallest normal (an
+ *           all-silent clip, a clip shorter than one block).  gain = nc_expf(fl(fl(target_db - lufs) GAIN_FACTOR)),
+ *           GAIN_FACTOR = 0.11512925464970229f.  n_bad = the non-finite samples of the clip (all channels, clamped to INT32_MAX); a clip
+ *           with n_bad != 0 has NaN in lufs and gain and 0 in both pass counts; other clips are untouched.
+ *   gain    nc_loudness_normalize writes fl(x gain) per sample (the quiet NaN 0x7fc00000 where gain is NaN) to out_off, which may equal
+ *           off (in place), and returns the rows so that the measured level can be stored;  nc_audio_apply_gain_db writes
+ *           fl(x nc_expf(fl(db[b] GAIN_FACTOR))): with db = stored lufs - target_db it undoes a normalisation after a decode.
+ * Deviations from the reference: the exact recursion instead of its two filter paths (ApplyFilterCPU's LFilter indexes the first
+ * dimension of a 3-D tensor; ApplyFilterGPU truncates the high pass, pole radius 0.995, at 512 taps and returns n + 1 samples);
+ * division by the integer N instead of multiplication by 1.0f / (0.4f rate); gate comparisons on the binary64 sums instead of binary32
+ * log10 values.  AudioSignal.Loudness() zero-pads a clip shorter than 0.5 s; here a clip shorter than one block reports -70.
+ * NC_EINVAL, before anything is launched: a null pointer; B < 1, C outside [1, 5], B C > 32767; a negative offset or length;
+ * sample_rate < 10 (N or S would be 0); an unknown filter; a target or a db[b] that is not finite.
+ *
+ * replaces: LoudnessMeter.IntegratedLoudness / NormalizeAudio   AudioTools/LoudnessMeter.cs:127-207
+ * replaces: AudioSignal.Loudness / Normalize                    AudioTools/AudioSignal.cs:847-940
+ *           each as _dev (DEVICE buffers, asynchronous on `hip_stream`), plain (HOST buffers, synchronous) and _host (no device). */
+#define NC_KWEIGHT_REFERENCE 0
+#define NC_KWEIGHT_DESIGNED 1
+#define NC_LOUDNESS_MAX_CHANNELS 5
+typedef struct nc_loudness_cfg {
+    int32_t filter;      /* NC_KWEIGHT_* */
+    float target_db;     /* the level `gain` leads to; the reference's default is -24 */
+} nc_loudness_cfg;
+typedef struct nc_loudness_row {
+    float lufs, gain;
+    int32_t n_blocks, n_pass_abs, n_pass_rel, n_bad;
+} nc_loudness_row;
+NC_API nc_status nc_audio_kweight_coeffs(int32_t sample_rate, int32_t filter, double* b /* [2][3] */, double* a /* [2][3] */);
+NC_API nc_status nc_audio_kweight_tables(int32_t sample_rate, int32_t filter, float* Hm /* [64][64] */, float* Cm /* [4][64] */,
+                                         double* Gs /* [64][4] */, double* M /* [4][4] */);
+NC_API nc_status nc_audio_kweight_dev(int device_index, const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                                      int32_t filter, float* out, const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_kweight(int device_index, const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                                  int32_t filter, float* out, const int64_t* out_off);
+NC_API nc_status nc_audio_kweight_host(const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t sample_rate, int32_t filter,
+                                       float* out, const int64_t* out_off);
+NC_API nc_status nc_loudness_dev(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n,
+                                 int32_t sample_rate, const nc_loudness_cfg* cfg, nc_loudness_row* out, void* hip_stream);
+NC_API nc_status nc_loudness(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                             const nc_loudness_cfg* cfg, nc_loudness_row* out);
+NC_API nc_status nc_loudness_host(const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                                  const nc_loudness_cfg* cfg, nc_loudness_row* out);
+NC_API nc_status nc_loudness_normalize_dev(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n,
+                                           int32_t sample_rate, const nc_loudness_cfg* cfg, float* out, const int64_t* out_off,
+                                           nc_loudness_row* rows, void* hip_stream);
+NC_API nc_status nc_loudness_normalize(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n,
+                                       int32_t sample_rate, const nc_loudness_cfg* cfg, float* out, const int64_t* out_off,
+                                       nc_loudness_row* rows);
+NC_API nc_status nc_loudness_normalize_host(const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                                            const nc_loudness_cfg* cfg, float* out, const int64_t* out_off, nc_loudness_row* rows);
+NC_API nc_status nc_audio_apply_gain_db_dev(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n,
+                                            const float* db, float* out, const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_apply_gain_db(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n,
+                                        const float* db, float* out, const int64_t* out_off);
+NC_API nc_status nc_audio_apply_gain_db_host(const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, const float* db,
+                                             float* out, const int64_t* out_off);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE

@@ -116,7 +116,17 @@ class NcQualityRow(C.Structure):
                 ("n_bad", C.c_int32)]
 
 
+class NcLoudnessCfg(C.Structure):
+    _fields_ = [("filter", C.c_int32), ("target_db", C.c_float)]
+
+
+class NcLoudnessRow(C.Structure):
+    _fields_ = [("lufs", C.c_float), ("gain", C.c_float), ("n_blocks", C.c_int32), ("n_pass_abs", C.c_int32), ("n_pass_rel", C.c_int32),
+                ("n_bad", C.c_int32)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
+NC_KWEIGHT_REFERENCE, NC_KWEIGHT_DESIGNED = 0, 1
 NC_WINDOW_HANN, NC_WINDOW_ONES = 0, 1
 
 _lib = None
@@ -287,6 +297,20 @@ SYMBOLS = [
     ("nc_quality_metrics_dev", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P, _P]),
     ("nc_quality_metrics", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P]),
     ("nc_quality_metrics_host", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcQualityCfg), _P]),
+    ("nc_audio_kweight_coeffs", C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    ("nc_audio_kweight_tables", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("nc_audio_kweight_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("nc_audio_kweight", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("nc_audio_kweight_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("nc_loudness_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P, _P]),
+    ("nc_loudness", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P]),
+    ("nc_loudness_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P]),
+    ("nc_loudness_normalize_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P, _P, _P, _P]),
+    ("nc_loudness_normalize", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P, _P, _P]),
+    ("nc_loudness_normalize_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.POINTER(NcLoudnessCfg), _P, _P, _P]),
+    ("nc_audio_apply_gain_db_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("nc_audio_apply_gain_db", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("nc_audio_apply_gain_db_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),

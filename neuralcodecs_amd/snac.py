@@ -353,6 +353,17 @@ class SNAC(_lib.ProfileMixin):
         ref, est = quality.round_trip_rows(clips, dec)
         return quality.hand_back(quality.quality_metrics(ref, est, sample_rate=self.config.sample_rate, scales=scales), was_torch)
 
+    def normalize_ragged(self, clips, target_db: float = -24.0, filter: str = "reference", host: bool = False):
+        """nc_loudness_normalize_dev on 1-D clips of any lengths at the model's sample rate (neuralcodecs_amd/loudness.py): the levelled
+        clips, views of one packed buffer and ready for encode_ragged, and the per-clip rows (lufs, gain, ...) to store."""
+        from . import loudness
+        return loudness.normalize_ragged(clips, self.config.sample_rate, target_db, filter, host)
+
+    def restore_ragged(self, decoded, rows, host: bool = False):
+        """nc_audio_apply_gain_db_dev: the decoded clips back at the levels normalize_ragged measured (rows: what it returned)."""
+        from . import loudness
+        return loudness.restore_ragged(decoded, rows, host)
+
     # ---- incremental sessions (codes or PCM pushed as they arrive) ---------------------------------
     def decode_session(self, B: int, n_quantizers: Optional[int] = None):
         """nc_session_create(decode): push the code levels of the next frames (a multiple of align, each level at its own rate) with
