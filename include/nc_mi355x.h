@@ -1268,6 +1268,13 @@ NC_API nc_status nc_op_encodec_trace(nc_codec* h, int32_t decoder, const float* 
  * behind step T - 1.  Host pointers, synchronous.  Splitting T into pieces and carrying the state gives the one-shot result bit for bit. */
 NC_API nc_status nc_op_encodec_lstm_carried(nc_codec* h, int32_t decoder, const float* x, int32_t N, int64_t T, float* h_state, float* c_state,
                                             float* y);
+/* The device copy every stream, session and ragged call is made of (concat_copy, csrc/nc_copy.h), alone: for each of n_desc descriptors
+ * (a_off, na, b_off, nb, s0, dst_off, n) -- seven int64 each, in elements of elt = 4 or 8 bytes --
+ * dst[dst_off + j] = (a[a_off, a_off + na) ++ b[b_off, b_off + nb) ++ zeros)[s0 + j] for j < n, all descriptors in ONE launch (n_desc <= 65535).
+ * Host pointers, synchronous; dst [dst_n] is uploaded first, so what no descriptor covers comes back as it went in.  A descriptor that
+ * leaves a [a_n], b [b_n] or dst is refused (NC_ESTATE) before anything is launched; destinations must not overlap. */
+NC_API nc_status nc_op_concat_copy(int device_index, int32_t elt, const void* a, int64_t a_n, const void* b, int64_t b_n, void* dst, int64_t dst_n,
+                                   const int64_t* desc, int64_t n_desc);
 /* nc_log10f (csrc/nc_math.h, the canonical log10 of the quality metrics) on n positive normal binary32 values, evaluated on the host */
 NC_API nc_status nc_op_log10f(const float* x, int64_t n, float* y);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */

@@ -344,6 +344,7 @@ SYMBOLS = [
     ("nc_op_encodec_lstm_carried", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("nc_op_encodec_trace", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nc_op_concat_copy", C.c_int, [C.c_int, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64]),
     ("nc_op_log10f", C.c_int, [_P, C.c_int64, _P]),
     ("nc_op_fold_weight_norm", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
     ("nc_op_dwconv1d", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -40,13 +40,13 @@
 
 #include "nc_guard.h"
 #include "nc_limits.h"
+#include "nc_pool.h"
 
 namespace nc {
 
 namespace {
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int64_t round_up(int64_t a, int64_t m) { return ceil_div(a, m) * m; }
 
 void halo_from_layers(const int32_t* er, int ne, const int32_t* dr, int nd, int final_reach, int W, int vq_max, int64_t align, nc_halo* out) {
     if (ne <= 0 || ne > 8 || nd <= 0 || nd > 8) fail(NC_EINVAL, "encoder/decoder rate lists must hold 1..8 entries");

@@ -16,13 +16,15 @@
 // Kernels (new): cz_copy2d_kernel -- table-driven 2-D block copies (window gather, carry rewrite, concatenation of carried and new
 // frames, carry update); cz_state_gather_kernel / cz_state_scatter_kernel -- the LSTM state rows of a batch by slot index to and from
 // the unit-major [C][N] layout of lstm_step_kernel.  No LDS, no atomics, no workgroup waits for another; vector stores only.  All tables
-// of a step are written and bounds-checked on the host before anything is launched and travel in one pinned image (nc_ragged.h).
+// of a step are written and bounds-checked on the host before anything is launched and travel in one pinned image (nc_ragged.h).  The
+// pool's host scaffold (two-half carry, slot lookup, a step's state refusals, host-pointer staging) is nc_pool.h, shared with the stream pool.
 #include <algorithm>
 #include <cstring>
 #include <tuple>
 
 #include "nc_encodec_rows.h"
 #include "nc_guard.h"
+#include "nc_pool.h"
 #include "nc_ragged.h"
 
 using namespace nc;
@@ -206,8 +208,7 @@ struct CzPlan {
 
 CzPlan make_plan(const EncodecModel& m, const CzGeom& g, bool decode, int n, const int32_t* ids, const int64_t* T0, const int64_t* E0, const int64_t* n_in,
                  const int32_t* flush, int32_t max_rows, const char* what) {
-    if (max_rows < 0 || max_rows > EncodecModel::RAGGED_MAX_ROWS) fail(NC_EINVAL, "%s: max_rows must be 0 (default) .. %d", what, EncodecModel::RAGGED_MAX_ROWS);
-    const int64_t cap_rows = max_rows > 0 ? max_rows : kDefaultRaggedRows;
+    const int64_t cap_rows = er_max_rows(max_rows, what);
     CzPlan P;
     P.e.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -316,15 +317,14 @@ void launch_jobs(EncodecModel& m, const JobTabs& jt, const char* dimg, size_t li
     if (l.empty()) return;
     const CzJob* dj = reinterpret_cast<const CzJob*>(dimg + jt.at[li]);
     const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (jt.longest[li] + 1023) / 1024), 1024);
-    for (size_t done = 0; done < l.size(); done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, l.size() - done);
+    for_grid_y(l.size(), [&](size_t done, size_t cnt) {
         double bytes = 0;
         if (m.prof.on)
             for (size_t i = 0; i < cnt; ++i) bytes += 2.0 * sizeof(T) * (double)(l[done + i].rows * l[done + i].cols);
         ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
         hipLaunchKernelGGL(cz_copy2d_kernel<T>, dim3(gx, (unsigned)cnt), dim3(256), 0, m.stream, dj + done, src, dst);
         NC_HIP(hipGetLastError());
-    }
+    });
 }
 
 // while it lives the handle's one-clip launches take the step-wise LSTM form: a causal step never launches a kernel that waits on other workgroups
@@ -334,14 +334,6 @@ struct StepwiseScope {
     explicit StepwiseScope(LstmRuntime& rt) : r(rt), prev(rt.force_stepwise) { r.force_stepwise = true; }
     ~StepwiseScope() { r.force_stepwise = prev; }
 };
-
-constexpr int64_t kAlign = 64;   // elements: every batch tensor of the arena starts on a 256-byte (float) boundary
-int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
-void h2d(DevBuf& d, const void* h, size_t n, hipStream_t s) {
-    d.reserve(std::max<size_t>(n, 16));
-    if (n) NC_HIP(hipMemcpyAsync(d.p, h, n, hipMemcpyHostToDevice, s));
-}
 
 }  // namespace
 
@@ -362,6 +354,7 @@ struct nc_encodec_causal_pool {
     int rows_in = 0;                     // rows of the input carry: channels (Encode) | codebooks (Decode)
     int64_t cap_t = 0;                   // elements per row of a slot's half: samples | code frames
     int64_t keep = 0;                    // LSTM-output frames a slot carries: K - 1 (Encode) | halo_d (Decode)
+    TwoHalves halves;                    // of the carry: [rows_in][cap_t] per slot and half
     DevBuf carry;                        // [2][n_slots][rows_in][cap_t] float PCM | int64 codes
     DevBuf arena;                        // the gathered windows of every batch of a step
     DevBuf hs, cs;                       // [n_slots][layers][Cl]
@@ -371,9 +364,9 @@ struct nc_encodec_causal_pool {
     EncodecModel& model() const { return as<EncodecModel>(h); }
     Lstm& lstm_of(EncodecModel& m) const { return decode ? m.dec_lstm : m.enc_lstm; }
     int64_t n_slots() const { return (int64_t)slots.size(); }
-    int64_t half_elems() const { return (int64_t)rows_in * cap_t; }
-    int64_t carry_at(int half, int slot) const { return ((int64_t)half * n_slots() + slot) * half_elems(); }
-    int64_t carry_elems() const { return 2 * n_slots() * half_elems(); }
+    static constexpr const char* kNull = "null causal pool";
+    static constexpr const char* kRange = kSlotOutOfRange;
+    static constexpr int kRangeLast = 0;
 
     CzPlan plan(int n, const int32_t* ids, const int64_t* n_in, const int32_t* flush, const char* what) const;
     template <class T>
@@ -387,18 +380,8 @@ struct nc_encodec_causal_pool {
 
 // every refusal that needs the slots' state, then the plan (which refuses the rest); nothing is changed
 CzPlan nc_encodec_causal_pool::plan(int n, const int32_t* ids, const int64_t* n_in, const int32_t* flush, const char* what) const {
-    if (!ids || !n_in) fail(NC_EINVAL, "%s: null pointer", what);
-    if (n <= 0) fail(NC_EINVAL, "%s: n must be positive", what);
-    std::vector<char> seen(slots.size(), 0);
-    std::vector<int64_t> T0((size_t)n), E0((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (ids[i] < 0 || ids[i] >= n_slots()) fail(NC_EINVAL, "%s: slot %d is out of range (the pool has %lld)", what, ids[i], (long long)n_slots());
-        if (seen[(size_t)ids[i]]) fail(NC_EINVAL, "%s: slot %d is named twice", what, ids[i]);
-        seen[(size_t)ids[i]] = 1;
-        const Slot& s = slots[(size_t)ids[i]];
-        if (s.ended) fail(NC_EINVAL, "%s: slot %d has been flushed: reset it before the next stream", what, ids[i]);
-        T0[(size_t)i] = s.T; E0[(size_t)i] = s.E;
-    }
+    std::vector<int64_t> T0, E0;
+    pool_named_slots(*this, n, ids, n_in, what, &Slot::E, T0, E0);
     const EncodecModel& m = model();
     return make_plan(m, g, decode, n, ids, T0.data(), E0.data(), n_in, flush, m.ragged_rows, what);
 }
@@ -435,7 +418,7 @@ void nc_encodec_causal_pool::step_dev(const CzPlan& P, const T* in, void* out, f
         const Slot& s = slots[(size_t)e.id];
         const int64_t a_n = std::min(len, std::max<int64_t>(0, e.T0 - g0)), b_n = len - a_n;
         if (len < 0 || g0 < s.base || g0 + len > e.T1 || e.T0 - s.base > cap_t) fail(NC_ESTATE, "internal: slot %d: a window leaves what the slot holds", e.id);
-        jt.add(to_carry ? j_cc : j_ca, carry_at(s.cur, e.id) + (g0 - s.base), cap_t, carry_elems(), dst, dst_rs, dst_elems, R, a_n, e.id);
+        jt.add(to_carry ? j_cc : j_ca, halves.at(s.cur, e.id) + (g0 - s.base), cap_t, halves.elems(), dst, dst_rs, dst_elems, R, a_n, e.id);
         jt.add(to_carry ? j_ic : j_ia, (int64_t)R * e.in_off + (g0 + a_n - e.T0), e.n_in, in_elems, dst + a_n, dst_rs, dst_elems, R, b_n, e.id);
     };
     for (size_t bi = 0; bi < P.batches.size(); ++bi)
@@ -449,10 +432,10 @@ void nc_encodec_causal_pool::step_dev(const CzPlan& P, const T* in, void* out, f
         if (e.row >= 0) {        // frames went out: what the next step needs, into the other half
             const int64_t base1 = decode ? std::max<int64_t>(0, e.T1 - g.carry_d) : std::max<int64_t>(0, e.E1 - g.halo_e) * g.hop;
             if (e.T1 - base1 > cap_t) fail(NC_ESTATE, "internal: slot %d keeps more than its carry holds", e.id);
-            gather(e, base1, e.T1 - base1, true, carry_at(s.cur ^ 1, e.id), cap_t, carry_elems());
+            gather(e, base1, e.T1 - base1, true, halves.at(s.cur ^ 1, e.id), cap_t, halves.elems());
         } else if (e.n_in > 0) { // nothing went out: the push is appended behind what the slot holds
             if (e.T1 - s.base > cap_t) fail(NC_ESTATE, "internal: slot %d holds more than its carry", e.id);
-            gather(e, e.T0, e.n_in, true, carry_at(s.cur, e.id) + (e.T0 - s.base), cap_t, carry_elems());
+            gather(e, e.T0, e.n_in, true, halves.at(s.cur, e.id) + (e.T0 - s.base), cap_t, halves.elems());
         }
     }
     // per batch: the rows' slots, the concatenation of carried and new LSTM frames, the new carry, the emission
@@ -612,16 +595,6 @@ void nc_encodec_causal_pool::run_decode(EncodecModel& m, const CzPlan& P, const 
 // ================================================================================================ C ABI
 namespace {
 
-nc_encodec_causal_pool& pool_of(const nc_encodec_causal_pool* p) {
-    if (!p) fail(NC_EINVAL, "null causal pool");
-    return *const_cast<nc_encodec_causal_pool*>(p);
-}
-
-nc_encodec_causal_pool::Slot& slot_of(nc_encodec_causal_pool& x, int32_t slot) {
-    if (slot < 0 || slot >= x.n_slots()) fail(NC_EINVAL, "slot %d is out of range (the pool has %lld)", slot, (long long)x.n_slots());
-    return x.slots[(size_t)slot];
-}
-
 void pool_step(nc_encodec_causal_pool& x, bool host, int32_t n, const int32_t* slots, const int64_t* n_in, const int32_t* flush, const void* in, void* out, float* emb,
                int64_t out_cap, int64_t* n_out) {
     const char* what = host ? "nc_encodec_causal_pool_step" : "nc_encodec_causal_pool_step_dev";
@@ -650,21 +623,12 @@ void pool_step(nc_encodec_causal_pool& x, bool host, int32_t n, const int32_t* s
     } else {
         OwnStreamScope own(m);
         m.lstm.note_timeout();   // (left behind by an earlier device-pointer call: not this call's failure; a causal step launches no kernel that can time out)
-        if (x.decode) {
-            h2d(x.in_stage, in, (size_t)x.nq * P.total_in * 8, m.stream);
-            x.out_stage.reserve(std::max<size_t>((size_t)need * 4, 16));
-            x.step_dev<int64_t>(P, x.in_stage.as<int64_t>(), x.out_stage.p, nullptr);
-            if (need) NC_HIP(hipMemcpyAsync(out, x.out_stage.p, (size_t)need * 4, hipMemcpyDeviceToHost, m.stream));
-        } else {
-            const size_t n_emb = (size_t)m.cfg.dimension * P.total_out * 4;
-            h2d(x.in_stage, in, (size_t)m.cfg.channels * P.total_in * 4, m.stream);
-            x.out_stage.reserve(std::max<size_t>((size_t)need * 8, 16));
-            if (emb) x.emb_stage.reserve(std::max<size_t>(n_emb, 16));
-            x.step_dev<float>(P, x.in_stage.as<float>(), x.out_stage.p, emb ? x.emb_stage.as<float>() : nullptr);
-            if (need) NC_HIP(hipMemcpyAsync(out, x.out_stage.p, (size_t)need * 8, hipMemcpyDeviceToHost, m.stream));
-            if (emb && n_emb) NC_HIP(hipMemcpyAsync(emb, x.emb_stage.p, n_emb, hipMemcpyDeviceToHost, m.stream));
-        }
-        NC_HIP(hipStreamSynchronize(m.stream));
+        if (x.decode)
+            pool_step_staged(x, m.stream, in, (size_t)x.nq * P.total_in * 8, out, (size_t)need * 4, nullptr, 0,
+                             [&](void* din, void* dout, float*) { x.step_dev<int64_t>(P, static_cast<const int64_t*>(din), dout, nullptr); });
+        else
+            pool_step_staged(x, m.stream, in, (size_t)m.cfg.channels * P.total_in * 4, out, (size_t)need * 8, emb, (size_t)m.cfg.dimension * P.total_out * 4,
+                             [&](void* din, void* dout, float* demb) { x.step_dev<float>(P, static_cast<const float*>(din), dout, demb); });
     }
     on_failure.armed = false;
     x.commit(P);
@@ -714,10 +678,11 @@ nc_status nc_encodec_causal_pool_create(nc_codec* h, int32_t decode, int32_t n_s
         const CzGeom& g = p->g;
         p->rows_in = p->decode ? p->nq : m.cfg.channels;
         p->cap_t = p->decode ? g.carry_d : std::max(g.min_e, g.halo_e + 1) * g.hop;
+        p->halves = {n_slots, (int64_t)p->rows_in * p->cap_t};
         p->keep = p->decode ? g.halo_d : g.carry_e;
         const int Cl = m.cfg.n_filters << m.cfg.n_ratios, nl = std::max(1, m.cfg.lstm_layers);
         m.use_device();
-        p->carry.reserve((size_t)std::max<int64_t>(p->carry_elems(), 4) * (p->decode ? 8 : 4));
+        p->carry.reserve((size_t)std::max<int64_t>(p->halves.elems(), 4) * (p->decode ? 8 : 4));
         p->hs.reserve((size_t)n_slots * nl * Cl * 4);
         p->cs.reserve((size_t)n_slots * nl * Cl * 4);
         p->tail.reserve((size_t)std::max<int64_t>((int64_t)n_slots * Cl * p->keep, 4) * 4);
@@ -731,10 +696,7 @@ nc_status nc_encodec_causal_pool_destroy(nc_encodec_causal_pool* p) {
 
 nc_status nc_encodec_causal_pool_reset_slot(nc_encodec_causal_pool* p, int32_t slot) {
     return guard([&] {
-        nc_encodec_causal_pool::Slot& s = slot_of(pool_of(p), slot);
-        const int cur = s.cur;   // (work already queued may still read this half; a new stream reads neither before it has written one, and starts from zero state)
-        s = nc_encodec_causal_pool::Slot{};
-        s.cur = cur;
+        reset_keep_cur(slot_of(pool_of(p), slot));
     });
 }
 

@@ -14,15 +14,17 @@
 // Kernels.  Rows are gathered from / scattered to the packed tensors by the table-driven copies of nc_ragged.hip, one launch per tensor
 // and batch (a row's [n_q, T'] block is contiguous in both layouts).  A segmented Decode ends in ONE overlap_add_ragged_kernel launch
 // that writes every clip from frames that live in different batch outputs; the decoded frames of all batches are kept in one arena
-// until then.  All tables of a call are written (and bounds-checked) on the host before anything is launched and travel in one pinned
-// image, copied once.
+// until then; it stores through store_split16 (nc_copy.h).  All tables of a call are written (and bounds-checked) on the host before
+// anything is launched and travel in one pinned image, copied once.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
 
+#include "nc_copy.h"
 #include "nc_encodec_rows.h"
 #include "nc_guard.h"
+#include "nc_pool.h"
 #include "nc_ragged.h"
 
 namespace nc {
@@ -30,28 +32,12 @@ namespace nc {
 namespace {
 
 // ---- overlap-add over all clips (OlaClip, OlaFrame, ola_sample, ola_eps: nc_encodec_rows.h) -----------------------------------------
-// blockIdx.y = (clip, channel), blockIdx.x strides over its samples.  Memory-bound, no LDS, no atomics; the output row is split at its
-// first 16-byte boundary (scalar head), whole 16-byte stores, scalar tail; the frames are read at any alignment.
+// blockIdx.y = (clip, channel), blockIdx.x strides over its samples.  Memory-bound, no LDS, no atomics; the output row is stored by
+// store_split16 (nc_copy.h) with ola_sample as its element; the frames are read at any alignment.
 __global__ __launch_bounds__(256) void overlap_add_ragged_kernel(const OlaClip* __restrict__ clips, const OlaFrame* __restrict__ fr,
                                                                  const float* __restrict__ frames, int64_t stride, float* __restrict__ pcm) {
     const OlaClip d = clips[blockIdx.y];
-    float* __restrict__ o = pcm + d.out;
-    const int64_t total = d.total;
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(o) & 15) / 4);
-    const int64_t head = mis ? (total < 4 - mis ? total : 4 - mis) : 0;
-    const int64_t nvec = (total - head) / 4, tail0 = head + nvec * 4;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    if (tid < head) o[tid] = ola_sample(d, fr, frames, stride, tid);
-    for (int64_t v = tid; v < nvec; v += nthr) {
-        const int64_t base = head + v * 4;
-        float4 x;
-        x.x = ola_sample(d, fr, frames, stride, base);
-        x.y = ola_sample(d, fr, frames, stride, base + 1);
-        x.z = ola_sample(d, fr, frames, stride, base + 2);
-        x.w = ola_sample(d, fr, frames, stride, base + 3);
-        *reinterpret_cast<float4*>(o + base) = x;
-    }
-    if (tid < total - tail0) o[tail0 + tid] = ola_sample(d, fr, frames, stride, tail0 + tid);
+    store_split16<float>(pcm + d.out, d.total, [&](int64_t t) { return ola_sample(d, fr, frames, stride, t); });
 }
 
 // ---- planner -----------------------------------------------------------------------------------------------------------------------
@@ -66,10 +52,8 @@ struct ErPlan {
 ErPlan make_plan(const EncodecModel& m, bool decode, int B, const int64_t* lengths, int32_t max_rows, const char* what) {
     if (!lengths) fail(NC_EINVAL, "%s: null pointer", what);
     if (B <= 0) fail(NC_EINVAL, "%s: B must be positive", what);
-    if (max_rows < 0 || max_rows > EncodecModel::RAGGED_MAX_ROWS)
-        fail(NC_EINVAL, "%s: max_rows must be 0 (default) .. %d", what, EncodecModel::RAGGED_MAX_ROWS);
     ErPlan P;
-    P.max_rows = max_rows > 0 ? max_rows : kDefaultRaggedRows;
+    P.max_rows = er_max_rows(max_rows, what);
     for (int b = 0; b < B; ++b) {
         if (lengths[b] <= 0) fail(NC_EINVAL, "%s: clip %d has length %lld", what, b, (long long)lengths[b]);
         if (lengths[b] > ((int64_t)1 << 30)) fail(NC_EINVAL, "%s: clip %d: T must be at most 2^30", what, b);
@@ -281,28 +265,18 @@ void EncodecModel::decode_ragged_dev(const int64_t* codes, const float* scales, 
     if (!segmented) return;
     const OlaClip* dct = reinterpret_cast<const OlaClip*>(extra);
     const OlaFrame* dft = reinterpret_cast<const OlaFrame*>(extra + ctab.size() * sizeof(OlaClip));
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (longest + 1023) / 1024), 4096);
-    for (size_t done = 0; done < ctab.size(); done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, ctab.size() - done);
+    const unsigned gx = copy_grid_x(longest, 4);
+    for_grid_y(ctab.size(), [&](size_t done, size_t cnt) {
         ProfScope ps(&prof, stream, NC_KC_ELEM, 0.0, 8.0 * (double)C * (double)P.total_decoded);
         hipLaunchKernelGGL(overlap_add_ragged_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, stream, dct + done, dft, rg_frames.as<float>(), stride, pcm);
         NC_HIP(hipGetLastError());
-    }
+    });
 }
 
 }  // namespace nc
 
 // ================================================================================================ C ABI
 using namespace nc;
-
-namespace {
-
-void h2d(DevBuf& d, const void* h, size_t n, hipStream_t s) {
-    d.reserve(std::max<size_t>(n, 16));
-    NC_HIP(hipMemcpyAsync(d.p, h, n, hipMemcpyHostToDevice, s));
-}
-
-}  // namespace
 
 extern "C" {
 

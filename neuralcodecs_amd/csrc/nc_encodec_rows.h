@@ -15,6 +15,12 @@ namespace nc {
 
 // the best measured value of profiles/encodec_ragged_bench.json
 constexpr int32_t kDefaultRaggedRows = 128;
+// rows per batch for a max_rows setting (0: the default); NC_EINVAL outside 0 .. RAGGED_MAX_ROWS
+inline int64_t er_max_rows(int32_t max_rows, const char* what) {
+    if (max_rows < 0 || max_rows > EncodecModel::RAGGED_MAX_ROWS)
+        fail(NC_EINVAL, "%s: max_rows must be 0 (default) .. %d", what, EncodecModel::RAGGED_MAX_ROWS);
+    return max_rows > 0 ? max_rows : kDefaultRaggedRows;
+}
 
 // ---- overlap-add ---------------------------------------------------------------------------------------------------------------------
 struct OlaClip {             // one (clip, channel) of the output

@@ -14,13 +14,17 @@
 // Kernels.  encodec_stream_gather_kernel: one launch per Encode step assembles every row of every batch from the slot's carry and the
 // entry's new PCM and writes every pushing slot's new carry.  overlap_add_stream_kernel: one launch per Decode step over all (entry,
 // channel) pairs writes the final samples and the new carry.  Both read one half of a slot's carry and write the other (the step then
-// flips the slot), so no thread reads what another thread of the launch writes; vector stores only, no atomics.  All tables of a step
-// are written and bounds-checked on the host before anything is launched and travel in one pinned image (nc_ragged.h).
+// flips the slot), so no thread reads what another thread of the launch writes; vector stores only, no atomics.  Both store through the
+// shared copy body (nc_copy.h); the pool's host scaffold -- two-half carry, slot lookup, a step's state refusals, host-pointer staging --
+// is nc_pool.h.  All tables of a step are written and bounds-checked on the host before anything is launched and travel in one pinned
+// image (nc_ragged.h).
 #include <algorithm>
 #include <cstring>
 
+#include "nc_copy.h"
 #include "nc_encodec_rows.h"
 #include "nc_guard.h"
+#include "nc_pool.h"
 #include "nc_ragged.h"
 
 using namespace nc;
@@ -36,86 +40,25 @@ struct EsRun { int64_t dst, a_src, a_n, b_src, b_n, to_carry; };
 // carry_dst (the last full frame's tail to the slot's other half).
 struct EsOla { OlaClip clip; int64_t t0, carry_dst, carry_src, carry_n; };
 
-constexpr int64_t kAlign = 64;   // floats: every batch tensor of an arena starts on a 256-byte boundary, as an allocation of its own would
-int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
 // ---- kernels -----------------------------------------------------------------------------------------------------------------------
-// blockIdx.y = run, blockIdx.x strides over it.  Memory-bound, no LDS, no atomics; the destination is split at its first 16-byte
-// boundary (scalar head), whole 16-byte stores, scalar tail (ragged_copy_body's split); a vector that lies in one source and is
-// 16-byte aligned there is one load.  carry_in and carry_out are the same buffer: a run reads one half of a slot and writes the other,
-// or appends behind what the slot holds.
+// blockIdx.y = run, blockIdx.x strides over it.  Memory-bound, no LDS, no atomics; a run is one concat_copy (nc_copy.h).  carry_in and
+// carry_out are the same buffer, so neither is __restrict__ here: a run reads one half of a slot and writes the other, or appends behind
+// what the slot holds.
 __global__ __launch_bounds__(256) void encodec_stream_gather_kernel(const EsRun* __restrict__ runs, const float* carry_in, const float* __restrict__ pcm,
                                                                     float* __restrict__ x, float* carry_out) {
     const EsRun g = runs[blockIdx.y];
-    const float* a = carry_in + g.a_src;
-    const float* __restrict__ b = pcm + g.b_src - g.a_n;   // b[i] for i >= a_n
-    float* d = (g.to_carry ? carry_out : x) + g.dst;
-    const int64_t total = g.a_n + g.b_n;
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(d) & 15) / 4);
-    const int64_t head = mis ? (total < 4 - mis ? total : 4 - mis) : 0;
-    const int64_t nvec = (total - head) / 4, tail0 = head + nvec * 4;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    if (tid < head) d[tid] = tid < g.a_n ? a[tid] : b[tid];
-    for (int64_t v = tid; v < nvec; v += nthr) {
-        const int64_t base = head + v * 4;
-        float4 q;
-        if (base + 4 <= g.a_n && (reinterpret_cast<uintptr_t>(a + base) & 15) == 0) {
-            q = *reinterpret_cast<const float4*>(a + base);
-        } else if (base >= g.a_n && (reinterpret_cast<uintptr_t>(b + base) & 15) == 0) {
-            q = *reinterpret_cast<const float4*>(b + base);
-        } else {
-            q.x = base < g.a_n ? a[base] : b[base];
-            q.y = base + 1 < g.a_n ? a[base + 1] : b[base + 1];
-            q.z = base + 2 < g.a_n ? a[base + 2] : b[base + 2];
-            q.w = base + 3 < g.a_n ? a[base + 3] : b[base + 3];
-        }
-        *reinterpret_cast<float4*>(d + base) = q;
-    }
-    if (tid < total - tail0) d[tail0 + tid] = tail0 + tid < g.a_n ? a[tail0 + tid] : b[tail0 + tid];
+    concat_copy<float>(carry_in + g.a_src, g.a_n, pcm + g.b_src, g.b_n, 0, (g.to_carry ? carry_out : x) + g.dst, g.a_n + g.b_n);
 }
 
-// blockIdx.y = (entry, channel), blockIdx.x strides over its samples and then over its carry.  The arithmetic is ola_sample's; the
-// stores are overlap_add_ragged_kernel's split.  `frames` holds the carry halves of every slot in front of this step's decoded frames:
-// the samples read the slot's current half and the arena, the copy writes the other half.
+// blockIdx.y = (entry, channel), blockIdx.x strides over its samples and then over its carry.  The samples are stored as in
+// overlap_add_ragged_kernel, ola_sample being the element; the carry is a concat_copy of one piece.  `frames` holds the carry halves of
+// every slot in front of this step's decoded frames: the samples read the slot's current half and the arena, the copy writes the other half.
 __global__ __launch_bounds__(256) void overlap_add_stream_kernel(const EsOla* __restrict__ jobs, const OlaFrame* __restrict__ fr, float* frames, int64_t stride,
                                                                  float* __restrict__ pcm) {
     const EsOla j = jobs[blockIdx.y];
     const OlaClip d = j.clip;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    {
-        float* __restrict__ o = pcm + d.out;
-        const int64_t total = d.total - j.t0, t0 = j.t0;
-        const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(o) & 15) / 4);
-        const int64_t head = mis ? (total < 4 - mis ? total : 4 - mis) : 0;
-        const int64_t nvec = (total - head) / 4, tail0 = head + nvec * 4;
-        if (tid < head) o[tid] = ola_sample(d, fr, frames, stride, t0 + tid);
-        for (int64_t v = tid; v < nvec; v += nthr) {
-            const int64_t base = head + v * 4;
-            float4 x;
-            x.x = ola_sample(d, fr, frames, stride, t0 + base);
-            x.y = ola_sample(d, fr, frames, stride, t0 + base + 1);
-            x.z = ola_sample(d, fr, frames, stride, t0 + base + 2);
-            x.w = ola_sample(d, fr, frames, stride, t0 + base + 3);
-            *reinterpret_cast<float4*>(o + base) = x;
-        }
-        if (tid < total - tail0) o[tail0 + tid] = ola_sample(d, fr, frames, stride, t0 + tail0 + tid);
-    }
-    {
-        const float* s = frames + j.carry_src;
-        float* c = frames + j.carry_dst;
-        const int64_t total = j.carry_n;
-        const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(c) & 15) / 4);
-        const int64_t head = mis ? (total < 4 - mis ? total : 4 - mis) : 0;
-        const int64_t nvec = (total - head) / 4, tail0 = head + nvec * 4;
-        if (tid < head) c[tid] = s[tid];
-        for (int64_t v = tid; v < nvec; v += nthr) {
-            const int64_t base = head + v * 4;
-            float4 x;
-            x.x = s[base]; x.y = s[base + 1]; x.z = s[base + 2]; x.w = s[base + 3];
-            *reinterpret_cast<float4*>(c + base) = x;
-        }
-        if (tid < total - tail0) c[tail0 + tid] = s[tail0 + tid];
-    }
+    store_split16<float>(pcm + d.out, d.total - j.t0, [&](int64_t t) { return ola_sample(d, fr, frames, stride, j.t0 + t); });
+    concat_copy<float>(frames + j.carry_src, j.carry_n, nullptr, 0, 0, frames + j.carry_dst, j.carry_n);
 }
 
 // ---- planner -----------------------------------------------------------------------------------------------------------------------
@@ -171,10 +114,8 @@ struct EsPlan {
 
 EsPlan make_plan(const EncodecModel& m, const EsGeom& g, bool decode, int n, const int32_t* ids, const int64_t* T0, const int64_t* next0, const int64_t* n_in,
                  const int32_t* flush, const int64_t* frame_lens, int32_t max_rows, const char* what) {
-    if (max_rows < 0 || max_rows > EncodecModel::RAGGED_MAX_ROWS)
-        fail(NC_EINVAL, "%s: max_rows must be 0 (default) .. %d", what, EncodecModel::RAGGED_MAX_ROWS);
     EsPlan P;
-    P.max_rows = max_rows > 0 ? max_rows : kDefaultRaggedRows;
+    P.max_rows = er_max_rows(max_rows, what);
     P.e.resize((size_t)n);
     int64_t lens_at = 0, n_rows = 0;
     for (int i = 0; i < n; ++i) {
@@ -274,13 +215,6 @@ void report(const EncodecModel& m, int nq, const EsPlan& P, nc_encodec_ragged_pl
     }
 }
 
-// (host-pointer steps run through encodec_host_run: a step changes no slot before it is through and writes only the halves of the carry
-// that the slots do not hold yet, so running it twice after a persistent-LSTM timeout is running it once)
-void h2d(DevBuf& d, const void* h, size_t n, hipStream_t s) {
-    d.reserve(std::max<size_t>(n, 16));
-    if (n) NC_HIP(hipMemcpyAsync(d.p, h, n, hipMemcpyHostToDevice, s));
-}
-
 }  // namespace
 
 // ===================================================================================================================== the pool
@@ -296,16 +230,17 @@ struct nc_encodec_stream_pool {
         int cur = 0;                     // the half of the carry that holds the slot's state
     };
     std::vector<Slot> slots;
-    int64_t cap = 0;                     // carry elements per slot and half: Encode [channels][segment_length], Decode [channels][ov]
+    TwoHalves halves;                    // of the carry; per slot and half: Encode [channels][segment_length], Decode [channels][ov]
     // Encode: `carry` is [2][n_slots][cap], `arena` the dense inputs of every batch of a step.  Decode: `arena` is the carry halves
     // followed by the decoded frames of every batch of a step -- one buffer, the frames' base of ola_sample.
     DevBuf carry, arena;
-    DevBuf in_stage, sc_stage, out_stage, sc_out, emb_out;   // the packed tensors of a host-pointer call
+    DevBuf in_stage, sc_stage, out_stage, sc_out, emb_stage;   // the packed tensors of a host-pointer call
 
     EncodecModel& model() const { return as<EncodecModel>(h); }
     int64_t n_slots() const { return (int64_t)slots.size(); }
-    int64_t carry_at(int half, int slot) const { return ((int64_t)half * n_slots() + slot) * cap; }
-    int64_t carry_elems() const { return 2 * n_slots() * cap; }
+    static constexpr const char* kNull = "null stream pool";
+    static constexpr const char* kRange = kSlotOutOfRange;
+    static constexpr int kRangeLast = 0;
 
     EsPlan plan(int n, const int32_t* ids, const int64_t* n_in, const int32_t* flush, const int64_t* frame_lens, const char* what) const;
     void check(const EsPlan& P) const;
@@ -318,18 +253,8 @@ struct nc_encodec_stream_pool {
 
 // every refusal that needs the slots' state, then the plan (which refuses the rest); nothing is changed
 EsPlan nc_encodec_stream_pool::plan(int n, const int32_t* ids, const int64_t* n_in, const int32_t* flush, const int64_t* frame_lens, const char* what) const {
-    if (!ids || !n_in) fail(NC_EINVAL, "%s: null pointer", what);
-    if (n <= 0) fail(NC_EINVAL, "%s: n must be positive", what);
-    std::vector<char> seen(slots.size(), 0);
-    std::vector<int64_t> T0((size_t)n), next0((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (ids[i] < 0 || ids[i] >= n_slots()) fail(NC_EINVAL, "%s: slot %d is out of range (the pool has %lld)", what, ids[i], (long long)n_slots());
-        if (seen[(size_t)ids[i]]) fail(NC_EINVAL, "%s: slot %d is named twice", what, ids[i]);
-        seen[(size_t)ids[i]] = 1;
-        const Slot& s = slots[(size_t)ids[i]];
-        if (s.ended) fail(NC_EINVAL, "%s: slot %d has been flushed: reset it before the next stream", what, ids[i]);
-        T0[(size_t)i] = s.T; next0[(size_t)i] = s.next;
-    }
+    std::vector<int64_t> T0, next0;
+    pool_named_slots(*this, n, ids, n_in, what, &Slot::next, T0, next0);
     const EncodecModel& m = model();
     return make_plan(m, g, decode, n, ids, T0.data(), next0.data(), n_in, flush, frame_lens, m.ragged_rows, what);
 }
@@ -349,7 +274,7 @@ void nc_encodec_stream_pool::grow_arena(EncodecModel& m, int64_t elems) {
     if (!decode || !arena.p) { arena.reserve((size_t)elems * 4); return; }
     DevBuf big;
     big.reserve((size_t)elems * 4);
-    NC_HIP(hipMemcpyAsync(big.p, arena.p, (size_t)carry_elems() * 4, hipMemcpyDeviceToDevice, m.stream));
+    NC_HIP(hipMemcpyAsync(big.p, arena.p, (size_t)halves.elems() * 4, hipMemcpyDeviceToDevice, m.stream));
     NC_HIP(hipStreamSynchronize(m.stream));   // (earlier steps on this stream still read the old buffer)
     arena = std::move(big);
 }
@@ -388,7 +313,7 @@ void nc_encodec_stream_pool::encode_dev(EncodecModel& m, const EsPlan& P, const 
         // [g0, g0 + len) of the stream: [next0 * stride, T0) is in the slot's current half, [T0, T1) in the entry's PCM
         const int64_t c0 = e.next0 * g.stride, held = e.T0 - c0;
         const int64_t a_n = std::min(len, std::max<int64_t>(0, e.T0 - g0)), b_n = len - a_n;
-        const int64_t a_src = carry_at(slots[(size_t)e.id].cur, e.id) + (int64_t)c * g.seg + (g0 - c0);
+        const int64_t a_src = halves.at(slots[(size_t)e.id].cur, e.id) + (int64_t)c * g.seg + (g0 - c0);
         const int64_t b_src = e.in_off + (int64_t)c * e.n_in + (g0 + a_n - e.T0);
         if (len <= 0 || g0 < c0 || g0 + len > e.T1 || held < 0 || held > g.seg || (a_n && g0 - c0 + a_n > held) || (b_n && (b_src < e.in_off || b_src + b_n > e.in_off + (int64_t)C * e.n_in)) ||
             dst < 0 || dst + len > dst_elems)
@@ -408,10 +333,10 @@ void nc_encodec_stream_pool::encode_dev(EncodecModel& m, const EsPlan& P, const 
         const Slot& s = slots[(size_t)e.id];
         for (int c = 0; c < C; ++c) {
             if (e.next1 != e.next0) {   // segments went out: what is kept, into the other half
-                const int64_t base = carry_at(s.cur ^ 1, e.id);
-                add_run(e, c, e.next1 * g.stride, e.n_samples, base + (int64_t)c * g.seg, true, base + cap);
+                const int64_t base = halves.at(s.cur ^ 1, e.id);
+                add_run(e, c, e.next1 * g.stride, e.n_samples, base + (int64_t)c * g.seg, true, base + halves.cap);
             } else {                    // nothing went out: the push is appended behind what the slot holds
-                const int64_t base = carry_at(s.cur, e.id);
+                const int64_t base = halves.at(s.cur, e.id);
                 add_run(e, c, e.T0, e.n_in, base + (int64_t)c * g.seg + (e.T0 - e.next0 * g.stride), true, base + (int64_t)(c + 1) * g.seg);
             }
         }
@@ -450,9 +375,8 @@ void nc_encodec_stream_pool::encode_dev(EncodecModel& m, const EsPlan& P, const 
     arena.reserve((size_t)std::max<int64_t>(x_total, 4) * 4);
     LaneScope lanes(m);
     const EsRun* druns = reinterpret_cast<const EsRun*>(rg_upload(m, t));
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (longest + 1023) / 1024), 4096);
-    for (size_t done = 0; done < runs.size(); done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, runs.size() - done);
+    const unsigned gx = copy_grid_x(longest, 4);
+    for_grid_y(runs.size(), [&](size_t done, size_t cnt) {
         double bytes = 0;
         if (m.prof.on)
             for (size_t i = 0; i < cnt; ++i) bytes += 8.0 * (double)(runs[done + i].a_n + runs[done + i].b_n);
@@ -460,7 +384,7 @@ void nc_encodec_stream_pool::encode_dev(EncodecModel& m, const EsPlan& P, const 
         hipLaunchKernelGGL(encodec_stream_gather_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, m.stream, druns + done, carry.as<float>(), pcm, arena.as<float>(),
                            carry.as<float>());
         NC_HIP(hipGetLastError());
-    }
+    });
     if (P.batches.empty()) return;   // nothing was completed: no model kernel
     m.run_batches(er_assign_lanes(P.rows, P.batches), true, [&](size_t i) {
         const ErBatch& bt = P.batches[i];
@@ -485,7 +409,7 @@ void nc_encodec_stream_pool::decode_dev(EncodecModel& m, const EsPlan& P, const 
     RgTables t;
     std::vector<size_t> first_launch;
     std::vector<int64_t> a_off;                     // of every batch's [N, C, Lo] output in the arena, behind the carry halves
-    int64_t a_total = round_up(carry_elems(), kAlign);
+    int64_t a_total = round_up(halves.elems(), kAlign);
     for (const ErBatch& bt : P.batches) {
         const int64_t N = (int64_t)bt.count, Tz = bt.key;
         first_launch.push_back(t.launches.size());
@@ -518,7 +442,7 @@ void nc_encodec_stream_pool::decode_dev(EncodecModel& m, const EsPlan& P, const 
         const int64_t first = (int64_t)ftab.size();
         std::vector<int64_t> flen;
         if (carried) {   // rows [C][ov] of the slot's current half stand for samples [stride, L_full) of the last full frame
-            ftab.push_back({carry_at(s.cur, e.id) - stride, g.L_full, g.ov});
+            ftab.push_back({halves.at(s.cur, e.id) - stride, g.L_full, g.ov});
             flen.push_back(g.L_full);
         }
         int64_t last_off = -1;
@@ -526,7 +450,7 @@ void nc_encodec_stream_pool::decode_dev(EncodecModel& m, const EsPlan& P, const 
             const int bi = e.at[r].first, row = e.at[r].second;
             if (bi < 0) fail(NC_ESTATE, "internal: slot %d: a frame without a batch", e.id);
             const int64_t Lo = P.rows[P.batches[(size_t)bi].first].len, off = a_off[(size_t)bi] + (int64_t)row * C * Lo;
-            if (off < round_up(carry_elems(), kAlign) || off + C * Lo > a_total) fail(NC_ESTATE, "internal: slot %d: a frame leaves the arena", e.id);
+            if (off < round_up(halves.elems(), kAlign) || off + C * Lo > a_total) fail(NC_ESTATE, "internal: slot %d: a frame leaves the arena", e.id);
             ftab.push_back({off, Lo, Lo});
             flen.push_back(Lo);
             last_off = off;
@@ -545,8 +469,8 @@ void nc_encodec_stream_pool::decode_dev(EncodecModel& m, const EsPlan& P, const 
             EsOla j{};
             j.clip = {C * e.out_off + c * e.n_samples, total, first, L0, nfr, c, eps, 0};
             j.t0 = t0;
-            if (keeps) { j.carry_dst = carry_at(s.cur ^ 1, e.id) + (int64_t)c * g.ov; j.carry_src = last_off + (int64_t)c * g.L_full + stride; j.carry_n = g.ov; }
-            if (j.clip.out < 0 || j.clip.out + e.n_samples > C * P.total_samples || (keeps && (j.carry_src + j.carry_n > a_total || j.carry_dst + j.carry_n > carry_elems())))
+            if (keeps) { j.carry_dst = halves.at(s.cur ^ 1, e.id) + (int64_t)c * g.ov; j.carry_src = last_off + (int64_t)c * g.L_full + stride; j.carry_n = g.ov; }
+            if (j.clip.out < 0 || j.clip.out + e.n_samples > C * P.total_samples || (keeps && (j.carry_src + j.carry_n > a_total || j.carry_dst + j.carry_n > halves.elems())))
                 fail(NC_ESTATE, "internal: slot %d: an overlap-add job leaves its tensors", e.id);
             jobs.push_back(j);
         }
@@ -576,27 +500,16 @@ void nc_encodec_stream_pool::decode_dev(EncodecModel& m, const EsPlan& P, const 
         });
     const EsOla* dj = reinterpret_cast<const EsOla*>(extra);
     const OlaFrame* dft = reinterpret_cast<const OlaFrame*>(extra + jobs.size() * sizeof(EsOla));
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (longest + 1023) / 1024), 4096);
-    for (size_t done = 0; done < jobs.size(); done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, jobs.size() - done);
+    const unsigned gx = copy_grid_x(longest, 4);
+    for_grid_y(jobs.size(), [&](size_t done, size_t cnt) {
         ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, 8.0 * (double)C * (double)P.total_samples);
         hipLaunchKernelGGL(overlap_add_stream_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, m.stream, dj + done, dft, arena.as<float>(), stride, pcm);
         NC_HIP(hipGetLastError());
-    }
+    });
 }
 
 // ================================================================================================ C ABI
 namespace {
-
-nc_encodec_stream_pool& pool_of(const nc_encodec_stream_pool* p) {
-    if (!p) fail(NC_EINVAL, "null stream pool");
-    return *const_cast<nc_encodec_stream_pool*>(p);
-}
-
-nc_encodec_stream_pool::Slot& slot_of(nc_encodec_stream_pool& x, int32_t slot) {
-    if (slot < 0 || slot >= x.n_slots()) fail(NC_EINVAL, "slot %d is out of range (the pool has %lld)", slot, (long long)x.n_slots());
-    return x.slots[(size_t)slot];
-}
 
 // elements of out_packed the step writes
 int64_t out_elems(const nc_encodec_stream_pool& x, const EsPlan& P) {
@@ -616,27 +529,23 @@ void pool_step(nc_encodec_stream_pool& x, bool host, int32_t n, const int32_t* s
     if (!host) {
         x.step_dev(P, in, scales_in, out, scales_out, emb);
     } else {
-        const int D = m.cfg.dimension;
+        // The device part runs through encodec_host_run: a step changes no slot before it is through and writes only the halves of the
+        // carry that the slots do not hold yet, so running it twice after a persistent-LSTM timeout is running it once.
         const size_t n_rows = P.rows.size();
         OwnStreamScope own(m);
         if (x.decode) {
-            h2d(x.in_stage, in, (size_t)x.nq * P.total_in * 8, m.stream);
             if (scales_in) h2d(x.sc_stage, scales_in, n_rows * 4, m.stream);
-            x.out_stage.reserve(std::max<size_t>((size_t)need * 4, 16));
-            encodec_host_run(m, [&] { x.step_dev(P, x.in_stage.p, scales_in ? x.sc_stage.as<float>() : nullptr, x.out_stage.p, nullptr, nullptr); });
-            if (need) NC_HIP(hipMemcpyAsync(out, x.out_stage.p, (size_t)need * 4, hipMemcpyDeviceToHost, m.stream));
+            pool_step_staged(x, m.stream, in, (size_t)x.nq * P.total_in * 8, out, (size_t)need * 4, nullptr, 0, [&](void* din, void* dout, float*) {
+                encodec_host_run(m, [&] { x.step_dev(P, din, scales_in ? x.sc_stage.as<float>() : nullptr, dout, nullptr, nullptr); });
+            });
         } else {
-            const size_t n_emb = (size_t)D * P.total_frames * 4;
-            h2d(x.in_stage, in, (size_t)P.total_in * 4, m.stream);
-            x.out_stage.reserve(std::max<size_t>((size_t)need * 8, 16));
             x.sc_out.reserve(std::max<size_t>(n_rows * 4, 16));
-            if (emb) x.emb_out.reserve(std::max<size_t>(n_emb, 16));
-            encodec_host_run(m, [&] { x.step_dev(P, x.in_stage.p, nullptr, x.out_stage.p, x.sc_out.as<float>(), emb ? x.emb_out.as<float>() : nullptr); });
-            if (need) NC_HIP(hipMemcpyAsync(out, x.out_stage.p, (size_t)need * 8, hipMemcpyDeviceToHost, m.stream));
-            if (scales_out && m.cfg.normalize && n_rows) NC_HIP(hipMemcpyAsync(scales_out, x.sc_out.p, n_rows * 4, hipMemcpyDeviceToHost, m.stream));
-            if (emb && n_emb) NC_HIP(hipMemcpyAsync(emb, x.emb_out.p, n_emb, hipMemcpyDeviceToHost, m.stream));
+            pool_step_staged(x, m.stream, in, (size_t)P.total_in * 4, out, (size_t)need * 8, emb, (size_t)m.cfg.dimension * P.total_frames * 4,
+                             [&](void* din, void* dout, float* demb) {
+                                 encodec_host_run(m, [&] { x.step_dev(P, din, nullptr, dout, x.sc_out.as<float>(), demb); });
+                                 if (scales_out && m.cfg.normalize && n_rows) NC_HIP(hipMemcpyAsync(scales_out, x.sc_out.p, n_rows * 4, hipMemcpyDeviceToHost, m.stream));
+                             });
         }
-        NC_HIP(hipStreamSynchronize(m.stream));
     }
     x.commit(P);
     for (size_t i = 0; i < P.e.size(); ++i) {
@@ -685,10 +594,10 @@ nc_status nc_encodec_stream_pool_create(nc_codec* h, int32_t decode, int32_t n_s
         if (n_q < 0 || n_q > m.cfg.n_codebooks) fail(NC_EINVAL, "codes carry %d codebooks; the model has %d", n_q, m.cfg.n_codebooks);
         p->nq = n_q > 0 ? n_q : m.n_q;
         p->slots.resize((size_t)n_slots);
-        p->cap = round_up((int64_t)m.cfg.channels * (p->decode ? p->g.ov : p->g.seg), 4);
+        p->halves = {n_slots, round_up((int64_t)m.cfg.channels * (p->decode ? p->g.ov : p->g.seg), 4)};
         m.use_device();
-        if (p->decode) p->arena.reserve((size_t)(round_up(p->carry_elems(), kAlign) + (int64_t)n_slots * m.cfg.channels * p->g.L_full) * 4);
-        else p->carry.reserve((size_t)p->carry_elems() * 4);
+        if (p->decode) p->arena.reserve((size_t)(round_up(p->halves.elems(), kAlign) + (int64_t)n_slots * m.cfg.channels * p->g.L_full) * 4);
+        else p->carry.reserve((size_t)p->halves.elems() * 4);
         *out = p.release();
     });
 }
@@ -699,10 +608,7 @@ nc_status nc_encodec_stream_pool_destroy(nc_encodec_stream_pool* p) {
 
 nc_status nc_encodec_stream_pool_reset_slot(nc_encodec_stream_pool* p, int32_t slot) {
     return guard([&] {
-        nc_encodec_stream_pool::Slot& s = slot_of(pool_of(p), slot);
-        const int cur = s.cur;   // (work already queued may still read this half; a new stream reads neither before it has written one)
-        s = nc_encodec_stream_pool::Slot{};
-        s.cur = cur;
+        reset_keep_cur(slot_of(pool_of(p), slot));
     });
 }
 

@@ -14,12 +14,14 @@
 //
 // Kernels.  One table-driven copy per tensor and launch batch instead of one pitched copy per window: a descriptor is a run of n elements
 // from src to dst followed by `fill` zeros.  The host writes all tables of a call into pinned memory and copies them once, asynchronously,
-// on the handle's stream.
+// on the handle's stream.  The copy is concat_copy (nc_copy.h), the launch loop over grid.y for_grid_y (nc_pool.h).
 #include <algorithm>
 #include <cstring>
 #include <map>
 
+#include "nc_copy.h"
 #include "nc_guard.h"
+#include "nc_pool.h"
 #include "nc_ragged.h"
 
 namespace nc {
@@ -27,37 +29,12 @@ namespace nc {
 namespace {
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
-// Memory-bound, no LDS, no atomics.  blockIdx.y = descriptor, blockIdx.x strides over its run.  The destination side is written with
-// 16-byte stores: the run is split at the first 16-byte boundary of dst (scalar head), whole vectors, scalar tail.  The source has any
-// element alignment: consecutive lanes read consecutive vectors, so its dword loads of one wavefront cover one contiguous span; where
-// the source vector happens to be 16-byte aligned as well it is one load.
-template <class T>
-struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
-
+// Memory-bound, no LDS, no atomics.  blockIdx.y = descriptor, blockIdx.x strides over its run, which concat_copy (nc_copy.h) stores: a
+// run of n source elements followed by `fill` zeros is the concatenation of one piece.
 template <class T>
 __device__ __forceinline__ void ragged_copy_body(const RgSeg* __restrict__ segs, const T* __restrict__ src, T* __restrict__ dst) {
-    constexpr int V = 16 / sizeof(T);
     const RgSeg g = segs[blockIdx.y];
-    const T* __restrict__ s = src + g.src;
-    T* __restrict__ d = dst + g.dst;
-    const int64_t n = g.n, total = g.n + g.fill;
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(d) & 15) / sizeof(T));
-    const int64_t head = mis ? (total < V - mis ? total : V - mis) : 0;
-    const int64_t nvec = (total - head) / V, tail0 = head + nvec * V;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    if (tid < head) d[tid] = tid < n ? s[tid] : T(0);
-    for (int64_t v = tid; v < nvec; v += stride) {
-        const int64_t base = head + v * V;
-        Vec16<T> x;
-        if (base + V <= n && (reinterpret_cast<uintptr_t>(s + base) & 15) == 0) {
-            x = *reinterpret_cast<const Vec16<T>*>(s + base);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) x.v[j] = base + j < n ? s[base + j] : T(0);
-        }
-        *reinterpret_cast<Vec16<T>*>(d + base) = x;
-    }
-    if (tid < total - tail0) d[tail0 + tid] = tail0 + tid < n ? s[tail0 + tid] : T(0);
+    concat_copy<T>(src + g.src, g.n, nullptr, 0, 0, dst + g.dst, g.n + g.fill);
 }
 
 // packed PCM (or SNAC noise) -> dense window rows, zero-filled behind a clip's end
@@ -212,18 +189,16 @@ const char* upload(Codec& m, const Tables& t) {
 
 template <class T>
 void launch(Codec& m, const Tables& t, size_t which, void (*kernel)(const RgSeg*, const T*, T*), const T* src, T* dst) {
-    constexpr int64_t per_block = 256 * (16 / sizeof(T));
     const Tables::Launch& L = t.launches[which];
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div(L.longest, per_block)), 4096);
-    for (size_t done = 0; done < L.count; done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, L.count - done);
+    const unsigned gx = copy_grid_x(L.longest, sizeof(T));
+    for_grid_y(L.count, [&](size_t done, size_t cnt) {
         double bytes = 0;
         if (m.prof.on)
             for (size_t i = 0; i < cnt; ++i) { const RgSeg& g = t.segs[L.first + done + i]; bytes += (double)(2 * g.n + g.fill) * sizeof(T); }
         ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
         hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, m.stream, m.rg_tab.dev.as<RgSeg>() + L.first + done, src, dst);
         NC_HIP(hipGetLastError());
-    }
+    });
 }
 
 std::vector<int64_t> prefix(int B, const std::vector<int64_t>& per_clip) {

@@ -1,59 +1,17 @@
 // What incremental sessions (nc_session.hip) and the session pool (nc_session_pool.hip) share: the schedule of one stream, the row
-// families of its tensors, the frame arithmetic of one step and the device-side copy of a concatenation.
+// families of its tensors and the frame arithmetic of one step.  The device-side copy of a concatenation that
+// their kernels are made of is concat_copy (nc_copy.h).
 #pragma once
 #include <algorithm>
 
+#include "nc_copy.h"
 #include "nc_guard.h"
 
 namespace nc {
 
 constexpr int SS_MAX_LEVELS = 8;
 
-// ---- device side -----------------------------------------------------------------------------------------------------------------
-template <class T>
-struct alignas(16) SsVec16 { T v[16 / sizeof(T)]; };
-
-// element i of a[0, na) ++ b[0, nb) ++ zeros
-template <class T>
-__device__ __forceinline__ T cat_at(const T* __restrict__ a, int64_t na, const T* __restrict__ b, int64_t nb, int64_t i) {
-    return i < na ? a[i] : (i < na + nb ? b[i - na] : T(0));
-}
-
-// d[j] = (a ++ b ++ zeros)[s0 + j] for j in [0, total): reads stay inside a[0, na) and b[0, nb), writes inside d[0, total).
-// 16-byte stores from the first 16-byte boundary of d, a scalar head in front and a scalar tail behind; a 16-byte load where the source
-// vector lies in one aligned piece.  blockIdx.x strides over the run.
-template <class T>
-__device__ __forceinline__ void concat_copy(const T* __restrict__ a, int64_t na, const T* __restrict__ b, int64_t nb, int64_t s0,
-                                            T* __restrict__ d, int64_t total) {
-    constexpr int V = 16 / sizeof(T);
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(d) & 15) / sizeof(T));
-    const int64_t head = mis ? (total < V - mis ? total : V - mis) : 0;
-    const int64_t nvec = (total - head) / V, tail0 = head + nvec * V;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    if (tid < head) d[tid] = cat_at(a, na, b, nb, s0 + tid);
-    for (int64_t v = tid; v < nvec; v += stride) {
-        const int64_t base = head + v * V, i = s0 + base;
-        const T* p = nullptr;   // the vector lies inside one of the two pieces
-        if (i + V <= na) p = a + i;
-        else if (i >= na && i + V <= na + nb) p = b + (i - na);
-        SsVec16<T> x;
-        if (p && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            x = *reinterpret_cast<const SsVec16<T>*>(p);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) x.v[j] = cat_at(a, na, b, nb, i + j);
-        }
-        *reinterpret_cast<SsVec16<T>*>(d + base) = x;
-    }
-    if (tid < total - tail0) d[tail0 + tid] = cat_at(a, na, b, nb, s0 + tail0 + tid);
-}
-
 inline int64_t ss_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-inline unsigned ss_grid_x(int64_t longest, size_t elt) {
-    const int64_t per_block = 256 * (16 / (int64_t)elt);
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(1, ss_ceil_div(longest, per_block)), 4096);
-}
 
 // ---- schedule --------------------------------------------------------------------------------------------------------------------
 struct SsStep { int64_t w0, w1, k0, k1, h0n; };   // window, kept frames, first resident frame afterwards

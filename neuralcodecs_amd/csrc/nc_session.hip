@@ -25,7 +25,7 @@ namespace nc {
 namespace {
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
-// (concat_copy, the copy both kernels are made of: nc_session.h)
+// (concat_copy, the copy both kernels are made of: nc_copy.h)
 // One row family of an assembly launch (a code level, a noise stage, the PCM): `rows` rows, each hist_n resident elements followed by
 // new_n pushed ones.  The window row takes the first win_n elements of that concatenation (+0 behind its end); the next history is
 // its elements [next_off, hist_n + new_n).  History rows are dense; the pushed data and the window have a base and a row pitch.
@@ -104,7 +104,7 @@ void assemble(Codec& m, void (*kernel)(SsArgs, const T*, const T*, T*, T*), cons
     }
     if (longest <= 0) return;
     ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
-    hipLaunchKernelGGL(kernel, dim3(ss_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)(2 * f.nl)), dim3(256), 0, m.stream, a, hist, nw, win, next);
+    hipLaunchKernelGGL(kernel, dim3(copy_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)(2 * f.nl)), dim3(256), 0, m.stream, a, hist, nw, win, next);
     NC_HIP(hipGetLastError());
 }
 
@@ -121,7 +121,7 @@ void emit(Codec& m, void (*kernel)(SsEmitArgs, const T*, T*), int nl, int rows, 
     }
     if (longest <= 0) return;
     ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, bytes);
-    hipLaunchKernelGGL(kernel, dim3(ss_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)nl), dim3(256), 0, m.stream, a, src, dst);
+    hipLaunchKernelGGL(kernel, dim3(copy_grid_x(longest, sizeof(T)), (unsigned)rows, (unsigned)nl), dim3(256), 0, m.stream, a, src, dst);
     NC_HIP(hipGetLastError());
 }
 

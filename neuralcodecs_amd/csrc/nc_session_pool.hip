@@ -15,11 +15,13 @@
 //   emit                     the kept columns of a group's output go to the packed output with the table-driven copy of the ragged calls
 //                            (RgTables / rg_copy_*: one source run per descriptor is all an emit needs), one launch per group.
 // All descriptors of a step are written and bounds-checked on the host first and travel in one pinned image with one asynchronous copy
-// (rg_upload).  No LDS, no atomics; profile class NC_KC_ELEM.
+// (rg_upload).  No LDS, no atomics; profile class NC_KC_ELEM.  The copy is concat_copy (nc_copy.h); the two-half addressing, the slot
+// lookup and the grid.y launch loop are nc_pool.h's.
 #include <cstring>
 #include <map>
 #include <vector>
 
+#include "nc_pool.h"
 #include "nc_ragged.h"
 #include "nc_session.h"
 
@@ -66,13 +68,12 @@ struct SegTable {
 template <class T>
 void launch_assemble(Codec& m, void (*kernel)(const PoolSeg*, T*, const T*, T*), const SegTable& t, const PoolSeg* dev, T* hist, const T* nw, T* win) {
     if (t.segs.empty()) return;
-    const unsigned gx = ss_grid_x(t.longest, sizeof(T));
+    const unsigned gx = copy_grid_x(t.longest, sizeof(T));
     ProfScope ps(&m.prof, m.stream, NC_KC_ELEM, 0.0, t.bytes);
-    for (size_t done = 0; done < t.segs.size(); done += 65535) {   // grid.y holds 65535 descriptors
-        const size_t cnt = std::min<size_t>(65535, t.segs.size() - done);
+    for_grid_y(t.segs.size(), [&](size_t done, size_t cnt) {
         hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, m.stream, dev + done, hist, nw, win);
         NC_HIP(hipGetLastError());
-    }
+    });
 }
 
 // ---- grouping ----------------------------------------------------------------------------------------------------------------------
@@ -97,8 +98,6 @@ std::vector<PoolGroup> group_windows(int n, const int64_t* width, int max_rows, 
     return groups;
 }
 
-int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
 }  // namespace nc
@@ -113,12 +112,14 @@ struct nc_session_pool {
         uint64_t seed = 0;
     };
     std::vector<Slot> slots;
-    int64_t cap_main = 0, cap_noise = 0;   // elements per slot and slab
-    DevBuf hist, nhist;           // [2][n_slots][cap]: a slot's history is in half st.cur, its next one goes to the other half
+    TwoHalves main, noise;        // of hist and nhist: a slot's history is in half st.cur, its next one goes to the other half
+    DevBuf hist, nhist;           // [2][n_slots][cap]
     DevBuf in_stage, nz_stage, out_stage;   // host-pointer calls and drawn noise
 
     int64_t n_slots() const { return (int64_t)slots.size(); }
-    int64_t hist_at(int half, int slot, int64_t cap) const { return ((int64_t)half * n_slots() + slot) * cap; }
+    static constexpr const char* kNull = "null session pool";
+    static constexpr const char* kRange = "slot %d is outside 0..%lld";
+    static constexpr int kRangeLast = 1;
 };
 
 namespace {
@@ -130,16 +131,6 @@ struct Entry {
     int group = -1, row = 0;
     int64_t in_off = 0, nz_off = 0, out_off = 0;
 };
-
-nc_session_pool& pool_of(const nc_session_pool* p) {
-    if (!p) fail(NC_EINVAL, "null session pool");
-    return *const_cast<nc_session_pool*>(p);
-}
-
-nc_session_pool::Slot& slot_of(nc_session_pool& p, int32_t slot) {
-    if (slot < 0 || slot >= p.n_slots()) fail(NC_EINVAL, "slot %d is outside 0..%lld", slot, (long long)p.n_slots() - 1);
-    return p.slots[(size_t)slot];
-}
 
 // Every entry checked against its slot and moved on frame counts alone; nothing changes.
 std::vector<Entry> plan_entries(nc_session_pool& p, int32_t n, const int32_t* slots, const int64_t* n_in) {
@@ -191,8 +182,8 @@ void pool_step(nc_session_pool& p, bool host, int32_t n, const int32_t* slots, c
         const int64_t cnt = (int64_t)groups[gi].entries.size(), Wf = groups[gi].W;
         for (size_t r = 0; r < groups[gi].entries.size(); ++r) { es[(size_t)groups[gi].entries[r]].group = (int)gi; es[(size_t)groups[gi].entries[r]].row = (int)r; }
         wbase[gi] = win_n; nbase[gi] = nwin_n;
-        win_n = round_up(win_n + cnt * rps * g.main.total(Wf * per), 64);
-        if (g.with_noise) nwin_n = round_up(nwin_n + cnt * g.noise.total(Wf), 64);
+        win_n = round_up(win_n + cnt * rps * g.main.total(Wf * per), kAlign);
+        if (g.with_noise) nwin_n = round_up(nwin_n + cnt * g.noise.total(Wf), kAlign);
         const SessionMove& mv = es[(size_t)groups[gi].entries[0]].mv;
         if (g.decode) {
             res_n = std::max(res_n, cnt * mv.Lw);
@@ -209,7 +200,7 @@ void pool_step(nc_session_pool& p, bool host, int32_t n, const int32_t* slots, c
     for (const Entry& e : es) {
         const SessionMove& mv = e.mv;
         const int cur = p.slots[(size_t)e.slot].st.cur;
-        const int64_t h_lo = p.hist_at(cur, e.slot, p.cap_main), x_lo = p.hist_at(1 - cur, e.slot, p.cap_main);
+        const int64_t h_lo = p.main.at(cur, e.slot), x_lo = p.main.at(1 - cur, e.slot);
         const Lay lh = lay_of(g.main, mv.hist_u, rps, false), ln = lay_of(g.main, mv.new_u, rps, g.main.row_major), lx = lay_of(g.main, mv.next_u, rps, false);
         Lay lw{};
         int64_t grows = 0;
@@ -222,21 +213,21 @@ void pool_step(nc_session_pool& p, bool host, int32_t n, const int32_t* slots, c
                 const int64_t a = h_lo + lh.base[i] + q * lh.len[i], b = e.in_off + ln.base[i] + q * ln.pitch[i];
                 if (mv.run)
                     tm.add({a, lh.len[i], b, ln.len[i], 0, wbase[(size_t)e.group] + lw.base[i] + ((int64_t)e.row * rps + q) * lw.pitch[i], lw.len[i], 0}, h_lo,
-                           h_lo + p.cap_main, x_lo, x_lo + p.cap_main, in_n, win_n, elt);
-                tm.add({a, lh.len[i], b, ln.len[i], lh.len[i] + ln.len[i] - lx.len[i], x_lo + lx.base[i] + q * lx.len[i], lx.len[i], 1}, h_lo, h_lo + p.cap_main,
-                       x_lo, x_lo + p.cap_main, in_n, win_n, elt);
+                           h_lo + p.main.cap, x_lo, x_lo + p.main.cap, in_n, win_n, elt);
+                tm.add({a, lh.len[i], b, ln.len[i], lh.len[i] + ln.len[i] - lx.len[i], x_lo + lx.base[i] + q * lx.len[i], lx.len[i], 1}, h_lo, h_lo + p.main.cap,
+                       x_lo, x_lo + p.main.cap, in_n, win_n, elt);
             }
         if (g.with_noise) {
-            const int64_t zh = p.hist_at(cur, e.slot, p.cap_noise), zx = p.hist_at(1 - cur, e.slot, p.cap_noise);
+            const int64_t zh = p.noise.at(cur, e.slot), zx = p.noise.at(1 - cur, e.slot);
             const Lay zl = lay_of(g.noise, mv.hist_u, 1, false), zn = lay_of(g.noise, mv.new_u, 1, false), zz = lay_of(g.noise, mv.next_u, 1, false);
             Lay zw{};
             if (mv.run) zw = lay_of(g.noise, mv.Wf, (int64_t)groups[(size_t)e.group].entries.size(), false);
             for (int i = 0; i < g.noise.nl; ++i) {
                 const int64_t a = zh + zl.base[i], b = e.nz_off + zn.base[i];
                 if (mv.run)
-                    tz.add({a, zl.len[i], b, zn.len[i], 0, nbase[(size_t)e.group] + zw.base[i] + (int64_t)e.row * zw.pitch[i], zw.len[i], 0}, zh, zh + p.cap_noise, zx,
-                           zx + p.cap_noise, nz_n, nwin_n, 4);
-                tz.add({a, zl.len[i], b, zn.len[i], zl.len[i] + zn.len[i] - zz.len[i], zx + zz.base[i], zz.len[i], 1}, zh, zh + p.cap_noise, zx, zx + p.cap_noise, nz_n,
+                    tz.add({a, zl.len[i], b, zn.len[i], 0, nbase[(size_t)e.group] + zw.base[i] + (int64_t)e.row * zw.pitch[i], zw.len[i], 0}, zh, zh + p.noise.cap, zx,
+                           zx + p.noise.cap, nz_n, nwin_n, 4);
+                tz.add({a, zl.len[i], b, zn.len[i], zl.len[i] + zn.len[i] - zz.len[i], zx + zz.base[i], zz.len[i], 1}, zh, zh + p.noise.cap, zx, zx + p.noise.cap, nz_n,
                        nwin_n, 4);
             }
         }
@@ -370,12 +361,12 @@ nc_status nc_session_pool_create(nc_codec* h, int32_t decode, int32_t n_slots, i
         // a stream holds at most hl + hr + align frames (invariant 1); encode: as samples, plus less than one hop * align buffered
         const SessionGeom& g = p->g;
         const int64_t cap_f = g.hl + g.hr + g.align;
-        p->cap_main = round_up((int64_t)g.rows() * g.main.total(g.decode ? cap_f : cap_f * g.hop + g.unit()), 4);
-        if (g.with_noise) p->cap_noise = round_up(g.noise.total(cap_f), 4);
+        p->main = {n_slots, round_up((int64_t)g.rows() * g.main.total(g.decode ? cap_f : cap_f * g.hop + g.unit()), 4)};
+        if (g.with_noise) p->noise = {n_slots, round_up(g.noise.total(cap_f), 4)};
         Codec& m = codec_of(h);
         m.use_device();
-        p->hist.reserve((size_t)(2 * n_slots * p->cap_main) * g.elt());
-        if (g.with_noise) p->nhist.reserve((size_t)(2 * n_slots * p->cap_noise) * 4);
+        p->hist.reserve((size_t)p->main.elems() * g.elt());
+        if (g.with_noise) p->nhist.reserve((size_t)p->noise.elems() * 4);
         *out = p.release();
     });
 }
@@ -385,7 +376,7 @@ nc_status nc_session_pool_destroy(nc_session_pool* p) {
 }
 
 nc_status nc_session_pool_reset_slot(nc_session_pool* p, int32_t slot) {
-    return guard([&] { slot_of(pool_of(p), slot).st = SessionState{}; });
+    return guard([&] { reset_keep_cur(slot_of(pool_of(p), slot).st); });
 }
 
 nc_status nc_session_pool_set_seed(nc_session_pool* p, int32_t slot, uint64_t seed) {
@@ -421,6 +412,36 @@ nc_status nc_session_pool_step(nc_session_pool* p, int32_t n, const int32_t* slo
         OwnStreamScope own(m);
         pool_step(x, true, n, slots, n_in, in_packed, noise_packed, out_packed, out_cap, n_out);
         NC_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+// test hook: concat_copy (nc_copy.h) alone, as ONE pool_assemble launch over n_desc descriptors (a_off, na, b_off, nb, s0, dst_off, n)
+nc_status nc_op_concat_copy(int device_index, int32_t elt, const void* a, int64_t a_n, const void* b, int64_t b_n, void* dst, int64_t dst_n,
+                            const int64_t* desc, int64_t n_desc) {
+    return guard([&] {
+        if (!a || !b || !dst || !desc) fail(NC_EINVAL, "null argument");
+        if ((elt != 4 && elt != 8) || a_n <= 0 || b_n <= 0 || dst_n <= 0 || n_desc <= 0 || n_desc > 65535)
+            fail(NC_EINVAL, "elt must be 4 or 8, the arrays non-empty, n_desc in 1..65535 (one launch)");
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
+        if (device_index < 0 || device_index >= n_dev) fail(NC_EINVAL, "device index out of range");
+        NC_HIP(hipSetDevice(device_index));
+        SegTable t;
+        for (int64_t i = 0; i < n_desc; ++i) {
+            const int64_t* d = desc + 7 * i;
+            t.add({d[0], d[1], d[2], d[3], d[4], d[5], d[6], 0}, 0, a_n, 0, 0, b_n, dst_n, (size_t)elt);
+        }
+        if (t.segs.empty()) return;
+        DevBuf da, db, dd, ds;
+        h2d(da, a, (size_t)a_n * elt, nullptr);
+        h2d(db, b, (size_t)b_n * elt, nullptr);
+        h2d(dd, dst, (size_t)dst_n * elt, nullptr);
+        h2d(ds, t.segs.data(), t.segs.size() * sizeof(PoolSeg), nullptr);
+        const dim3 grid(copy_grid_x(t.longest, (size_t)elt), (unsigned)t.segs.size());
+        if (elt == 4) hipLaunchKernelGGL(pool_assemble_f32, grid, dim3(256), 0, nullptr, ds.as<PoolSeg>(), da.as<float>(), db.as<float>(), dd.as<float>());
+        else hipLaunchKernelGGL(pool_assemble_i64, grid, dim3(256), 0, nullptr, ds.as<PoolSeg>(), da.as<int64_t>(), db.as<int64_t>(), dd.as<int64_t>());
+        NC_HIP(hipGetLastError());
+        NC_HIP(hipMemcpy(dst, dd.p, (size_t)dst_n * elt, hipMemcpyDeviceToHost));
     });
 }
 

@@ -456,28 +456,25 @@ def encodec_stream_plan(config: EncodecConfig, pushed, emitted, n_in, flush=None
             [{"n_frames": int(nf[i]), "code_frames": int(cf[i]), "n_samples": int(ns[i])} for i in range(n)])
 
 
-class EncodecStreamPool:
-    """n_slots independent live streams on one segmented Encodec model, one direction, stepped together (nc_encodec_stream_pool_*).
-
-        out = pool.step({slot: x | FLUSH | (x, FLUSH), ...})
-
-    encode pool: x is PCM [channels, n] (any n >= 0); out[slot] is the list of EncodedFrame (leading batch of 1) of the segments the push
-    completed -- often empty.  decode pool: x is a list of EncodedFrame [1, n_q, F]; out[slot] is PCM [channels, n_out].  FLUSH ends the
-    slot's stream (after the last x of a tuple) and emits the rest; reset_slot() makes the slot new.  Everything a slot emitted, end to
-    end, equals encode() / decode() on the whole stream, bit for bit.  numpy in, numpy out (host API); torch device tensors in, device
-    tensors out on torch's current stream."""
+class _EncodecPool:
+    """What the two Encodec pools share: the lifetime of the C pool behind nc_encodec_<_PREFIX>_pool_*, the calls on one slot, the split
+    of an entry's value, the ctypes arrays of a step and its torch-or-numpy side."""
+    _PREFIX = ""
 
     def __init__(self, model: Encodec, decode: bool, n_slots: int, n_q: Optional[int]):
         self.model, self.decode, self.n_slots = model, bool(decode), int(n_slots)
         self._p = C.c_void_p()
         self._torch = False
-        _lib.check(_lib.lib().nc_encodec_stream_pool_create(model._h, 1 if decode else 0, int(n_slots), int(n_q or 0), C.byref(self._p)))
+        _lib.check(self._sym("create")(model._h, 1 if decode else 0, int(n_slots), int(n_q or 0), C.byref(self._p)))
         self.n_q = int(n_q) if n_q else model.query(1)[1]
+
+    def _sym(self, name):
+        return getattr(_lib.lib(), f"nc_encodec_{self._PREFIX}_pool_{name}")
 
     def close(self) -> None:
         if getattr(self, "_p", None) is not None and self._p.value:
             try:
-                _lib.lib().nc_encodec_stream_pool_destroy(self._p)
+                self._sym("destroy")(self._p)
             finally:
                 self._p = C.c_void_p()
 
@@ -494,11 +491,11 @@ class EncodecStreamPool:
             pass
 
     def reset_slot(self, slot: int) -> None:
-        _lib.check(_lib.lib().nc_encodec_stream_pool_reset_slot(self._p, int(slot)))
+        _lib.check(self._sym("reset_slot")(self._p, int(slot)))
 
     def pending(self, slot: int) -> int:
         n = C.c_int64()
-        _lib.check(_lib.lib().nc_encodec_stream_pool_pending(self._p, int(slot), C.byref(n)))
+        _lib.check(self._sym("pending")(self._p, int(slot), C.byref(n)))
         return n.value
 
     @staticmethod
@@ -511,6 +508,69 @@ class EncodecStreamPool:
         if v is None:
             raise ValueError("the pushed data must not be null (FLUSH ends a stream)")
         return v, False
+
+    @staticmethod
+    def _c(slots, n_in, flush):
+        n = len(slots)
+        return (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+
+    def _io(self):
+        """-> (empty(k, dtype), ptr(x), cat(parts, dtype), float32, int64, the step symbol) on torch device tensors (torch's current
+        stream) or on numpy arrays, whichever the last entries were"""
+        if self._torch:
+            import torch
+            dev = torch.device("cuda", self.model.device_index)
+            empty = lambda k, dt: torch.empty((max(1, k),), dtype=dt, device=dev)  # noqa: E731
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            cat = lambda parts, dt: torch.cat([p.reshape(-1).to(dt) for p in parts]).contiguous() if parts else empty(0, dt)  # noqa: E731
+            self.model._bind_torch_stream()
+            return empty, ptr, cat, torch.float32, torch.int64, self._sym("step_dev")
+        empty = lambda k, dt: np.empty((max(1, k),), dt)  # noqa: E731
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dt).reshape(-1) for p in parts])) if parts else empty(0, dt)  # noqa: E731
+        return empty, ptr, cat, np.float32, np.int64, self._sym("step")
+
+
+class _EncodecPoolSession:
+    def __init__(self, pool):
+        self.pool = pool
+
+    def push(self, x, **kw):
+        out = self.pool.step({0: x}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def flush(self, x=None, **kw):
+        out = self.pool.step({0: FLUSH if x is None else (x, FLUSH)}, **kw)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def pending(self) -> int:
+        return self.pool.pending(0)
+
+    def reset(self) -> None:
+        self.pool.reset_slot(0)
+
+    def close(self) -> None:
+        self.pool.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class EncodecStreamPool(_EncodecPool):
+    """n_slots independent live streams on one segmented Encodec model, one direction, stepped together (nc_encodec_stream_pool_*).
+
+        out = pool.step({slot: x | FLUSH | (x, FLUSH), ...})
+
+    encode pool: x is PCM [channels, n] (any n >= 0); out[slot] is the list of EncodedFrame (leading batch of 1) of the segments the push
+    completed -- often empty.  decode pool: x is a list of EncodedFrame [1, n_q, F]; out[slot] is PCM [channels, n_out].  FLUSH ends the
+    slot's stream (after the last x of a tuple) and emits the rest; reset_slot() makes the slot new.  Everything a slot emitted, end to
+    end, equals encode() / decode() on the whole stream, bit for bit.  numpy in, numpy out (host API); torch device tensors in, device
+    tensors out on torch's current stream."""
+
+    _PREFIX = "stream"
 
     def _entries(self, entries: dict):
         if not entries:
@@ -548,8 +608,7 @@ class EncodecStreamPool:
     def _query(self, slots, flush, n_in, lens):
         n = len(slots)
         nf, cf, ns = (C.c_int32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
-        _lib.check(_lib.lib().nc_encodec_stream_pool_query(self._p, n, (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush]),
-                                                           _lib.i64_array(lens) if lens is not None else None, nf, cf, ns))
+        _lib.check(self._sym("query")(self._p, n, *self._c(slots, n_in, flush), _lib.i64_array(lens) if lens is not None else None, nf, cf, ns))
         return [int(x) for x in nf], [int(x) for x in cf], [int(x) for x in ns]
 
     def plan(self, entries: dict):
@@ -560,40 +619,25 @@ class EncodecStreamPool:
 
     def _plan(self, slots, flush, n_in, lens):
         n = len(slots)
-        c_slots, c_n_in, c_flush = (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+        c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
         c_lens = _lib.i64_array(lens) if lens is not None else None
-        return _ragged_rows(lambda _n, _l, p, rows, cap: _lib.lib().nc_encodec_stream_pool_plan(self._p, n, c_slots, c_n_in, c_flush, c_lens, p, rows, cap),
+        return _ragged_rows(lambda _n, _l, p, rows, cap: self._sym("plan")(self._p, n, c_slots, c_n_in, c_flush, c_lens, p, rows, cap),
                             [], self.decode)
 
     def step(self, entries: dict, return_emb: bool = False) -> dict:
         slots, data, flush, n_in, lens = self._entries(entries)
         n = len(slots)
         nf, cf, ns = self._query(slots, flush, n_in, lens)                 # every refusal that needs no device, and the sizes
-        L, m = _lib.lib(), self.model
+        m = self.model
         Cn, D, nq = m.config.channels, m.config.dimension, (self.n_q if self.decode else m.query(1)[1])
-        c_slots, c_n_in, c_flush = (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
+        c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
         c_lens = _lib.i64_array(lens) if lens is not None else None
         seg_frames = None
         if not self.decode:                                                 # code frames of every segment an entry emits, in segment order
             seg_frames = [[] for _ in slots]
             for r in sorted(self._plan(slots, flush, n_in, lens)[1], key=lambda r: (r["clip"], r["segment"])):
                 seg_frames[r["clip"]].append(r["frames"])
-        on_dev = self._torch
-        if on_dev:
-            import torch
-            dev = torch.device("cuda", m.device_index)
-            empty = lambda k, dt: torch.empty((max(1, k),), dtype=dt, device=dev)  # noqa: E731
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            f32, i64 = torch.float32, torch.int64
-            cat = lambda parts, dt: torch.cat([p.reshape(-1).to(dt) for p in parts]).contiguous() if parts else empty(0, dt)  # noqa: E731
-            m._bind_torch_stream()
-            fn = L.nc_encodec_stream_pool_step_dev
-        else:
-            empty = lambda k, dt: np.empty((max(1, k),), dt)  # noqa: E731
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-            f32, i64 = np.float32, np.int64
-            cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dt).reshape(-1) for p in parts])) if parts else empty(0, dt)  # noqa: E731
-            fn = L.nc_encodec_stream_pool_step
+        empty, ptr, cat, f32, i64, fn = self._io()
         if self.decode:
             codes = cat([f.codes for fl in data for f in fl], i64)
             scales = cat([f.scale for fl in data for f in fl], f32) if m.config.normalize else None
@@ -617,34 +661,8 @@ class EncodecStreamPool:
         return (res, embs) if return_emb else res
 
 
-class EncodecStreamSession:
+class EncodecStreamSession(_EncodecPoolSession):
     """One live stream: a stream pool with one slot.  push(x) -> what became final; flush([x]) ends the stream; reset() starts anew."""
-
-    def __init__(self, pool: EncodecStreamPool):
-        self.pool = pool
-
-    def push(self, x, **kw):
-        out = self.pool.step({0: x}, **kw)
-        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
-
-    def flush(self, x=None, **kw):
-        out = self.pool.step({0: FLUSH if x is None else (x, FLUSH)}, **kw)
-        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
-
-    def pending(self) -> int:
-        return self.pool.pending(0)
-
-    def reset(self) -> None:
-        self.pool.reset_slot(0)
-
-    def close(self) -> None:
-        self.pool.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def _causal_rows(call):
@@ -672,7 +690,7 @@ def encodec_causal_plan(config: EncodecConfig, received=(0,), emitted=(0,), n_in
     return {k: int(getattr(info, k)) for k, _ in _lib.NcEncodecCausalInfo._fields_}, n_batches, rows, [int(n_out[i]) for i in range(n)]
 
 
-class EncodecCausalPool:
+class EncodecCausalPool(_EncodecPool):
     """n_slots independent live streams on one causal Encodec model without segmentation (the 24 kHz preset), one direction, stepped
     together (nc_encodec_causal_pool_*; Encodec.Encode / Encodec.Decode with SLSTM.forward's state carried).
 
@@ -683,39 +701,7 @@ class EncodecCausalPool:
     tuple) and emits the rest; reset_slot() makes the slot new.  Everything a slot emitted, end to end, equals encode() / decode() on the
     whole stream, bit for bit.  numpy in, numpy out (host API); torch device tensors in, device tensors out on torch's current stream."""
 
-    def __init__(self, model: Encodec, decode: bool, n_slots: int, n_q: Optional[int]):
-        self.model, self.decode, self.n_slots = model, bool(decode), int(n_slots)
-        self._p = C.c_void_p()
-        self._torch = False
-        _lib.check(_lib.lib().nc_encodec_causal_pool_create(model._h, 1 if decode else 0, int(n_slots), int(n_q or 0), C.byref(self._p)))
-        self.n_q = int(n_q) if n_q else model.query(1)[1]
-
-    def close(self) -> None:
-        if getattr(self, "_p", None) is not None and self._p.value:
-            try:
-                _lib.lib().nc_encodec_causal_pool_destroy(self._p)
-            finally:
-                self._p = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset_slot(self, slot: int) -> None:
-        _lib.check(_lib.lib().nc_encodec_causal_pool_reset_slot(self._p, int(slot)))
-
-    def pending(self, slot: int) -> int:
-        n = C.c_int64()
-        _lib.check(_lib.lib().nc_encodec_causal_pool_pending(self._p, int(slot), C.byref(n)))
-        return n.value
+    _PREFIX = "causal"
 
     def _entries(self, entries: dict):
         if not entries:
@@ -723,7 +709,7 @@ class EncodecCausalPool:
         slots, data, flush = [], [], []
         rows = self.n_q if self.decode else self.model.config.channels
         for s, v in entries.items():
-            d, f = EncodecStreamPool._split(v)
+            d, f = self._split(v)
             if d is not None:
                 if self.decode and d.ndim == 3 and d.shape[0] == 1:
                     d = d[0]
@@ -735,11 +721,6 @@ class EncodecCausalPool:
             self._torch = _is_torch(some[0])
         return slots, data, flush, [0 if d is None else int(d.shape[1]) for d in data]
 
-    @staticmethod
-    def _c(slots, n_in, flush):
-        n = len(slots)
-        return (C.c_int32 * n)(*slots), _lib.i64_array(n_in), (C.c_int32 * n)(*[int(f) for f in flush])
-
     def query(self, entries: dict) -> dict:
         """{slot: code frames (decode pool: samples per channel) the entry would emit} (nc_encodec_causal_pool_query)"""
         slots, _, flush, n_in = self._entries(entries)
@@ -749,7 +730,7 @@ class EncodecCausalPool:
         n = len(slots)
         c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
         n_out = (C.c_int64 * n)()
-        _lib.check(_lib.lib().nc_encodec_causal_pool_query(self._p, n, c_slots, c_n_in, c_flush, n_out))
+        _lib.check(self._sym("query")(self._p, n, c_slots, c_n_in, c_flush, n_out))
         return [int(x) for x in n_out]
 
     def plan(self, entries: dict):
@@ -758,31 +739,17 @@ class EncodecCausalPool:
         slots, _, flush, n_in = self._entries(entries)
         n = len(slots)
         c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
-        return _causal_rows(lambda rows, cap, nr, nb: _lib.lib().nc_encodec_causal_pool_plan(self._p, n, c_slots, c_n_in, c_flush, rows, cap, nr, nb))
+        return _causal_rows(lambda rows, cap, nr, nb: self._sym("plan")(self._p, n, c_slots, c_n_in, c_flush, rows, cap, nr, nb))
 
     def step(self, entries: dict, return_emb: bool = False):
         slots, data, flush, n_in = self._entries(entries)
         n = len(slots)
         n_out = self._query(slots, flush, n_in)                            # every refusal that needs no device, and the sizes
-        L, m = _lib.lib(), self.model
+        m = self.model
         Cn, D = m.config.channels, m.config.dimension
         nq = self.n_q if self.decode else m.query(1)[1]
         c_slots, c_n_in, c_flush = self._c(slots, n_in, flush)
-        if self._torch:
-            import torch
-            dev = torch.device("cuda", m.device_index)
-            empty = lambda k, dt: torch.empty((max(1, k),), dtype=dt, device=dev)  # noqa: E731
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            f32, i64 = torch.float32, torch.int64
-            cat = lambda parts, dt: torch.cat([p.reshape(-1).to(dt) for p in parts]).contiguous() if parts else empty(0, dt)  # noqa: E731
-            m._bind_torch_stream()
-            fn = L.nc_encodec_causal_pool_step_dev
-        else:
-            empty = lambda k, dt: np.empty((max(1, k),), dt)  # noqa: E731
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-            f32, i64 = np.float32, np.int64
-            cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dt).reshape(-1) for p in parts])) if parts else empty(0, dt)  # noqa: E731
-            fn = L.nc_encodec_causal_pool_step
+        empty, ptr, cat, f32, i64, fn = self._io()
         some = [d for d in data if d is not None]
         if self.decode:
             codes = cat(some, i64)
@@ -799,31 +766,5 @@ class EncodecCausalPool:
         return res, {s: p.reshape(1, D, -1) for s, p in zip(slots, _lib.split_packed(emb, [D * k for k in n_out]))}
 
 
-class EncodecCausalSession:
+class EncodecCausalSession(_EncodecPoolSession):
     """One live causal stream: a causal pool with one slot.  push(x) -> what became final; flush([x]) ends the stream; reset() starts anew."""
-
-    def __init__(self, pool: EncodecCausalPool):
-        self.pool = pool
-
-    def push(self, x, **kw):
-        out = self.pool.step({0: x}, **kw)
-        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
-
-    def flush(self, x=None, **kw):
-        out = self.pool.step({0: FLUSH if x is None else (x, FLUSH)}, **kw)
-        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
-
-    def pending(self) -> int:
-        return self.pool.pending(0)
-
-    def reset(self) -> None:
-        self.pool.reset_slot(0)
-
-    def close(self) -> None:
-        self.pool.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()

@@ -145,6 +145,18 @@ def encodec_lstm_carried(model, x, state=None, decoder=False):
     return y, (h, c)
 
 
+def concat_copy(a, b, dst, desc, device_index=0):
+    """nc_op_concat_copy: for every row (a_off, na, b_off, nb, s0, dst_off, n) of desc, dst[dst_off : dst_off + n] =
+    (a[a_off : a_off + na] ++ b[b_off : b_off + nb] ++ zeros)[s0 : s0 + n], all rows in one launch.  a, b, dst: 1-D float32 or int64 of
+    one dtype; returns a copy of dst with the rows written."""
+    out = np.array(dst, order="C", copy=True)
+    a = np.ascontiguousarray(a, out.dtype); b = np.ascontiguousarray(b, out.dtype)
+    desc = np.ascontiguousarray(desc, np.int64).reshape(-1, 7)
+    _lib.check(_lib.lib().nc_op_concat_copy(device_index, out.dtype.itemsize, a.ctypes.data, a.size, b.ctypes.data, b.size, out.ctypes.data, out.size,
+                                            desc.ctypes.data, desc.shape[0]))
+    return out
+
+
 def fold_weight_norm(v, g):
     v = np.ascontiguousarray(v, np.float32); g = np.ascontiguousarray(g, np.float32).reshape(-1)
     w = np.empty_like(v)
