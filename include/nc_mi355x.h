@@ -1104,6 +1104,61 @@ NC_API nc_status nc_audio_apply_gain_db(int device_index, const float* pcm, int3
 NC_API nc_status nc_audio_apply_gain_db_host(const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, const float* db,
                                              float* out, const int64_t* out_off);
 
+/* ------------------------------------------------------------------------------------ band-limited resampling
+ * Windowed-sinc polyphase resampling of R rows (a row is one channel of one clip) from `src` to `dst` Hz: the resampler of the upstream
+ * DAC pipeline (julius resample_frac, the family of torchaudio's resample), as one fixed bit pattern.  The host twin
+ * (csrc/nc_resample_host.hip: plain serial C++ on HOST pointers, no device) and the kernels (csrc/nc_resample.hip) share the checks, the
+ * geometry and the table builder (csrc/nc_resample.h) and nothing of the per-sample arithmetic; they agree bit for bit.
+ *   ratio   g = gcd(src, dst), U = dst / g, D = src / g.  src == dst: every row is copied.
+ *   config  nc_resample_cfg { zeros, rolloff }; a NULL pointer, zeros == 0 or rolloff == 0 stand for julius' defaults zeros = 24 and
+ *           rolloff = the binary64 0.945, as julius holds it (widened from 0.945f, 24 * 441 / (160 rolloff) of 44100 -> 16000 lands a hair
+ *           above 70 and W would be 71 where julius has 70).  A rolloff that is given is widened from binary32.  Admitted: 1 <= zeros <= 64,
+ *           0.5 <= rolloff <= 1.
+ *   geom    in binary64: base = min(U, D) rolloff;  W = ceil(zeros D / base) (the product first, then the
+ *           quotient);  K = 2 W + D;  K4 = K rounded up to a multiple of 4.                              (nc_audio_resample_sinc_geom)
+ *   table   h[U][K4] in binary64, rounded ONCE to binary32.  For k < K, with pi = 0x1.921fb54442d18p+1:
+ *             t = ((-(double)i) / U + (double)(k - W) / D) base, clamped to [-zeros, zeros];  a = pi t;
+ *             v = (a == 0 ? 1 : sin(a) / a) c c,  c = cos(a / (2 zeros));
+ *           row i is divided by its own sum (k ascending from 0.0), so every phase has unity DC gain; for K <= k < K4 the tap is +0.
+ *           sin and cos are libm's: the builder runs on the host only, the kernels and the twin of one process read the same table, and
+ *           nothing on the data path depends on libm.  Two libm builds may differ in the last binary64 place, which moves a binary32
+ *           rounding only next to a tie: tests hold the table within 1 ulp of binary32 of a binary64 restatement, not bit for bit.
+ *                                                                                                        (nc_audio_resample_sinc_table)
+ *   pad     xpad[j] = x[clamp(j - W, 0, n - 1)]: the edge sample repeated, as julius does; no padded copy is ever stored.
+ *   chain   y[m U + i] = acc after acc = 0.0f; acc = fmaf(h[i][k], xpad[m D + k], acc) for k = 0 .. K4 - 1 ascending, in binary32.  The
+ *           zero taps K .. K4 - 1 are part of the chain (they can turn -0 into +0 and meet a non-finite sample).
+ *           A result that is a NaN is stored as the quiet NaN 0x7fc00000: the sign and payload of the NaN an invalid operation makes
+ *           (0 x inf, inf - inf) differ between hosts and gfx950.
+ *   length  n_out = ceil(n U / D), exact in int64 (nc_audio_resample_sinc_len; -1 on bad arguments).  Row r writes out[out_off[r] + j] for
+ *           j < n_out only; a row of length 0 writes nothing.
+ * off[] / n[] / out_off[] are HOST arrays of ELEMENT offsets and lengths, as in the loudness calls.
+ * NC_EINVAL, before anything is launched: a null pointer; a rate < 1; R outside [1, 32767]; a negative offset; n[r] outside [0, 2^30]; a
+ * config outside the admitted ranges; a table U K4 4 B above 4 MiB (the L2 of one XCD: 32000 -> 44100 passes with 641 KB, 44100 -> 44101
+ * is refused); an output row [out + out_off[r], + n_out) that overlaps an input row [pcm + off[r'], + n[r']) (the lengths differ, so the
+ * call never runs in place); a row whose n_out is above 2^31 - 256 (one launch).
+ * Deviation from the reference: AudioSignal.ResampleFrac is not mirrored, because it does not do what its name says -- each of its two
+ * stages adds 128 samples it never trims (4800 samples at 48 kHz become 4412 at 44.1 kHz, 2464 at 24 kHz); the filter is normalised to
+ * sum 1 AFTER zero-stuffing, which cancels its own gain U (24 kHz -> 48 kHz halves the amplitude); and the half-width is 64 taps in the
+ * UPSAMPLED domain, so for 48 kHz -> 44.1 kHz (U = 147) the 129 taps see at most one non-zero sample (a 0.5 sine comes out at 0.0055).
+ * tests/test_resample_cpu.py restates it and asserts the three findings.
+ *
+ * replaces: AudioSignal.ResampleFrac                            AudioTools/AudioSignal.cs:962-1032
+ *           as _dev (DEVICE buffers, asynchronous on `hip_stream`), plain (HOST buffers: upload, run, download) and _host (no device). */
+typedef struct nc_resample_cfg {
+    int32_t zeros;       /* zero crossings of the sinc on either side; 0 = 24 */
+    float rolloff;       /* cutoff as a fraction of the lower Nyquist; 0 = 0.945 */
+} nc_resample_cfg;
+NC_API int64_t nc_audio_resample_sinc_len(int64_t n_in, int32_t src, int32_t dst);
+NC_API nc_status nc_audio_resample_sinc_geom(int32_t src, int32_t dst, const nc_resample_cfg* cfg, int32_t* U, int32_t* D, int32_t* W, int32_t* K,
+                                             int32_t* K4);
+NC_API nc_status nc_audio_resample_sinc_table(int32_t src, int32_t dst, const nc_resample_cfg* cfg, float* h /* [U][K4] */);
+NC_API nc_status nc_audio_resample_sinc_dev(int device_index, const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t src,
+                                            int32_t dst, const nc_resample_cfg* cfg, float* out, const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_resample_sinc(int device_index, const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t src,
+                                        int32_t dst, const nc_resample_cfg* cfg, float* out, const int64_t* out_off);
+NC_API nc_status nc_audio_resample_sinc_host(const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t src, int32_t dst,
+                                             const nc_resample_cfg* cfg, float* out, const int64_t* out_off);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE

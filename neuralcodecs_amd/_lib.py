@@ -125,6 +125,10 @@ class NcLoudnessRow(C.Structure):
                 ("n_bad", C.c_int32)]
 
 
+class NcResampleCfg(C.Structure):
+    _fields_ = [("zeros", C.c_int32), ("rolloff", C.c_float)]
+
+
 NC_CHUNK_AUTO, NC_CHUNK_OFF = 0, -1
 NC_KWEIGHT_REFERENCE, NC_KWEIGHT_DESIGNED = 0, 1
 NC_WINDOW_HANN, NC_WINDOW_ONES = 0, 1
@@ -311,6 +315,13 @@ SYMBOLS = [
     ("nc_audio_apply_gain_db_dev", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("nc_audio_apply_gain_db", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("nc_audio_apply_gain_db_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("nc_audio_resample_sinc_len", C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ("nc_audio_resample_sinc_geom", C.c_int, [C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nc_audio_resample_sinc_table", C.c_int, [C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P]),
+    ("nc_audio_resample_sinc_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P, _P]),
+    ("nc_audio_resample_sinc", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P]),
+    ("nc_audio_resample_sinc_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),

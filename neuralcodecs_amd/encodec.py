@@ -398,6 +398,12 @@ class Encodec(_lib.ProfileMixin):
         from . import loudness
         return loudness.normalize_ragged(clips, self.config.sampling_rate, target_db, filter, host)
 
+    def resample_ragged(self, clips, sample_rate: int, host: bool = False):
+        """nc_audio_resample_sinc_dev on 1-D clips of any lengths at `sample_rate` (neuralcodecs_amd/resample.py): the clips at the model's
+        sample rate, views of one packed buffer and ready for normalize_ragged / encode_ragged."""
+        from . import resample
+        return resample.resample_ragged(clips, sample_rate, self.config.sampling_rate, host)
+
     def restore_ragged(self, decoded, rows, host: bool = False):
         """nc_audio_apply_gain_db_dev: the decoded clips back at the levels normalize_ragged measured (rows: what it returned)."""
         from . import loudness

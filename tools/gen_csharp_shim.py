@@ -12,8 +12,9 @@ Checked, not generated (hand-written against those stubs and against the referen
   bindings/csharp/SNAC.Native.cs    DAC / SNAC / Encodec classes, signature for signature; NeuralCodecs.Create*NativeAsync factories.
   bindings/csharp/Encodec.Native.cs Every NcMi355x.nc_* call they make must exist in the header with the same number of arguments
   bindings/csharp/NeuralCodecs.Native.cs   (check_templates); tests/test_csharp_shim_cpu.py additionally parses the REFERENCE's .cs files
-  bindings/csharp/Quality.Native.cs        QualityNative / LoudnessNative: static helpers over the round-trip quality and loudness exports,
-  bindings/csharp/Loudness.Native.cs       held to the header's argument counts by check_templates as well.
+  bindings/csharp/Quality.Native.cs        QualityNative / LoudnessNative: static helpers over the round-trip quality, loudness
+  bindings/csharp/Loudness.Native.cs       and resampling exports, held to the header's argument counts by check_templates as well.
+  bindings/csharp/Resample.Native.cs       ResampleNative: the same for the band-limited resampler.
                                     (Config/*Config.cs, Models/*.cs, NeuralCodecs.cs, Core/Exceptions) and holds the classes to them.
 dotnet is not available in the build image, so the files are cross-checked, not compiled.
 """
@@ -222,7 +223,7 @@ def gen_native(enums, structs, funcs, defines):
 # ---- hand-written model classes (bindings/csharp/*.Native.cs): checked here and in tests/test_csharp_shim_cpu.py -------------------------
 MODEL_FILES = ("DAC.Native.cs", "SNAC.Native.cs", "Encodec.Native.cs", "NeuralCodecs.Native.cs")
 # hand-written static helpers over the audio-tool exports: held to the header's argument counts like the model classes
-TOOL_FILES = ("Quality.Native.cs", "Loudness.Native.cs")
+TOOL_FILES = ("Quality.Native.cs", "Loudness.Native.cs", "Resample.Native.cs")
 
 
 def model_sources():
