@@ -718,7 +718,11 @@ NC_API nc_status nc_encodec_causal_pool_step_dev(nc_encodec_causal_pool* p, int3
  * (Modules/Encodec/BitPacker.cs: values LSB-first into a little-endian bit stream, `bits` per value, flushed to a whole byte) in the
  * order EncodecCompressor writes a frame (EncodecCompressor.cs:170-181: t outer, codebook k inner).  One packed row per clip.
  *   codes  [B,K,T] int64 (device)         packed [B, nc_packed_bytes(K*T, bits)] uint8 (device)
- * Used for `.ecdc` payloads without the language model and to shrink the multi-GPU code all-gather 64/bits times. */
+ * Used for `.ecdc` payloads without the language model and to shrink the multi-GPU code all-gather 64/bits times.
+ * Only the low `bits` bits of a code are written: where BitPacker.Push throws ArgumentOutOfRangeException (a negative code, a code of
+ * 1 << bits or more) these calls cannot, so the caller checks the range (the Python mirror does); the neighbours' bits are never
+ * touched.  The pad bits of a row's last byte are written as 0 and ignored when unpacking.  `packed` may have any byte alignment.
+ * 1 <= bits <= 24; B, K, T > 0; NULL pointers and a device index out of range: NC_EINVAL, nothing written. */
 NC_API int64_t nc_packed_bytes(int64_t n_values, int32_t bits);
 NC_API nc_status nc_pack_codes_dev(int device_index, const int64_t* codes, int32_t B, int32_t K, int64_t T, int32_t bits, uint8_t* packed,
                                    void* hip_stream);
@@ -735,12 +739,16 @@ NC_API nc_status nc_unpack_codes(int device_index, const uint8_t* packed, int32_
  *   pcm16_to_float   replaces AudioUtils.AudioBytesToFloatArray (Core/Utils/AudioUtils.cs:13-36): out = int16 * (1/32768f), same
  *                    order; planar != 0 writes channel-major [channels][n_frames] like NAudioUtils.cs:94-104 / Examples/Program.cs:391-401
  *   float_to_pcm16   replaces AudioUtils.FloatArrayToAudioBytes (AudioUtils.cs:172-186) with the clamp of Dia.SaveAudio
- *                    (Models/Dia.cs:918-923): (short)(clamp(x,-1,1) * 32767), truncating
+ *                    (Models/Dia.cs:918-923): (short)(clamp(x,-1,1) * 32767), truncating.  A NaN sample gives 0, as Math.Min / Math.Max
+ *                    keep the NaN and (short)NaN is 0 (never full scale); +-inf gives +-32767, -0.0 gives 0
  *   mix_to_mono      replaces AudioUtils.ConvertToMono (AudioUtils.cs:45-61): interleaved [n_frames][channels] -> [n_frames]
  *   interleave       replaces AudioUtils.DeinterleaveToInterleave (AudioUtils.cs:90-101), any channel count
  *   deinterleave     replaces AudioUtils.InterleaveToDeinterleave (AudioUtils.cs:204-219)
  *   resample_linear  replaces AudioUtils.ResampleLinear (AudioUtils.cs:329-354) == SNAC.ResampleAudio (Models/SNAC.cs:284-308):
- *                    [B][n_in] -> [B][nc_audio_resample_len(n_in, src, dst)], binary64 position arithmetic */
+ *                    [B][n_in] -> [B][nc_audio_resample_len(n_in, src, dst)], binary64 position arithmetic
+ * nc_audio_resample_len is (int)(n_in * ((double)dst / src)) with the product in binary64.  It returns -1 for n_in < 0, a rate <= 0, or
+ * a product of 2^31 or more (the reference's (int) goes negative there and its `new float[n]` throws); nc_audio_resample_linear_dev
+ * refuses those, and a length of 0, with NC_EINVAL before anything is launched. */
 NC_API int64_t nc_audio_resample_len(int64_t n_in, int32_t src_rate, int32_t dst_rate);
 NC_API nc_status nc_audio_pcm16_to_float_dev(int device_index, const int16_t* pcm, int64_t n_frames, int32_t channels, int32_t planar,
                                              float* out, void* hip_stream);

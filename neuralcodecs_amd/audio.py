@@ -29,18 +29,23 @@ def _torch():
     return torch
 
 
-def _run(x, np_dtype, out_shape, out_dtype_np, launch):
-    """x -> contiguous device tensor, allocate the output, launch(dev_index, x_ptr, out_ptr, stream), hand back in x's kind."""
+def _run(x, np_dtype, out_shape, out_dtype_np, launch, zero_fill=False):
+    """x -> contiguous device tensor, allocate the output, launch(dev_index, x_ptr, out_ptr, stream), hand back in x's kind.
+    A torch tensor must already hold np_dtype (its memory is passed as it is); numpy and list input is converted to it.
+    zero_fill: the launch does not write every output element, the rest is +0.0 (the reference's `new float[n]`)."""
     torch = _torch()
     was_torch = _is_torch(x)
     if was_torch:
+        want = {np.float32: torch.float32, np.int16: torch.int16}[np_dtype]
+        if x.dtype != want:
+            raise TypeError(f"expected a {want} tensor, got {x.dtype}")
         xt = x.contiguous()
         if not xt.is_cuda:
             xt = xt.cuda()
     else:
         xt = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np_dtype))).cuda()
     tdt = {np.float32: torch.float32, np.int16: torch.int16}[out_dtype_np]
-    out = torch.empty(out_shape, dtype=tdt, device=xt.device)
+    out = (torch.zeros if zero_fill else torch.empty)(out_shape, dtype=tdt, device=xt.device)
     stream = torch.cuda.current_stream(xt.device).cuda_stream
     _lib.check(launch(xt.device.index or 0, xt.data_ptr(), out.data_ptr(), stream))
     if was_torch:
@@ -76,13 +81,15 @@ def convert_to_mono(x, channels: int):
 def deinterleave_to_interleave(x, channels: int = 2):
     n = int(np.prod(x.shape)) if hasattr(x, "shape") else len(x)
     L = _lib.lib()
-    return _run(x, np.float32, (n,), np.float32, lambda d, xi, xo, s: L.nc_audio_interleave_dev(d, xi, n // channels, channels, xo, s))
+    return _run(x, np.float32, (n,), np.float32, lambda d, xi, xo, s: L.nc_audio_interleave_dev(d, xi, n // channels, channels, xo, s),
+                zero_fill=n % channels != 0)           # the n % channels samples past the last whole frame: +0.0
 
 
 def interleave_to_deinterleave(x, channels: int = 2):
     n = int(np.prod(x.shape)) if hasattr(x, "shape") else len(x)
     L = _lib.lib()
-    return _run(x, np.float32, (n,), np.float32, lambda d, xi, xo, s: L.nc_audio_deinterleave_dev(d, xi, n // channels, channels, xo, s))
+    return _run(x, np.float32, (n,), np.float32, lambda d, xi, xo, s: L.nc_audio_deinterleave_dev(d, xi, n // channels, channels, xo, s),
+                zero_fill=n % channels != 0)
 
 
 def resample_linear(x, src: int, dst: int):
@@ -92,7 +99,9 @@ def resample_linear(x, src: int, dst: int):
     B = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
     L = _lib.lib()
     n_out = L.nc_audio_resample_len(n_in, src, dst)
-    if n_out <= 0:
+    if n_out < 0:
+        raise ValueError("sample rates must be positive and the resampled length below 2^31")
+    if n_out == 0:
         raise ValueError("resampled clip would be empty")
     return _run(x, np.float32, shape[:-1] + (n_out,), np.float32,
                 lambda d, xi, xo, s: L.nc_audio_resample_linear_dev(d, xi, B, n_in, src, dst, xo, s))

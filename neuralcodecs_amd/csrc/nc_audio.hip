@@ -27,7 +27,9 @@ __global__ void pcm16_to_float_kernel(const int16_t* __restrict__ in, int64_t n_
 __global__ void float_to_pcm16_kernel(const float* __restrict__ in, int64_t n, int16_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float c = fmaxf(-1.0f, fminf(1.0f, in[i]));
+    const float x = in[i];
+    // fminf / fmaxf return the other operand for a NaN (that would be full scale); Math.Min / Math.Max keep it and (short)NaN is 0
+    const float c = x != x ? 0.0f : fmaxf(-1.0f, fminf(1.0f, x));
     out[i] = (int16_t)(int)(c * 32767.0f);   // conversion truncates toward zero, like the C# cast
 }
 
@@ -99,7 +101,9 @@ extern "C" {
 int64_t nc_audio_resample_len(int64_t n_in, int32_t src_rate, int32_t dst_rate) {
     if (n_in < 0 || src_rate <= 0 || dst_rate <= 0) return -1;
     const double ratio = (double)dst_rate / (double)src_rate;
-    return (int64_t)(int32_t)((double)n_in * ratio);   // `(int)(input.Length * ratio)`
+    const double len = (double)n_in * ratio;           // `(int)(input.Length * ratio)`
+    if (!(len < 2147483648.0)) return -1;              // the reference's (int) goes negative there and `new float[n]` throws
+    return (int64_t)len;
 }
 
 nc_status nc_audio_pcm16_to_float_dev(int device_index, const int16_t* pcm, int64_t n_frames, int32_t channels, int32_t planar, float* out,
@@ -158,7 +162,8 @@ nc_status nc_audio_resample_linear_dev(int device_index, const float* in, int32_
         if (B <= 0 || n_in <= 0) fail(NC_EINVAL, "B and n_in must be positive");
         if (src_rate <= 0 || dst_rate <= 0) fail(NC_EINVAL, "sample rates must be positive");
         const int64_t n_out = nc_audio_resample_len(n_in, src_rate, dst_rate);
-        if (n_out <= 0) fail(NC_EINVAL, "resampled clip would be empty");
+        if (n_out < 0) fail(NC_EINVAL, "resampled length must be below 2^31");
+        if (n_out == 0) fail(NC_EINVAL, "resampled clip would be empty");
         audio_device(device_index);
         const double ratio = (double)dst_rate / (double)src_rate;
         hipLaunchKernelGGL(resample_linear_kernel, dim3(grid_for((int64_t)B * n_out)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), in, B, n_in,

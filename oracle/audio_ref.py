@@ -42,17 +42,28 @@ def mix_to_mono(x, channels):
 
 
 def interleave(planar, channels=2):
-    p = np.asarray(planar, dtype=np.float32).reshape(channels, -1)
-    return p.T.copy().reshape(-1)
+    """`new float[n]`, then the n // channels whole frames: the n % channels samples behind them stay +0.0 (AudioUtils.cs:92-93)."""
+    x = np.asarray(planar, dtype=np.float32).reshape(-1)
+    f = len(x) // channels
+    out = np.zeros(len(x), np.float32)
+    out[: f * channels] = x[: f * channels].reshape(channels, f).T.reshape(-1)
+    return out
 
 
 def deinterleave(inter, channels=2):
-    p = np.asarray(inter, dtype=np.float32).reshape(-1, channels)
-    return p.T.copy().reshape(-1)
+    x = np.asarray(inter, dtype=np.float32).reshape(-1)
+    f = len(x) // channels
+    out = np.zeros(len(x), np.float32)
+    out[: f * channels] = x[: f * channels].reshape(f, channels).T.reshape(-1)
+    return out
 
 
 def resample_len(n_in, src, dst):
-    return int(n_in * (float(dst) / float(src)))
+    """-1 where the reference's `(int)` leaves int32 (its `new float[n]` then throws) or a rate is not positive."""
+    if n_in < 0 or src <= 0 or dst <= 0:
+        return -1
+    n = float(n_in) * (float(dst) / float(src))
+    return int(n) if n < 2.0 ** 31 else -1
 
 
 def resample_linear(x, src, dst):

@@ -46,3 +46,36 @@ def test_ecdc_header_layout_and_validation():
         containers.ecdc_read_header(io.BytesIO(bad.getvalue()))
     with pytest.raises(IOError):
         containers.ecdc_read_header(io.BytesIO(raw[:20]))
+
+
+# ------------------------------------------------------------- the Python-integer BitPacker that tests/test_containers_gpu.py judges with
+import audio_judge as J  # noqa: E402
+from neuralcodecs_amd import _lib  # noqa: E402
+
+
+def test_reference_bitpacker_known_answer():
+    """bits = 3, values 5 2 7: 101 at bits 0-2, 010 at 3-5, 111 at 6-8 -> 1101 0101, 0000 0001 (LSB first, flushed to a whole byte)."""
+    assert J.ref_bitpack([5, 2, 7], 3) == bytes([0xD5, 0x01])
+    assert J.ref_bitunpack(bytes([0xD5, 0x01]), 3, 3) == [5, 2, 7]
+    assert J.ref_bitunpack(bytes([0xD5, 0xFF]), 3, 3) == [5, 2, 7]               # pad bits are not part of a value
+    codes = J.to_codes(np.arange(6)[None], 2, 3)                                  # stream order: t outer, codebook inner
+    assert codes.tolist() == [[[0, 2, 4], [1, 3, 5]]] and J.to_stream(codes).tolist() == [[0, 1, 2, 3, 4, 5]]
+
+
+def test_pack_shapes_reach_every_tail_and_every_straddle():
+    for bits in range(1, 25):
+        assert J.tail_residues(bits) == J.possible_residues(bits), bits
+        assert 0 in J.tail_residues(bits)                                         # a last value that ends on the row's last byte
+        three = any(J.first_slot_spanning(3, bits, K * T) is not None for K, T in J.PACK_SHAPES)
+        assert three == (bits >= 10 and bits not in (10, 12, 16)), bits           # 10, 12 and 16 start every value on an even bit
+        names = {n for K, T in J.PACK_SHAPES for n, _ in J.pack_patterns(bits, K, T, 1)}
+        assert {"random", "ones", "alternating", "single-first", "single-last"} <= names
+        assert ("single-two-bytes" in names) == (bits not in (1, 2, 4, 8) and bits < 17)     # from 17 bits on every value touches three
+    assert max(K * T for K, T in J.PACK_SHAPES) <= 2000
+
+
+def test_packed_bytes_is_the_ceiling():
+    f = _lib.lib().nc_packed_bytes
+    for n in (0, 1, 2, 7, 8, 9, 783, 2 ** 31 - 1, 2 ** 31, 2 ** 40 - 1, 2 ** 40):
+        for bits in range(1, 25):
+            assert f(n, bits) == -(-n * bits // 8), (n, bits)
