@@ -54,13 +54,6 @@ void encodec_host_call(EncodecModel& m, Stage&& stage, Run&& run) {
 }
 
 // ---- helpers of the op-level test hooks ----
-void op_set_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
-
 // The hooks build throw-away layers and buffers: all of them are DevBufs (or made of DevBufs) and go back to the device when the hook
 // returns or throws.
 float* op_upload(DevBuf& d, const float* h, size_t n) {
@@ -585,7 +578,7 @@ nc_status nc_op_conv1d(int device_index, const nc_conv_desc* d, const float* x, 
     return guard([&] {
         if (!d || !x || !weight || !y) fail(NC_EINVAL, "null argument");
         if (d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->K <= 0 || d->stride <= 0 || d->Tin <= 0) fail(NC_EINVAL, "bad conv shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         ConvLayer L;
         L.build(weight, bias, d->Cin, d->Cout, d->K, d->stride, d->pad, d->dil, d->out_pad, d->transposed != 0);
         const int64_t Tout = L.out_len(d->Tin);
@@ -611,7 +604,7 @@ nc_status nc_op_conv1d_bench(int device_index, const nc_conv_desc* d, int32_t fu
     return guard([&] {
         if (!d || !avg_ms || iters <= 0) fail(NC_EINVAL, "null argument");
         if (d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->K <= 0 || d->stride <= 0 || d->Tin <= 0) fail(NC_EINVAL, "bad conv shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         uint64_t st = 0x9E3779B97F4A7C15ull;
         auto rnd = [&]() {  // uniform [-1,1)
             st = st * 6364136223846793005ull + 1442695040888963407ull;
@@ -669,7 +662,7 @@ nc_status nc_op_res_unit(int device_index, int32_t B, int32_t C, int64_t T, int3
     return guard([&] {
         if (!x || !w7 || !b7 || !a1 || !a2 || !w1 || !b1 || !y) fail(NC_EINVAL, "null argument");
         if (B <= 0 || C <= 0 || T <= 0 || dil <= 0 || iters < 0 || (iters > 0 && !avg_ms)) fail(NC_EINVAL, "bad arguments");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         ConvLayer c7, c1;
         c7.build(w7, b7, C, C, 7, 1, 3 * dil, dil, 0, false);
         c1.build(w1, b1, C, C, 1, 1, 0, 1, 0, false);
@@ -702,7 +695,7 @@ nc_status nc_op_vq_argmin(int device_index, const float* z_e, int32_t B, int32_t
                           int64_t* idx, float* st) {
     return guard([&] {
         if (!z_e || !codebook || !idx || !st || B <= 0 || D <= 0 || T <= 0 || N <= 0) fail(NC_EINVAL, "bad arguments");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         Codebook cb;
         cb.build(codebook, N, D);
         DevBuf dz, di, ds;
@@ -720,7 +713,7 @@ nc_status nc_op_euclid_rvq(int device_index, const float* residual, int32_t B, i
                            int32_t form, int64_t* codes, float* residual_out) {
     return guard([&] {
         if (!residual || !codebooks || !codes || B <= 0 || D <= 0 || T <= 0 || N <= 0 || n_q <= 0 || form < 0 || form > 1) fail(NC_EINVAL, "bad arguments");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         op_euclid_rvq(residual, B, D, T, codebooks, n_q, N, form, codes, residual_out);
     });
 }
@@ -735,7 +728,7 @@ nc_status nc_op_dac_rvq(int device_index, const float* residual, int32_t B, int3
             fail(NC_EINVAL, "bad arguments");
         if (form == 1 && !dac_rvq_fused_admits(n_q, L, D, N))   // before anything is built or launched
             fail(NC_EUNSUPPORTED, "no one-launch DAC quantizer for latent %d, codebook %d x %d", L, N, D);
-        op_set_device(device_index);
+        use_checked_device(device_index);
         DacRvq rvq;
         for (int i = 0; i < n_q; ++i)
             rvq.add_stage(w_in + (size_t)i * D * L, b_in ? b_in + (size_t)i * D : nullptr, w_out + (size_t)i * L * D,
@@ -760,7 +753,7 @@ nc_status nc_op_rvq_update(int device_index, const float* q, float* zq, float* r
     return guard([&] {
         if (!q || !zq) fail(NC_EINVAL, "null argument");
         if (rows <= 0 || T <= 0 || s <= 0 || T % s != 0 || rows > ((int64_t)1 << 31) / T) fail(NC_EINVAL, "bad update shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         const size_t n = (size_t)rows * T;
         DevBuf dq, dz, dr;
         op_upload(dq, q, n / s); op_upload(dz, zq, n);
@@ -779,7 +772,7 @@ nc_status nc_op_vq_gather(int device_index, const float* codebook, int32_t N, in
         if (N <= 0 || D <= 0 || B <= 0 || T <= 0 || T > ((int64_t)1 << 30) || codes_offset < 0 || codes_bstride < T || out_guard < 0 ||
             codes_bstride > ((int64_t)1 << 31) / B || (int64_t)B * D > ((int64_t)1 << 31) / T)
             fail(NC_EINVAL, "bad gather shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         Codebook cb;
         cb.build(codebook, N, D);
         const size_t n_codes = (size_t)codes_offset + (size_t)(B - 1) * codes_bstride + T;   // the words the B rows of T codes span
@@ -828,7 +821,7 @@ nc_status nc_op_dwconv1d(int device_index, int32_t B, int32_t C, int64_t T, int3
     return guard([&] {
         if (!x || !w || !y) fail(NC_EINVAL, "null argument");
         if (B <= 0 || C <= 0 || T <= 0 || T > ((int64_t)1 << 30) || K <= 0 || pad < 0 || dil <= 0) fail(NC_EINVAL, "bad depthwise shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         DwConvLayer L;
         L.build(w, bias, C, K, pad, dil);
         DevBuf dx, dy, dai, dao;
@@ -848,7 +841,7 @@ nc_status nc_op_layer_norm(int device_index, int32_t B, int32_t C, int64_t T, co
     return guard([&] {
         if (!x || !gamma || !beta || !y) fail(NC_EINVAL, "null argument");
         if (B <= 0 || C <= 0 || T <= 0) fail(NC_EINVAL, "bad LayerNorm shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         DevBuf dx, dy, dg, db;
         const size_t n = (size_t)B * C * T;
         op_upload(dx, x, n); op_upload(dg, gamma, C); op_upload(db, beta, C);
@@ -865,7 +858,7 @@ nc_status nc_op_local_attn(int device_index, int32_t B, int32_t C, int64_t T, in
         if (!qkv || !inv_freq || !y) fail(NC_EINVAL, "null argument");
         if (B <= 0 || C <= 0 || T <= 0) fail(NC_EINVAL, "bad attention shape");
         if (W <= 0 || W > 32 || T % W != 0 || C % 64 != 0) fail(NC_EUNSUPPORTED, "local attention: window %d / dim %d / %lld steps not supported", W, C, (long long)T);
-        op_set_device(device_index);
+        use_checked_device(device_index);
         std::vector<float> cs, sn;
         rotary_tables(inv_freq, W, cs, sn);
         DevBuf dq, dy, dc, ds;
@@ -883,7 +876,7 @@ nc_status nc_op_avg_pool(int device_index, int64_t rows, int64_t T, int32_t s, c
     return guard([&] {
         if (!x || !y) fail(NC_EINVAL, "null argument");
         if (rows <= 0 || T <= 0 || s <= 0 || T / s <= 0) fail(NC_EINVAL, "bad pooling shape");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         DevBuf dx, dy;
         const size_t ny = (size_t)rows * (size_t)(T / s);
         op_upload(dx, x, (size_t)rows * T);
@@ -901,7 +894,7 @@ nc_status nc_op_snac_unit(int device_index, int32_t B, int32_t C, int64_t T, int
     return guard([&] {
         if (!x || !w7 || !a1 || !a2 || !w1 || !y) fail(NC_EINVAL, "null argument");
         if (B <= 0 || C <= 0 || T <= 0 || T > ((int64_t)1 << 30) || dil <= 0) fail(NC_EINVAL, "bad arguments");
-        op_set_device(device_index);
+        use_checked_device(device_index);
         DevBuf dx, dh, dy, d1, d2, dn;
         const size_t n = (size_t)B * C * T;
         op_upload(dx, x, n);

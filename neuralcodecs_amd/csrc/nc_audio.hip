@@ -71,12 +71,6 @@ __global__ void resample_linear_kernel(const float* __restrict__ in, int B, int6
     out[i] = y;
 }
 
-static void audio_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
 static unsigned grid_for(int64_t n) {
     if (n > (int64_t)0x7fffffff * 256) fail(NC_EINVAL, "too many samples for one launch");
     return (unsigned)((n + 255) / 256);
@@ -111,7 +105,7 @@ nc_status nc_audio_pcm16_to_float_dev(int device_index, const int16_t* pcm, int6
     NC_AUDIO_GUARD({
         if (!pcm || !out) fail(NC_EINVAL, "null pointer");
         if (n_frames <= 0 || channels <= 0) fail(NC_EINVAL, "n_frames and channels must be positive");
-        audio_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(pcm16_to_float_kernel, dim3(grid_for(n_frames * channels)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), pcm,
                            n_frames, channels, planar, out);
     })
@@ -121,7 +115,7 @@ nc_status nc_audio_float_to_pcm16_dev(int device_index, const float* in, int64_t
     NC_AUDIO_GUARD({
         if (!in || !out) fail(NC_EINVAL, "null pointer");
         if (n <= 0) fail(NC_EINVAL, "n must be positive");
-        audio_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(float_to_pcm16_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), in, n, out);
     })
 }
@@ -130,7 +124,7 @@ nc_status nc_audio_mix_to_mono_dev(int device_index, const float* in, int64_t n_
     NC_AUDIO_GUARD({
         if (!in || !out) fail(NC_EINVAL, "null pointer");
         if (n_frames <= 0 || channels <= 0) fail(NC_EINVAL, "n_frames and channels must be positive");
-        audio_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(mix_to_mono_kernel, dim3(grid_for(n_frames)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), in, n_frames, channels, out);
     })
 }
@@ -139,7 +133,7 @@ nc_status nc_audio_interleave_dev(int device_index, const float* planar, int64_t
     NC_AUDIO_GUARD({
         if (!planar || !out) fail(NC_EINVAL, "null pointer");
         if (n_frames <= 0 || channels <= 0) fail(NC_EINVAL, "n_frames and channels must be positive");
-        audio_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(interleave_kernel, dim3(grid_for(n_frames * channels)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), planar, n_frames,
                            channels, out);
     })
@@ -149,7 +143,7 @@ nc_status nc_audio_deinterleave_dev(int device_index, const float* interleaved, 
     NC_AUDIO_GUARD({
         if (!interleaved || !out) fail(NC_EINVAL, "null pointer");
         if (n_frames <= 0 || channels <= 0) fail(NC_EINVAL, "n_frames and channels must be positive");
-        audio_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(deinterleave_kernel, dim3(grid_for(n_frames * channels)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), interleaved,
                            n_frames, channels, out);
     })
@@ -164,7 +158,7 @@ nc_status nc_audio_resample_linear_dev(int device_index, const float* in, int32_
         const int64_t n_out = nc_audio_resample_len(n_in, src_rate, dst_rate);
         if (n_out < 0) fail(NC_EINVAL, "resampled length must be below 2^31");
         if (n_out == 0) fail(NC_EINVAL, "resampled clip would be empty");
-        audio_device(device_index);
+        use_checked_device(device_index);
         const double ratio = (double)dst_rate / (double)src_rate;
         hipLaunchKernelGGL(resample_linear_kernel, dim3(grid_for((int64_t)B * n_out)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), in, B, n_in,
                            ratio, n_out, out);

@@ -39,6 +39,10 @@ struct Error : std::runtime_error {
 
 void set_last_error(const char* msg);
 
+// The checked device switch of every entry point that takes a device index instead of a handle: NC_EDEVICE without a device, NC_EINVAL
+// for an index out of range, then hipSetDevice.
+void use_checked_device(int device_index);
+
 // Diagnostic switches (environment): ONE table in nc_util.hip holds every name the engine reads, its kind and what it
 // switches.  The accessors fail on a name the table does not hold, so a switch cannot exist without its row; nc_debug_switches()
 // (C ABI) lists the table, which is what tools/probe/envmatrix.sh enumerates and tests/test_abi_cpu.py holds DESIGN.md to.

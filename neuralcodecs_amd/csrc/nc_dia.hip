@@ -364,13 +364,6 @@ unsigned grid_for(int64_t n) {   // as nc_audio.hip
     return (unsigned)((n + 255) / 256);
 }
 
-void set_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
-
 // the delay pattern as a kernel argument; returns max(delay)
 int64_t check_delay(int C, const int32_t* delay, DiaDelay& dl) {
     if (!delay) fail(NC_EINVAL, "delay must not be null");
@@ -750,7 +743,7 @@ nc_status nc_dia_apply_delay_dev(int device_index, const int64_t* codes, int32_t
         if (T > (int64_t)1 << 40) fail(NC_EINVAL, "T too large");
         const int64_t n = (int64_t)B * T * C;
         const unsigned grid = grid_for(n);
-        set_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(dia_apply_delay_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(hip_stream), codes, n, T, C, dl, bos, out);
         NC_HIP(hipGetLastError());
     });
@@ -767,7 +760,7 @@ nc_status nc_dia_revert_delay_dev(int device_index, const int64_t* codes, int32_
         if (T > (int64_t)1 << 40) fail(NC_EINVAL, "T too large");
         const int64_t Tout = T - maxd, n = (int64_t)B * Tout * C;
         const unsigned grid = grid_for(n);
-        set_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(dia_revert_delay_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(hip_stream), codes, n, T, Tout, C, dl, min_valid,
                            max_valid, out);
         NC_HIP(hipGetLastError());
@@ -787,7 +780,7 @@ nc_status nc_dia_revert_pack_dev(int device_index, const int64_t* codes, int32_t
             if (lengths[b] <= 0 || lengths[b] > T - maxd)
                 fail(NC_EINVAL, "item %d: length %lld is not in [1, T - max(delay) = %lld]", b, (long long)lengths[b], (long long)(T - maxd));
         check_pack_grids(B, lengths);
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_revert_pack(codes, B, T, C, dl, lengths, min_valid, max_valid, out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
     });
 }
@@ -806,7 +799,7 @@ nc_status nc_dia_adjust_speed_dev(int device_index, const float* pcm_packed, int
             if (T[(size_t)b] != lens[b] && lens[b] < 2) fail(NC_EINVAL, "row %d: one sample cannot be interpolated", b);
         }
         check_speed_grids(B, T.data());
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_adjust_speed(pcm_packed, B, lens, T.data(), out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
     });
 }
@@ -870,7 +863,7 @@ nc_status nc_dia_prefill_pack_dev(int device_index, const int64_t* codes_packed,
         (void)as_i32(pad, "pad");   // PrepareAudioPrompt's padValue: taken and never written
         if (T_max < maxF + maxd) fail(NC_EINVAL, "T_max = %lld is below max(frames) + max(delay) = %lld", (long long)T_max, (long long)(maxF + maxd));
         check_prefill_grid(B, T_max, C);
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_prefill(codes_packed, B, frames, C, dl, bos32, T_max, out, static_cast<hipStream_t>(hip_stream), nullptr);
     });
 }
@@ -885,7 +878,7 @@ nc_status nc_audio_mix_to_mono_ragged_dev(int device_index, const float* in_pack
             if (channels[b] <= 0) fail(NC_EINVAL, "prompt %d has %d channels", b, channels[b]);
         }
         check_mix_grids(B, n_frames);
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_mix(in_packed, B, n_frames, channels, out_packed, static_cast<hipStream_t>(hip_stream), nullptr);
     });
 }
@@ -896,7 +889,7 @@ nc_status nc_dia_sample_dev(int device_index, const float* logits, int32_t B, in
     return guard([&] {
         if (!logits || !uniform || !tokens || !bad) fail(NC_EINVAL, "null pointer");
         check_sample(B, C, V, params);
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_sample(logits, B, C, V, *params, uniform, DiaDelay{}, DiaStepArgs{}, tokens, bad, static_cast<hipStream_t>(hip_stream));
     });
 }
@@ -905,7 +898,7 @@ nc_status nc_dia_generate_state_init_dev(int device_index, int32_t B, int64_t* s
     return guard([&] {
         if (!state) fail(NC_EINVAL, "null pointer");
         if (B <= 0) fail(NC_EINVAL, "B must be positive");
-        set_device(device_index);
+        use_checked_device(device_index);
         hipLaunchKernelGGL(dia_state_init_kernel, dim3(grid_for(3 * (int64_t)B)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), state, B);
         NC_HIP(hipGetLastError());
     });
@@ -929,7 +922,7 @@ nc_status nc_dia_generate_step_dev(int device_index, const float* logits, int32_
         st.state = state;
         st.generated = generated;
         st.active_out = active_out;
-        set_device(device_index);
+        use_checked_device(device_index);
         launch_sample(logits, B, C, V, *params, uniform, dl, st, nullptr, bad, static_cast<hipStream_t>(hip_stream));
     });
 }
@@ -967,7 +960,7 @@ nc_status nc_dia_generate_collect_dev(int device_index, const int32_t* generated
         const int64_t T_gen = longest + maxd;
         if (T_gen <= 0) fail(NC_EINVAL, "nothing was generated (T_gen = 0)");
         const unsigned grid = grid_for(T_gen * C);
-        set_device(device_index);
+        use_checked_device(device_index);
         for (int b0 = 0; b0 < B; b0 += kDiaItems) {
             const int n = std::min(kDiaItems, B - b0);
             DiaCollectItems it{};

@@ -13,9 +13,7 @@
 // kweight_out_kernel: y = fl(u + Gs[r] . s_q), one thread per sample (in place over u for the loudness calls).
 // loud_*_kernel: sub-block sums, cell sums, block sums and the per-clip finish, each in the stated order; no floating-point atomics (the
 // count of non-finite samples is an integer atomic).
-#include <map>
-#include <mutex>
-
+#include "nc_devcall.h"
 #include "nc_frag.h"
 #include "nc_guard.h"
 #include "nc_loudness.h"
@@ -37,8 +35,6 @@ struct KwRow {
     int64_t w0;         // first W_j of the clip
     int32_t clip, pad;
 };
-
-__device__ __forceinline__ int finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ __launch_bounds__(256) void kweight_mfma_kernel(const KwRow* __restrict__ rows, const float* __restrict__ T, float* __restrict__ U,
                                                            float* __restrict__ V, unsigned long long* __restrict__ bad) {
@@ -257,85 +253,35 @@ __global__ __launch_bounds__(256) void gain_kernel(const KwRow* __restrict__ row
     }
 }
 
-// ---- per-device state: the cached tables, one workspace, the pinned image of a call's row table -----------------------------------------
+// ---- per-device state: the cached tables and one workspace beside the call scaffold (nc_devcall.h) --------------------------------------
 struct KwDev {
     DevBuf T, Gs, M;
 };
+bool filled(const KwDev& d) { return d.T.p != nullptr; }
 
 struct LoudDev {
+    DevCall call;
     std::map<std::pair<int, int>, KwDev> tabs;   // (rate or 0, filter)
-    DevBuf U, V, Sq, part, cells, z, W, bad, tables, in, out, out_rows, gains;
-    void* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t copied = nullptr, done = nullptr;
-    bool copied_used = false, done_used = false;
+    DevBuf U, V, Sq, part, cells, z, W, bad, in, out, out_rows;
 };
 
-std::mutex g_mu;
-// never destroyed: the buffers must not be freed behind the runtime's own teardown at process exit
-std::map<int, LoudDev>& g_dev = *new std::map<int, LoudDev>();
-
-void loudness_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
+PerDevice<LoudDev> g_loud;
 
 const KwDev& tables_on(LoudDev& q, int sample_rate, int filter) {
-    KwDev& d = q.tabs[{filter == NC_KWEIGHT_REFERENCE ? 0 : sample_rate, filter}];
-    if (d.T.p) return d;
-    KwTables t;
-    build_kweight_tables(sample_rate, filter, t);
-    std::vector<float> T((size_t)kTableRows * kKwBlock, 0.0f);
-    for (int row = 0; row < kKwBlock + 4; ++row)
-        for (int k = 0; k < kKwBlock; ++k)
-            T[(size_t)row * kKwBlock + (size_t)(k & 3) * 16 + (size_t)(k >> 2)] = row < kKwBlock ? t.Hm[(size_t)row * kKwBlock + k] : t.Cm[(size_t)(row - kKwBlock) * kKwBlock + k];
-    d.Gs.reserve(sizeof(t.Gs));
-    d.M.reserve(sizeof(t.M));
-    NC_HIP(hipMemcpy(d.Gs.p, t.Gs, sizeof(t.Gs), hipMemcpyHostToDevice));
-    NC_HIP(hipMemcpy(d.M.p, t.M, sizeof(t.M), hipMemcpyHostToDevice));
-    d.T.reserve(T.size() * sizeof(float));
-    NC_HIP(hipMemcpy(d.T.p, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
-    return d;
+    return cached_table(q.tabs[{filter == NC_KWEIGHT_REFERENCE ? 0 : sample_rate, filter}], [&](KwDev& d) {
+        KwTables t;
+        build_kweight_tables(sample_rate, filter, t);
+        std::vector<float> T((size_t)kTableRows * kKwBlock, 0.0f);
+        for (int row = 0; row < kKwBlock + 4; ++row)
+            for (int k = 0; k < kKwBlock; ++k)
+                T[(size_t)row * kKwBlock + (size_t)(k & 3) * 16 + (size_t)(k >> 2)] = row < kKwBlock ? t.Hm[(size_t)row * kKwBlock + k] : t.Cm[(size_t)(row - kKwBlock) * kKwBlock + k];
+        fill_table(d.Gs, &t.Gs[0][0], sizeof(t.Gs) / sizeof(double));
+        fill_table(d.M, &t.M[0][0], sizeof(t.M) / sizeof(double));
+        fill_table(d.T, T.data(), T.size());
+    });
 }
 
-// The workspace is one per device: a call on another stream first waits for the call before it.
-void begin_call(LoudDev& q, hipStream_t s) {
-    if (!q.copied) NC_HIP(hipEventCreateWithFlags(&q.copied, hipEventDisableTiming));
-    if (!q.done) NC_HIP(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    if (q.done_used) NC_HIP(hipStreamWaitEvent(s, q.done, 0));
-}
-void end_call(LoudDev& q, hipStream_t s) {
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipEventRecord(q.done, s));
-    q.done_used = true;
-}
-
-// the row table of a call: written into pinned memory, copied once
-void* upload_tables(LoudDev& q, const void* src, size_t bytes, hipStream_t s) {
-    if (q.copied_used) NC_HIP(hipEventSynchronize(q.copied));   // the previous call's copy has read the pinned image
-    if (bytes > q.pin_cap) {
-        if (q.pin) (void)hipHostFree(q.pin);
-        q.pin = nullptr;
-        q.pin_cap = 0;
-        const size_t want = (bytes + 4095) & ~size_t(4095);
-        NC_HIP(hipHostMalloc(&q.pin, want, hipHostMallocDefault));
-        q.pin_cap = want;
-    }
-    memcpy(q.pin, src, bytes);
-    q.tables.reserve(bytes);
-    NC_HIP(hipMemcpyAsync(q.tables.p, q.pin, bytes, hipMemcpyHostToDevice, s));
-    NC_HIP(hipEventRecord(q.copied, s));
-    q.copied_used = true;
-    return q.tables.p;
-}
-
-unsigned grid_of(int64_t items, int per_block) {
-    const int64_t g = (items + per_block - 1) / per_block;
-    if (g > 0x7fffffff) fail(NC_EINVAL, "a row is too long for one launch");
-    return (unsigned)(g > 0 ? g : 1);
-}
+unsigned grid_of(int64_t items, int per_block) { return nc::grid_of(items, per_block, 0x7fffffff); }
 
 // GEMM, scan and output of the rows d_rows[0..R) (their y set); the workspace U / V / Sq is reserved by the caller
 void launch_filter(LoudDev& q, const KwDev& kd, const KwRow* d_rows, int R, int64_t max_n, unsigned long long* bad, hipStream_t s) {
@@ -362,12 +308,12 @@ void run_kweight(LoudDev& q, const float* pcm, int R, const int64_t* off, const 
         cols += (n[r] + kKwBlock - 1) / kKwBlock;
         max_n = n[r] > max_n ? n[r] : max_n;
     }
-    begin_call(q, s);
+    q.call.begin(s);
     reserve_filter(q, cols);
     const KwDev& kd = tables_on(q, sample_rate, filter);
-    const KwRow* d_rows = static_cast<const KwRow*>(upload_tables(q, rows.data(), rows.size() * sizeof(KwRow), s));
+    const KwRow* d_rows = q.call.upload(rows, s);
     launch_filter(q, kd, d_rows, R, max_n, nullptr, s);
-    end_call(q, s);
+    q.call.end(s);
 }
 
 // measure B clips into out_rows (device); with `out`, also write the levelled clips
@@ -397,7 +343,7 @@ void run_loudness(LoudDev& q, const float* pcm, int B, int C, const int64_t* off
         max_n = n[b] > max_n ? n[b] : max_n;
         max_J = J > max_J ? J : max_J;
     }
-    begin_call(q, s);
+    q.call.begin(s);
     reserve_filter(q, cols);
     q.part.reserve((size_t)n_part * sizeof(double));
     q.cells.reserve((size_t)n_cell * sizeof(double));
@@ -406,7 +352,7 @@ void run_loudness(LoudDev& q, const float* pcm, int B, int C, const int64_t* off
     q.bad.reserve((size_t)B * sizeof(unsigned long long));
     for (int r = 0; r < R; ++r) rows[(size_t)r].y = q.U.as<float>() + rows[(size_t)r].col0 * kKwBlock;   // y takes the place of u
     const KwDev& kd = tables_on(q, sample_rate, c.filter);
-    const KwRow* d_rows = static_cast<const KwRow*>(upload_tables(q, rows.data(), rows.size() * sizeof(KwRow), s));
+    const KwRow* d_rows = q.call.upload(rows, s);
     NC_HIP(hipMemsetAsync(q.bad.p, 0, (size_t)B * sizeof(unsigned long long), s));
     launch_filter(q, kd, d_rows, R, max_n, q.bad.as<unsigned long long>(), s);
     if (max_J > 0) {
@@ -419,7 +365,7 @@ void run_loudness(LoudDev& q, const float* pcm, int B, int C, const int64_t* off
     if (out && max_n > 0)
         hipLaunchKernelGGL(gain_kernel, dim3(grid_of(max_n, 1024), (unsigned)R), dim3(256), 0, s, d_rows + R, &out_rows[0].gain,
                            (int)(sizeof(nc_loudness_row) / sizeof(float)));
-    end_call(q, s);
+    q.call.end(s);
 }
 
 void run_gain(LoudDev& q, const float* pcm, int B, int C, const int64_t* off, const int64_t* n, const float* db, float* out, const int64_t* out_off,
@@ -439,40 +385,40 @@ void run_gain(LoudDev& q, const float* pcm, int B, int C, const int64_t* off, co
         }
         max_n = n[b] > max_n ? n[b] : max_n;
     }
-    begin_call(q, s);
-    unsigned char* dev = static_cast<unsigned char*>(upload_tables(q, img.data(), bytes, s));
+    q.call.begin(s);
+    unsigned char* dev = static_cast<unsigned char*>(q.call.upload(img.data(), bytes, s));
     if (max_n > 0)
         hipLaunchKernelGGL(gain_kernel, dim3(grid_of(max_n, 1024), (unsigned)R), dim3(256), 0, s, reinterpret_cast<const KwRow*>(dev),
                            reinterpret_cast<const float*>(dev + o_gain), 1);
-    end_call(q, s);
+    q.call.end(s);
 }
 
 void check_db(const float* db, int B) {
     if (!db) fail(NC_EINVAL, "null pointer");
     for (int b = 0; b < B; ++b)
-        if ((__builtin_bit_cast(uint32_t, db[b]) & 0x7f800000u) == 0x7f800000u) fail(NC_EINVAL, "db[%d] is not finite", b);
+        if (!finite32(db[b])) fail(NC_EINVAL, "db[%d] is not finite", b);
 }
 
-// HOST rows -> the device staging buffer, every row at a multiple of four elements
-std::vector<int64_t> stage_in(LoudDev& q, const float* pcm, int R, const int64_t* off, const int64_t* n, int rows_per_n, int64_t* total_out) {
-    std::vector<int64_t> packed((size_t)R);
-    int64_t total = 0;
-    for (int r = 0; r < R; ++r) {
-        packed[(size_t)r] = total;
-        total += (n[r / rows_per_n] + 3) & ~(int64_t)3;
-    }
-    q.in.reserve((size_t)(total > 0 ? total : 1) * sizeof(float));
-    for (int r = 0; r < R; ++r)
-        if (n[r / rows_per_n] > 0)
-            NC_HIP(hipMemcpy(q.in.as<float>() + packed[(size_t)r], pcm + off[r], (size_t)n[r / rows_per_n] * sizeof(float), hipMemcpyHostToDevice));
-    *total_out = total;
-    return packed;
-}
+constexpr int64_t kStageAlign = 4;   // HOST rows lie at multiples of four elements in the staging buffers: the gain kernel's 16-byte path
 
-void stage_out(LoudDev& q, const std::vector<int64_t>& packed, int R, const int64_t* n, int rows_per_n, float* out, const int64_t* out_off) {
-    for (int r = 0; r < R; ++r)
-        if (n[r / rows_per_n] > 0)
-            NC_HIP(hipMemcpy(out + out_off[r], q.out.as<float>() + packed[(size_t)r], (size_t)n[r / rows_per_n] * sizeof(float), hipMemcpyDeviceToHost));
+// the plain calls: HOST buffers through the staging buffers, synchronous.  measure: loudness / normalize; db: apply_gain_db
+void host_buffer_call(int device_index, const float* pcm, int B, int C, const int64_t* off, const int64_t* n, int sample_rate, const nc_loudness_cfg* c,
+                      const float* db, float* out, const int64_t* out_off, nc_loudness_row* rows) {
+    g_loud.locked(device_index, [&](LoudDev& q) {
+        const PackedRows packed(B * C, n, C, kStageAlign);
+        packed.copy_in(q.in, pcm, off);
+        if (out) packed.reserve(q.out);
+        if (c) {
+            q.out_rows.reserve((size_t)B * sizeof(nc_loudness_row));
+            run_loudness(q, q.in.as<float>(), B, C, packed.at.data(), n, sample_rate, *c, out ? q.out.as<float>() : nullptr, out ? packed.at.data() : nullptr,
+                         q.out_rows.as<nc_loudness_row>(), nullptr);
+        } else {
+            run_gain(q, q.in.as<float>(), B, C, packed.at.data(), n, db, q.out.as<float>(), packed.at.data(), nullptr);
+        }
+        NC_HIP(hipStreamSynchronize(nullptr));
+        if (c) NC_HIP(hipMemcpy(rows, q.out_rows.p, (size_t)B * sizeof(nc_loudness_row), hipMemcpyDeviceToHost));
+        if (out) packed.copy_out(q.out, out, out_off);
+    });
 }
 
 }  // namespace
@@ -488,9 +434,7 @@ extern "C" nc_status nc_audio_kweight_dev(int device_index, const float* pcm, in
         loudness_check_filter(sample_rate, filter);
         const int64_t* offs[2] = {off, out_off};
         loudness_check_rows(R, offs, 2, 1, n);
-        loudness_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_kweight(g_dev[device_index], pcm, R, off, n, sample_rate, filter, out, out_off, static_cast<hipStream_t>(hip_stream));
+        g_loud.locked(device_index, [&](LoudDev& q) { run_kweight(q, pcm, R, off, n, sample_rate, filter, out, out_off, static_cast<hipStream_t>(hip_stream)); });
     });
 }
 
@@ -501,15 +445,14 @@ extern "C" nc_status nc_audio_kweight(int device_index, const float* pcm, int32_
         loudness_check_filter(sample_rate, filter);
         const int64_t* offs[2] = {off, out_off};
         loudness_check_rows(R, offs, 2, 1, n);
-        loudness_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        LoudDev& q = g_dev[device_index];
-        int64_t total = 0;
-        const std::vector<int64_t> packed = stage_in(q, pcm, R, off, n, 1, &total);
-        q.out.reserve((size_t)(total > 0 ? total : 1) * sizeof(float));
-        run_kweight(q, q.in.as<float>(), R, packed.data(), n, sample_rate, filter, q.out.as<float>(), packed.data(), nullptr);
-        NC_HIP(hipStreamSynchronize(nullptr));
-        stage_out(q, packed, R, n, 1, out, out_off);
+        g_loud.locked(device_index, [&](LoudDev& q) {
+            const PackedRows packed(R, n, 1, kStageAlign);
+            packed.copy_in(q.in, pcm, off);
+            packed.reserve(q.out);
+            run_kweight(q, q.in.as<float>(), R, packed.at.data(), n, sample_rate, filter, q.out.as<float>(), packed.at.data(), nullptr);
+            NC_HIP(hipStreamSynchronize(nullptr));
+            packed.copy_out(q.out, out, out_off);
+        });
     });
 }
 
@@ -520,9 +463,9 @@ extern "C" nc_status nc_loudness_dev(int device_index, const float* pcm, int32_t
         const nc_loudness_cfg c = loudness_resolve_cfg(cfg, sample_rate);
         const int64_t* offs[1] = {off};
         loudness_check_clips(B, C, offs, 1, n);
-        loudness_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_loudness(g_dev[device_index], pcm, B, C, off, n, sample_rate, c, nullptr, nullptr, out, static_cast<hipStream_t>(hip_stream));
+        g_loud.locked(device_index, [&](LoudDev& q) {
+            run_loudness(q, pcm, B, C, off, n, sample_rate, c, nullptr, nullptr, out, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -534,9 +477,9 @@ extern "C" nc_status nc_loudness_normalize_dev(int device_index, const float* pc
         const nc_loudness_cfg c = loudness_resolve_cfg(cfg, sample_rate);
         const int64_t* offs[2] = {off, out_off};
         loudness_check_clips(B, C, offs, 2, n);
-        loudness_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_loudness(g_dev[device_index], pcm, B, C, off, n, sample_rate, c, out, out_off, rows, static_cast<hipStream_t>(hip_stream));
+        g_loud.locked(device_index, [&](LoudDev& q) {
+            run_loudness(q, pcm, B, C, off, n, sample_rate, c, out, out_off, rows, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -547,37 +490,9 @@ extern "C" nc_status nc_audio_apply_gain_db_dev(int device_index, const float* p
         const int64_t* offs[2] = {off, out_off};
         loudness_check_clips(B, C, offs, 2, n);
         check_db(db, B);
-        loudness_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_gain(g_dev[device_index], pcm, B, C, off, n, db, out, out_off, static_cast<hipStream_t>(hip_stream));
+        g_loud.locked(device_index, [&](LoudDev& q) { run_gain(q, pcm, B, C, off, n, db, out, out_off, static_cast<hipStream_t>(hip_stream)); });
     });
 }
-
-namespace {
-
-// the plain calls: HOST buffers through the staging buffers, synchronous.  measure: loudness / normalize; db: apply_gain_db
-void host_buffer_call(int device_index, const float* pcm, int B, int C, const int64_t* off, const int64_t* n, int sample_rate, const nc_loudness_cfg* c,
-                      const float* db, float* out, const int64_t* out_off, nc_loudness_row* rows) {
-    loudness_device(device_index);
-    std::lock_guard<std::mutex> lk(g_mu);
-    LoudDev& q = g_dev[device_index];
-    const int R = B * C;
-    int64_t total = 0;
-    const std::vector<int64_t> packed = stage_in(q, pcm, R, off, n, C, &total);
-    if (out) q.out.reserve((size_t)(total > 0 ? total : 1) * sizeof(float));
-    if (c) {
-        q.out_rows.reserve((size_t)B * sizeof(nc_loudness_row));
-        run_loudness(q, q.in.as<float>(), B, C, packed.data(), n, sample_rate, *c, out ? q.out.as<float>() : nullptr, out ? packed.data() : nullptr,
-                     q.out_rows.as<nc_loudness_row>(), nullptr);
-    } else {
-        run_gain(q, q.in.as<float>(), B, C, packed.data(), n, db, q.out.as<float>(), packed.data(), nullptr);
-    }
-    NC_HIP(hipStreamSynchronize(nullptr));
-    if (c) NC_HIP(hipMemcpy(rows, q.out_rows.p, (size_t)B * sizeof(nc_loudness_row), hipMemcpyDeviceToHost));
-    if (out) stage_out(q, packed, R, n, C, out, out_off);
-}
-
-}  // namespace
 
 extern "C" nc_status nc_loudness(int device_index, const float* pcm, int32_t B, int32_t C, const int64_t* off, const int64_t* n, int32_t sample_rate,
                                  const nc_loudness_cfg* cfg, nc_loudness_row* out) {

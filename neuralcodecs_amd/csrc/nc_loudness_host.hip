@@ -142,8 +142,6 @@ void build_kweight_tables(int sample_rate, int filter, KwTables& t) {
 
 namespace {
 
-bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
-
 double dot_state(const double* w, const double* s) { return ((w[0] * s[0] + w[1] * s[1]) + w[2] * s[2]) + w[3] * s[3]; }
 
 // y[0..n) of one row, block by block

@@ -20,6 +20,9 @@
 
 NC_HD float nc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
+// neither an infinity nor a NaN: the test on the exponent bits that the kernels, their host twins and the argument checks share
+NC_HD bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
+
 // The order of ATen's argmin, which the reference's quantizers call on the distance matrix (Modules/DAC/VectorQuantizer.cs:121,
 // Modules/SNAC/VectorQuantizer.cs:137, Modules/Encodec/EuclideanCodebook.cs:181): a NaN distance beats every number, and among equal
 // distances (and among NaNs) the LOWER index wins -- so a partly-NaN row yields its first NaN, an all-equal row index 0.

@@ -56,13 +56,6 @@ static void check_pack_args(const void* a, const void* b, int B, int K, int64_t 
     if (bits <= 0 || bits > 24) fail(NC_EINVAL, "Bits must be between 1 and 24");   // BitPacker.cs MaxBits
 }
 
-static void pack_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
-
 extern "C" {
 
 int64_t nc_packed_bytes(int64_t n_values, int32_t bits) { return (n_values * bits + 7) / 8; }
@@ -70,7 +63,7 @@ int64_t nc_packed_bytes(int64_t n_values, int32_t bits) { return (n_values * bit
 static nc_status pack_impl(int device_index, const int64_t* codes, int B, int K, int64_t T, int bits, uint8_t* packed, hipStream_t s) {
     try {
         check_pack_args(codes, packed, B, K, T, bits);
-        pack_device(device_index);
+        use_checked_device(device_index);
         const int64_t nbytes = nc_packed_bytes((int64_t)K * T, bits), tot = (int64_t)B * nbytes;
         hipLaunchKernelGGL(pack_codes_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, codes, B, K, T, bits, packed, nbytes);
         NC_HIP(hipGetLastError());
@@ -83,7 +76,7 @@ static nc_status pack_impl(int device_index, const int64_t* codes, int B, int K,
 static nc_status unpack_impl(int device_index, const uint8_t* packed, int B, int K, int64_t T, int bits, int64_t* codes, hipStream_t s) {
     try {
         check_pack_args(codes, packed, B, K, T, bits);
-        pack_device(device_index);
+        use_checked_device(device_index);
         const int64_t nbytes = nc_packed_bytes((int64_t)K * T, bits), tot = (int64_t)B * K * T;
         hipLaunchKernelGGL(unpack_codes_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, packed, B, K, T, bits, codes, nbytes);
         NC_HIP(hipGetLastError());
@@ -106,7 +99,7 @@ nc_status nc_unpack_codes_dev(int device_index, const uint8_t* packed, int32_t B
 nc_status nc_pack_codes(int device_index, const int64_t* codes, int32_t B, int32_t K, int64_t T, int32_t bits, uint8_t* packed) {
     try {
         check_pack_args(codes, packed, B, K, T, bits);
-        pack_device(device_index);
+        use_checked_device(device_index);
         DevBuf dc, dp;
         const size_t nc_ = (size_t)B * K * T * 8, np = (size_t)B * nc_packed_bytes((int64_t)K * T, bits);
         dc.reserve(nc_); dp.reserve(np);
@@ -126,7 +119,7 @@ nc_status nc_pack_codes(int device_index, const int64_t* codes, int32_t B, int32
 nc_status nc_unpack_codes(int device_index, const uint8_t* packed, int32_t B, int32_t K, int64_t T, int32_t bits, int64_t* codes) {
     try {
         check_pack_args(codes, packed, B, K, T, bits);
-        pack_device(device_index);
+        use_checked_device(device_index);
         DevBuf dc, dp;
         const size_t nc_ = (size_t)B * K * T * 8, np = (size_t)B * nc_packed_bytes((int64_t)K * T, bits);
         dc.reserve(nc_); dp.reserve(np);

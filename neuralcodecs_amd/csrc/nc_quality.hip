@@ -11,8 +11,7 @@
 // the 16 frames of one tap fall into 16 distinct even banks and the tap beside it (lanes +16) into the odd ones -- ds_read_b32 serves 32
 // lanes per cycle over 32 banks, conflict-free for every even H.  The A operand comes straight from the cached table, stored per row as
 // four runs [n % 4][n / 4] so that a lane's taps of four consecutive instructions are one 16-byte load.
-#include <mutex>
-
+#include "nc_devcall.h"
 #include "nc_frag.h"
 #include "nc_guard.h"
 #include "nc_math.h"
@@ -149,8 +148,6 @@ __global__ __launch_bounds__(256) void mel_frame_sums_kernel(const StftRow* __re
     fs_log[rx.f0 + t] = fl;
 }
 
-__device__ __forceinline__ int finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
-
 // row state (doubles): 0 mean x, 1 mean y, 2 sum |x - y|, 3 sum yc yc, 4 sum xc yc, 5 scale
 constexpr int kRowState = 6;
 
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(64) void quality_finish_kernel(int phase, const Tim
     out[b] = o;
 }
 
-// ---- per-device state: the cached tables, one workspace, the pinned image of a call's row tables ---------------------------------------
+// ---- per-device state: the cached tables and one workspace beside the call scaffold (nc_devcall.h) --------------------------------------
 struct MelKey {
     int sr, M, W;
     float fmin, fmax;
@@ -300,90 +297,42 @@ struct MelKey {
 struct MelDev {
     DevBuf fb, lo, hi;
 };
+bool filled(const MelDev& d) { return d.fb.p != nullptr; }
 
 struct QualityDev {
+    DevCall call;
     std::map<std::pair<int, int>, DevBuf> basis;   // (W, window) -> [2 (W/2+1)][4][W/4]
     std::map<MelKey, MelDev> mel;
-    DevBuf mag, melbuf, fs, part, part_bad, state, row_bad, tables, in_est, in_ref, out_rows;
-    void* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t copied = nullptr, done = nullptr;
-    bool copied_used = false, done_used = false;
+    DevBuf mag, melbuf, fs, part, part_bad, state, row_bad, in_est, in_ref, out_rows;
 };
 
-std::mutex g_mu;
-// never destroyed: the buffers must not be freed behind the runtime's own teardown at process exit
-std::map<int, QualityDev>& g_dev = *new std::map<int, QualityDev>();
-
-void quality_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
+PerDevice<QualityDev> g_quality;
 
 const float* basis_on(QualityDev& q, int W, int window) {
-    DevBuf& d = q.basis[{W, window}];
-    if (d.p) return d.as<float>();
-    const int K = W / 2 + 1, Wq = W / 4;
-    std::vector<float> C((size_t)K * W), S((size_t)K * W), T((size_t)2 * K * W);
-    build_dft_basis(W, window, C.data(), S.data());
-    for (int k = 0; k < K; ++k)
-        for (int n = 0; n < W; ++n) {
-            const size_t at = (size_t)(n & 3) * Wq + (size_t)(n >> 2);
-            T[(size_t)(2 * k) * W + at] = C[(size_t)k * W + n];
-            T[(size_t)(2 * k + 1) * W + at] = S[(size_t)k * W + n];
-        }
-    d.reserve(T.size() * sizeof(float));
-    NC_HIP(hipMemcpy(d.p, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
-    return d.as<float>();
+    return cached_table(q.basis[{W, window}], [&](DevBuf& d) {
+        const int K = W / 2 + 1, Wq = W / 4;
+        std::vector<float> C((size_t)K * W), S((size_t)K * W), T((size_t)2 * K * W);
+        build_dft_basis(W, window, C.data(), S.data());
+        for (int k = 0; k < K; ++k)
+            for (int n = 0; n < W; ++n) {
+                const size_t at = (size_t)(n & 3) * Wq + (size_t)(n >> 2);
+                T[(size_t)(2 * k) * W + at] = C[(size_t)k * W + n];
+                T[(size_t)(2 * k + 1) * W + at] = S[(size_t)k * W + n];
+            }
+        fill_table(d, T.data(), T.size());
+    }).as<float>();
 }
 
 const MelDev& mel_on(QualityDev& q, int sr, int M, int W, float fmin, float fmax) {
-    MelDev& d = q.mel[MelKey{sr, M, W, fmin, fmax}];
-    if (d.fb.p) return d;
-    const int K = W / 2 + 1;
-    std::vector<float> fb((size_t)M * K);
-    std::vector<int32_t> lo((size_t)M), hi((size_t)M);
-    build_mel_filterbank(sr, M, W, fmin, fmax, fb.data(), lo.data(), hi.data());
-    d.fb.reserve(fb.size() * sizeof(float));
-    d.lo.reserve(lo.size() * sizeof(int32_t));
-    d.hi.reserve(hi.size() * sizeof(int32_t));
-    NC_HIP(hipMemcpy(d.fb.p, fb.data(), fb.size() * sizeof(float), hipMemcpyHostToDevice));
-    NC_HIP(hipMemcpy(d.lo.p, lo.data(), lo.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    NC_HIP(hipMemcpy(d.hi.p, hi.data(), hi.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return d;
-}
-
-// The workspace is one per device: a call on another stream first waits for the call before it.
-void begin_call(QualityDev& q, hipStream_t s) {
-    if (!q.copied) NC_HIP(hipEventCreateWithFlags(&q.copied, hipEventDisableTiming));
-    if (!q.done) NC_HIP(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    if (q.done_used) NC_HIP(hipStreamWaitEvent(s, q.done, 0));
-}
-void end_call(QualityDev& q, hipStream_t s) {
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipEventRecord(q.done, s));
-    q.done_used = true;
-}
-
-// the row tables of a call: written into pinned memory, copied once
-void* upload_tables(QualityDev& q, const void* src, size_t bytes, hipStream_t s) {
-    if (q.copied_used) NC_HIP(hipEventSynchronize(q.copied));   // the previous call's copy has read the pinned image
-    if (bytes > q.pin_cap) {
-        if (q.pin) (void)hipHostFree(q.pin);
-        q.pin = nullptr;
-        q.pin_cap = 0;
-        const size_t want = (bytes + 4095) & ~size_t(4095);
-        NC_HIP(hipHostMalloc(&q.pin, want, hipHostMallocDefault));
-        q.pin_cap = want;
-    }
-    memcpy(q.pin, src, bytes);
-    q.tables.reserve(bytes);
-    NC_HIP(hipMemcpyAsync(q.tables.p, q.pin, bytes, hipMemcpyHostToDevice, s));
-    NC_HIP(hipEventRecord(q.copied, s));
-    q.copied_used = true;
-    return q.tables.p;
+    return cached_table(q.mel[MelKey{sr, M, W, fmin, fmax}], [&](MelDev& d) {
+        const int K = W / 2 + 1;
+        std::vector<float> fb((size_t)M * K);
+        std::vector<int32_t> lo((size_t)M), hi((size_t)M);
+        build_mel_filterbank(sr, M, W, fmin, fmax, fb.data(), lo.data(), hi.data());
+        fill_table(d.fb, fb.data(), fb.size());
+        fill_table(d.lo, lo.data(), lo.size());
+        fill_table(d.hi, hi.data(), hi.size());
+    });
 }
 
 int hop_shift(int H) {
@@ -454,7 +403,7 @@ void run_metrics(QualityDev& q, const float* ref, const int64_t* ref_off, const 
         mel_floats = frames * c.n_mels[i] > mel_floats ? frames * c.n_mels[i] : mel_floats;
     }
     if (max_blk > (int64_t)0x7fffffff * 64) fail(NC_EINVAL, "a row is too long for one launch");
-    begin_call(q, s);
+    q.call.begin(s);
     q.mag.reserve((size_t)mag_floats * sizeof(float));
     q.melbuf.reserve((size_t)mel_floats * sizeof(float));
     q.fs.reserve((size_t)fs_total * 2 * sizeof(double));
@@ -468,7 +417,7 @@ void run_metrics(QualityDev& q, const float* ref, const int64_t* ref_off, const 
         basis[i] = basis_on(q, c.W[i], NC_WINDOW_HANN);
         mels[i] = &mel_on(q, sr, c.n_mels[i], c.W[i], c.fmin[i], c.fmax[i]);
     }
-    unsigned char* dev = static_cast<unsigned char*>(upload_tables(q, img.data(), bytes, s));
+    unsigned char* dev = static_cast<unsigned char*>(q.call.upload(img.data(), bytes, s));
     const TimeRow* d_tr = reinterpret_cast<const TimeRow*>(dev + o_time);
     const StftRow* d_sr = reinterpret_cast<const StftRow*>(dev + o_stft);
     const int64_t* d_f0 = reinterpret_cast<const int64_t*>(dev + o_f0);
@@ -492,7 +441,7 @@ void run_metrics(QualityDev& q, const float* ref, const int64_t* ref_off, const 
                            c.n_mels[i], c.clamp_eps, fs_mag + fa.fs_off[i], fs_log + fa.fs_off[i]);
     }
     finish(3);
-    end_call(q, s);
+    q.call.end(s);
 }
 
 // STFT and / or mel spectrogram of B rows of one buffer
@@ -507,13 +456,13 @@ void run_spectra(QualityDev& q, const float* pcm, int B, const int64_t* off, con
         frames += F;
         max_frames = F > max_frames ? F : max_frames;
     }
-    begin_call(q, s);
+    q.call.begin(s);
     if (md) q.mag.reserve((size_t)frames * K * sizeof(float));
     const float* basis = basis_on(q, W, window);
-    const StftRow* d_rows = static_cast<const StftRow*>(upload_tables(q, rows.data(), rows.size() * sizeof(StftRow), s));
+    const StftRow* d_rows = q.call.upload(rows, s);
     launch_stft(d_rows, B, max_frames, basis, W, H, out_c64, md ? q.mag.as<float>() : nullptr, s);
     if (md) launch_mel(d_rows, B, max_frames, q.mag.as<float>(), *md, K, M, out_mel, s);
-    end_call(q, s);
+    q.call.end(s);
 }
 
 }  // namespace
@@ -529,9 +478,9 @@ extern "C" nc_status nc_audio_stft_dev(int device_index, const float* pcm, int32
         quality_check_window(W, H, window);
         const int64_t* offs[2] = {off, out_off};
         quality_check_rows(B, offs, 2, n, &W, 1);
-        quality_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_spectra(g_dev[device_index], pcm, B, off, n, W, H, window, out_c64, nullptr, 0, nullptr, out_off, static_cast<hipStream_t>(hip_stream));
+        g_quality.locked(device_index, [&](QualityDev& q) {
+            run_spectra(q, pcm, B, off, n, W, H, window, out_c64, nullptr, 0, nullptr, out_off, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -545,11 +494,10 @@ extern "C" nc_status nc_audio_mel_spectrogram_dev(int device_index, const float*
         quality_check_mel(sample_rate, n_mels, fmin, fmax);
         const int64_t* offs[2] = {off, out_off};
         quality_check_rows(B, offs, 2, n, &W, 1);
-        quality_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        QualityDev& q = g_dev[device_index];
-        const MelDev& md = mel_on(q, sample_rate, n_mels, W, fmin, fmax);
-        run_spectra(q, pcm, B, off, n, W, H, NC_WINDOW_HANN, nullptr, &md, n_mels, out, out_off, static_cast<hipStream_t>(hip_stream));
+        g_quality.locked(device_index, [&](QualityDev& q) {
+            const MelDev& md = mel_on(q, sample_rate, n_mels, W, fmin, fmax);
+            run_spectra(q, pcm, B, off, n, W, H, NC_WINDOW_HANN, nullptr, &md, n_mels, out, out_off, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -561,9 +509,9 @@ extern "C" nc_status nc_quality_metrics_dev(int device_index, const float* ref, 
         const nc_quality_cfg c = quality_resolve_cfg(cfg, sample_rate);
         const int64_t* offs[2] = {ref_off, est_off};
         quality_check_rows(B, offs, 2, n, c.W, c.n_scales);
-        quality_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_metrics(g_dev[device_index], ref, ref_off, est, est_off, n, B, sample_rate, c, out, static_cast<hipStream_t>(hip_stream));
+        g_quality.locked(device_index, [&](QualityDev& q) {
+            run_metrics(q, ref, ref_off, est, est_off, n, B, sample_rate, c, out, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -574,24 +522,15 @@ extern "C" nc_status nc_quality_metrics(int device_index, const float* ref, cons
         const nc_quality_cfg c = quality_resolve_cfg(cfg, sample_rate);
         const int64_t* offs[2] = {ref_off, est_off};
         quality_check_rows(B, offs, 2, n, c.W, c.n_scales);
-        quality_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        QualityDev& q = g_dev[device_index];
-        std::vector<int64_t> packed((size_t)B);
-        int64_t total = 0;
-        for (int b = 0; b < B; ++b) {
-            packed[(size_t)b] = total;
-            total += n[b];
-        }
-        q.in_est.reserve((size_t)total * sizeof(float));
-        q.in_ref.reserve((size_t)total * sizeof(float));
-        q.out_rows.reserve((size_t)B * sizeof(nc_quality_row));
-        for (int b = 0; b < B; ++b) {
-            NC_HIP(hipMemcpy(q.in_est.as<float>() + packed[(size_t)b], est + est_off[b], (size_t)n[b] * sizeof(float), hipMemcpyHostToDevice));
-            NC_HIP(hipMemcpy(q.in_ref.as<float>() + packed[(size_t)b], ref + ref_off[b], (size_t)n[b] * sizeof(float), hipMemcpyHostToDevice));
-        }
-        run_metrics(q, q.in_ref.as<float>(), packed.data(), q.in_est.as<float>(), packed.data(), n, B, sample_rate, c, q.out_rows.as<nc_quality_row>(), nullptr);
-        NC_HIP(hipStreamSynchronize(nullptr));
-        NC_HIP(hipMemcpy(out, q.out_rows.p, (size_t)B * sizeof(nc_quality_row), hipMemcpyDeviceToHost));
+        g_quality.locked(device_index, [&](QualityDev& q) {
+            const PackedRows packed(B, n, 1, 1);   // HOST rows end to end, no padding
+            packed.copy_in(q.in_est, est, est_off);
+            packed.copy_in(q.in_ref, ref, ref_off);
+            q.out_rows.reserve((size_t)B * sizeof(nc_quality_row));
+            run_metrics(q, q.in_ref.as<float>(), packed.at.data(), q.in_est.as<float>(), packed.at.data(), n, B, sample_rate, c, q.out_rows.as<nc_quality_row>(),
+                        nullptr);
+            NC_HIP(hipStreamSynchronize(nullptr));
+            NC_HIP(hipMemcpy(out, q.out_rows.p, (size_t)B * sizeof(nc_quality_row), hipMemcpyDeviceToHost));
+        });
     });
 }

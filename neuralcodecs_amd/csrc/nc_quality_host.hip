@@ -101,8 +101,6 @@ void build_mel_filterbank(int sample_rate, int n_mels, int n_fft, float fmin, fl
 
 namespace {
 
-bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
-
 // the reflect-padded row: W/2 samples mirrored about the first and the last sample
 std::vector<float> padded_row(const float* x, int64_t n, int W) {
     const int half = W / 2;

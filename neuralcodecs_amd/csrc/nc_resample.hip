@@ -12,10 +12,9 @@
 // phases of one frame, i.e. four consecutive output samples: one 16-byte store where the address allows it.
 // resample_vec_kernel: the same chain, one thread per output sample, straight from global memory -- for ratios whose U leaves a 16-phase
 // tile mostly empty (U < 8) or whose stretch does not fit the LDS budget of one workgroup.
-#include <map>
-#include <mutex>
 #include <tuple>
 
+#include "nc_devcall.h"
 #include "nc_frag.h"
 #include "nc_guard.h"
 #include "nc_math.h"
@@ -124,26 +123,14 @@ __global__ __launch_bounds__(256) void resample_copy_kernel(const RsRow* __restr
     if (o < r.n_out) r.y[o] = r.x[o];
 }
 
-// ---- per-device state: the cached table images, the pinned image of a call's row table -------------------------------------------------
+// ---- per-device state: the cached table images beside the call scaffold (nc_devcall.h) -------------------------------------------------
 struct RsDev {
+    DevCall call;
     std::map<std::tuple<int64_t, int64_t, int, uint64_t>, DevBuf> tabs;   // (U, D, zeros, the bits of rolloff)
-    DevBuf tables, in, out;
-    void* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t copied = nullptr, done = nullptr;
-    bool copied_used = false, done_used = false;
+    DevBuf in, out;
 };
 
-std::mutex g_mu;
-// never destroyed: the buffers must not be freed behind the runtime's own teardown at process exit
-std::map<int, RsDev>& g_dev = *new std::map<int, RsDev>();
-
-void resample_device(int device_index) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
-    NC_HIP(hipSetDevice(device_index));
-}
+PerDevice<RsDev> g_resample;
 
 RsArgs args_of(const ResampleGeom& q) {
     RsArgs a;
@@ -165,61 +152,19 @@ int64_t lds_words(const ResampleGeom& q, const RsArgs& a) {
 
 bool takes_mfma(const ResampleGeom& q, const RsArgs& a) { return q.U >= kMfmaMinU && (size_t)lds_words(q, a) * sizeof(float) <= kLdsBudget; }
 
-// The image is built on first use and copied with a blocking hipMemcpy under the unit's lock: it has arrived before this or any later
-// call, on whichever stream, launches a kernel that reads it.
 const float* table_on(RsDev& d, const ResampleGeom& q, const RsArgs& a) {
-    DevBuf& t = d.tabs[std::make_tuple(q.U, q.D, q.zeros, __builtin_bit_cast(uint64_t, q.rolloff))];
-    if (t.p) return t.as<float>();
-    std::vector<float> h;
-    build_resample_table(q, h);
-    const size_t row = (size_t)4 * a.Q4;
-    std::vector<float> img((size_t)16 * a.tiles * row, 0.0f);   // rows U .. 16 tiles - 1 and the tail of every run stay +0
-    for (int64_t i = 0; i < q.U; ++i)
-        for (int64_t k = 0; k < q.K4; ++k) img[(size_t)i * row + (size_t)(k & 3) * a.Q4 + (size_t)(k >> 2)] = h[(size_t)(i * q.K4 + k)];
-    DevBuf fresh;
-    fresh.reserve(img.size() * sizeof(float));
-    NC_HIP(hipMemcpy(fresh.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    t = std::move(fresh);
-    return t.as<float>();
+    return cached_table(d.tabs[std::make_tuple(q.U, q.D, q.zeros, __builtin_bit_cast(uint64_t, q.rolloff))], [&](DevBuf& t) {
+        std::vector<float> h;
+        build_resample_table(q, h);
+        const size_t row = (size_t)4 * a.Q4;
+        std::vector<float> img((size_t)16 * a.tiles * row, 0.0f);   // rows U .. 16 tiles - 1 and the tail of every run stay +0
+        for (int64_t i = 0; i < q.U; ++i)
+            for (int64_t k = 0; k < q.K4; ++k) img[(size_t)i * row + (size_t)(k & 3) * a.Q4 + (size_t)(k >> 2)] = h[(size_t)(i * q.K4 + k)];
+        fill_table(t, img.data(), img.size());
+    }).as<float>();
 }
 
-// The row table is one per device: a call on another stream first waits for the call before it.
-void begin_call(RsDev& d, hipStream_t s) {
-    if (!d.copied) NC_HIP(hipEventCreateWithFlags(&d.copied, hipEventDisableTiming));
-    if (!d.done) NC_HIP(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
-    if (d.done_used) NC_HIP(hipStreamWaitEvent(s, d.done, 0));
-}
-void end_call(RsDev& d, hipStream_t s) {
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipEventRecord(d.done, s));
-    d.done_used = true;
-}
-
-// the row table of a call: written into pinned memory, copied once
-const RsRow* upload_rows(RsDev& d, const std::vector<RsRow>& rows, hipStream_t s) {
-    const size_t bytes = rows.size() * sizeof(RsRow);
-    if (d.copied_used) NC_HIP(hipEventSynchronize(d.copied));   // the previous call's copy has read the pinned image
-    if (bytes > d.pin_cap) {
-        if (d.pin) (void)hipHostFree(d.pin);
-        d.pin = nullptr;
-        d.pin_cap = 0;
-        const size_t want = (bytes + 4095) & ~size_t(4095);
-        NC_HIP(hipHostMalloc(&d.pin, want, hipHostMallocDefault));
-        d.pin_cap = want;
-    }
-    memcpy(d.pin, rows.data(), bytes);
-    d.tables.reserve(bytes);
-    NC_HIP(hipMemcpyAsync(d.tables.p, d.pin, bytes, hipMemcpyHostToDevice, s));
-    NC_HIP(hipEventRecord(d.copied, s));
-    d.copied_used = true;
-    return d.tables.as<RsRow>();
-}
-
-unsigned grid_of(int64_t items, int per_block) {
-    const int64_t g = (items + per_block - 1) / per_block;
-    if (g > 0xffffff) fail(NC_EINVAL, "a row is too long for one launch");   // 256 threads each: below 2^32 in all
-    return (unsigned)(g > 0 ? g : 1);
-}
+unsigned grid_of(int64_t items, int per_block) { return nc::grid_of(items, per_block, 0xffffff); }   // 256 threads each: below 2^32 in all
 
 void run_resample(RsDev& d, const ResampleGeom& q, bool copy, const float* pcm, int R, const int64_t* off, const int64_t* n, float* out,
                   const int64_t* out_off, hipStream_t s) {
@@ -234,16 +179,16 @@ void run_resample(RsDev& d, const ResampleGeom& q, bool copy, const float* pcm, 
     const RsArgs a = args_of(q);
     const bool mfma = !copy && takes_mfma(q, a);
     const unsigned gx = mfma ? grid_of((max_out + q.U - 1) / q.U, kFrames) : grid_of(max_out, 256);
-    begin_call(d, s);
+    d.call.begin(s);
     const float* T = copy ? nullptr : table_on(d, q, a);
-    const RsRow* d_rows = upload_rows(d, rows, s);
+    const RsRow* d_rows = d.call.upload(rows, s);
     if (copy)
         hipLaunchKernelGGL(resample_copy_kernel, dim3(gx, (unsigned)R), dim3(256), 0, s, d_rows);
     else if (mfma)
         hipLaunchKernelGGL(resample_mfma_kernel, dim3(gx, (unsigned)R), dim3(256), (size_t)lds_words(q, a) * sizeof(float), s, d_rows, T, a);
     else
         hipLaunchKernelGGL(resample_vec_kernel, dim3(gx, (unsigned)R), dim3(256), 0, s, d_rows, T, a);
-    end_call(d, s);
+    d.call.end(s);
 }
 
 }  // namespace
@@ -257,9 +202,9 @@ extern "C" nc_status nc_audio_resample_sinc_dev(int device_index, const float* p
     return guard([&] {
         const ResampleGeom q = resample_geom(src, dst, cfg);
         resample_check_rows(pcm, R, off, n, q, src == dst, out, out_off);
-        resample_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        run_resample(g_dev[device_index], q, src == dst, pcm, R, off, n, out, out_off, static_cast<hipStream_t>(hip_stream));
+        g_resample.locked(device_index, [&](RsDev& d) {
+            run_resample(d, q, src == dst, pcm, R, off, n, out, out_off, static_cast<hipStream_t>(hip_stream));
+        });
     });
 }
 
@@ -269,27 +214,16 @@ extern "C" nc_status nc_audio_resample_sinc(int device_index, const float* pcm, 
         const ResampleGeom q = resample_geom(src, dst, cfg);
         const bool copy = src == dst;
         resample_check_rows(pcm, R, off, n, q, copy, out, out_off);
-        resample_device(device_index);
-        std::lock_guard<std::mutex> lk(g_mu);
-        RsDev& d = g_dev[device_index];
-        // HOST rows -> the device staging buffers, every row at a multiple of four elements
-        std::vector<int64_t> pin((size_t)R), pout((size_t)R), no((size_t)R);
-        int64_t tin = 0, tout = 0;
-        for (int r = 0; r < R; ++r) {
-            no[(size_t)r] = copy ? n[r] : resample_len(n[r], q.U, q.D);
-            pin[(size_t)r] = tin;
-            pout[(size_t)r] = tout;
-            tin += (n[r] + 3) & ~(int64_t)3;
-            tout += (no[(size_t)r] + 3) & ~(int64_t)3;
-        }
-        d.in.reserve((size_t)(tin > 0 ? tin : 1) * sizeof(float));
-        d.out.reserve((size_t)(tout > 0 ? tout : 1) * sizeof(float));
-        for (int r = 0; r < R; ++r)
-            if (n[r] > 0) NC_HIP(hipMemcpy(d.in.as<float>() + pin[(size_t)r], pcm + off[r], (size_t)n[r] * sizeof(float), hipMemcpyHostToDevice));
-        run_resample(d, q, copy, d.in.as<float>(), R, pin.data(), n, d.out.as<float>(), pout.data(), nullptr);
-        NC_HIP(hipStreamSynchronize(nullptr));
-        for (int r = 0; r < R; ++r)
-            if (no[(size_t)r] > 0)
-                NC_HIP(hipMemcpy(out + out_off[r], d.out.as<float>() + pout[(size_t)r], (size_t)no[(size_t)r] * sizeof(float), hipMemcpyDeviceToHost));
+        g_resample.locked(device_index, [&](RsDev& d) {
+            // HOST rows -> the device staging buffers, every row at a multiple of four elements (the 16-byte store of the matrix-core kernel)
+            std::vector<int64_t> no((size_t)R);
+            for (int r = 0; r < R; ++r) no[(size_t)r] = copy ? n[r] : resample_len(n[r], q.U, q.D);
+            const PackedRows pin(R, n, 1, 4), pout(R, no.data(), 1, 4);
+            pin.copy_in(d.in, pcm, off);
+            pout.reserve(d.out);
+            run_resample(d, q, copy, d.in.as<float>(), R, pin.at.data(), n, d.out.as<float>(), pout.at.data(), nullptr);
+            NC_HIP(hipStreamSynchronize(nullptr));
+            pout.copy_out(d.out, out, out_off);
+        });
     });
 }

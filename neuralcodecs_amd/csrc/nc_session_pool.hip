@@ -422,10 +422,7 @@ nc_status nc_op_concat_copy(int device_index, int32_t elt, const void* a, int64_
         if (!a || !b || !dst || !desc) fail(NC_EINVAL, "null argument");
         if ((elt != 4 && elt != 8) || a_n <= 0 || b_n <= 0 || dst_n <= 0 || n_desc <= 0 || n_desc > 65535)
             fail(NC_EINVAL, "elt must be 4 or 8, the arrays non-empty, n_desc in 1..65535 (one launch)");
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
-        if (device_index < 0 || device_index >= n_dev) fail(NC_EINVAL, "device index out of range");
-        NC_HIP(hipSetDevice(device_index));
+        use_checked_device(device_index);
         SegTable t;
         for (int64_t i = 0; i < n_desc; ++i) {
             const int64_t* d = desc + 7 * i;

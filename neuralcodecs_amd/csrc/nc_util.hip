@@ -13,6 +13,13 @@ static thread_local std::string g_last_error;
 void set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
 const char* get_last_error() { return g_last_error.c_str(); }
 
+void use_checked_device(int device_index) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(NC_EDEVICE, "no HIP device available (the engine has no CPU fallback)");
+    if (device_index < 0 || device_index >= n) fail(NC_EINVAL, "device index out of range");
+    NC_HIP(hipSetDevice(device_index));
+}
+
 // ---- diagnostic switches: the one table (see nc_common.h) --------------------------------------------------------------------------
 namespace {
 struct EnvRow { const char* name; char kind; const char* doc; };

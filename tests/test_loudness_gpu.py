@@ -237,6 +237,32 @@ def test_host_buffer_calls_equal_the_twin():
     _same_buffers(g, want_g)
 
 
+def test_calls_on_two_streams_share_the_workspace_in_order():
+    """the per-device workspace and pinned row table across streams: two calls on a side stream (the second uploads a table of the
+    other filter kind while that stream is current), then, with no host synchronisation, a call on the default stream behind them"""
+    import torch
+    rate = 44100
+    rows = [np.float32(0.3) * R.signal(n, rate, 60 + n) for n in (5000, 147, 2353)]
+    cfg = LoudnessConfig("designed", -20.0)
+    want = L.kweight(rows, rate, "reference", host=True)
+    want_lev, want_rows = L.normalize_loudness(rows, rate, cfg, host=True)
+    dev = [torch.from_numpy(r).cuda() for r in rows]
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        got = L.kweight(dev, rate, "reference")
+        lev, lrows = L.normalize_loudness(dev, rate, cfg)
+    again = L.kweight(dev, rate, "reference")                                      # the default stream, behind the calls on `side`
+    torch.cuda.synchronize()
+    assert all(g.is_cuda and g.dtype == torch.float32 for g in got + lev + again)
+    for g, a, w in zip(got, again, want):
+        _same_buffers(g.cpu().numpy(), w)
+        _same_buffers(a.cpu().numpy(), w)
+    for g, w in zip(lev, want_lev):
+        _same_buffers(g.cpu().numpy(), w)
+    _same_rows({k: lrows[k].cpu().numpy() for k in KEYS}, want_rows)
+
+
 def test_refusals_leave_the_device_usable():
     import torch
     lib = _lib.lib()

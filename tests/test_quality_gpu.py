@@ -181,6 +181,28 @@ def test_encodec_round_trip_quality_stereo_rows():
     m.dispose()
 
 
+def test_calls_on_two_streams_share_the_workspace_in_order():
+    """the per-device workspace and pinned row table across streams: an STFT and a mel spectrogram on a side stream (the second uploads
+    a new basis and filterbank while that stream is current), then, with no host synchronisation, the STFT on the default stream"""
+    import torch
+    W, H = WH[0]
+    lens = [5000, 147, 2353]
+    buf = np.concatenate([R.signal(n, SR, 60 + n) for n in lens])
+    want, _, _ = stft_packed(buf, W, H, lengths=lens, host=True)
+    want_mel, _, _ = mel_spectrogram_packed(buf, SR, 128, 32, 20, lengths=lens, host=True)
+    dev = torch.from_numpy(buf).cuda()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        got, _, _ = stft_packed(dev, W, H, lengths=lens)
+        mel, _, _ = mel_spectrogram_packed(dev, SR, 128, 32, 20, lengths=lens)
+    again, _, _ = stft_packed(dev, W, H, lengths=lens)                              # the default stream, behind the calls on `side`
+    torch.cuda.synchronize()
+    assert got.is_cuda and mel.is_cuda and again.is_cuda
+    assert np.isfinite(want).all() and np.array_equal(got.cpu().numpy(), want) and np.array_equal(again.cpu().numpy(), want)
+    assert np.isfinite(want_mel).all() and np.array_equal(mel.cpu().numpy(), want_mel)
+
+
 def test_refusals_leave_the_device_usable():
     import torch
     L = _lib.lib()
