@@ -1167,6 +1167,83 @@ NC_API nc_status nc_audio_resample_sinc(int device_index, const float* pcm, int3
 NC_API nc_status nc_audio_resample_sinc_host(const float* pcm, int32_t R, const int64_t* off, const int64_t* n, int32_t src, int32_t dst,
                                              const nc_resample_cfg* cfg, float* out, const int64_t* out_off);
 
+/* ------------------------------------------------------------------------------------ inverse STFT, spectral masks, MFCC
+ * From a spectrogram back to PCM, rectangles of a spectrogram set to a value, and cepstral coefficients -- on the packed buffers of the
+ * forward transform above, so that a caller who removes a hum band or blanks a click never leaves them.  Every value is one fixed bit
+ * pattern (fl = one binary32 rounding; no libm on the data path; -ffp-contract=off), stated here so that the *_host twins
+ * (csrc/nc_spectral_host.hip: plain serial C++ on HOST pointers, no device) and the kernels (csrc/nc_spectral.hip) agree bit for bit; they
+ * share nc_math.h, the checks and the table builders (csrc/nc_spectral.h) and nothing of the arithmetic on bins or samples.
+ *   ISTFT   torch.istft(X, n_fft = W, hop_length = H, window = w, center = True, length = L) per row; W, H and the windows as in the
+ *           forward transform.  Row b: frames[b] >= 1 frames, X complex64 [W/2+1][frames] (re, im interleaved) at COMPLEX element
+ *           spec_off[b]; length[b] samples are written at out[out_off[b]]; length[b] = 0 (or length = NULL) means H (frames - 1), what torch
+ *           returns without a length (nc_audio_istft_len; -1 on bad arguments).
+ *   basis   T[n][j], n = 0..W-1, j = 0..W+1, evaluated in binary64 and rounded once, c_0 = c_{W/2} = 1 and c_k = 2 otherwise:
+ *             T[n][2k] = fl(w(n) c_k cos(2 pi ((k n) mod W) / W) / W),  T[n][2k+1] = fl(-w(n) c_k sin(2 pi ((k n) mod W) / W) / W)
+ *           and T[n][1] = T[n][W+1] = +0 exactly: the inverse real transform ignores the imaginary parts of bins 0 and W/2 (torch.istft of a
+ *           spectrum with only those set is 0).  A NaN or an infinity there still poisons the frame, as 0 x NaN does.  (nc_audio_idft_basis)
+ *   frame   y_t[n] = ONE chain over j ascending of fmaf(T[n][j], Xflat[j][t], acc) from acc = 0;  Xflat[2k] = re, Xflat[2k+1] = im.
+ *   OLA     p = i + W/2 is the padded position of output sample i; frame t covers p where 0 <= p - t H < W.  Over the covering frames, t
+ *           ascending:  num[i] = the binary32 sum of y_t[p - t H] from +0;  env[i] = fl(the binary64 sum of (double)w32(p - t H)^2 from 0),
+ *           w32 = the window in binary64 rounded once;  out[i] = fl(num[i] / env[i]).  Samples with p >= W + H (frames - 1), a requested
+ *           length past the covered span, are +0.  No floating-point atomics; a sample's value depends on nothing but its row.
+ *           A result that is a NaN is stored as the quiet NaN 0x7fc00000 (hosts and gfx950 make different NaNs).
+ *   NOLA    checked on the host before anything is launched (the envelope depends on W, H, the window, frames and the length only):
+ *           NC_EINVAL where a covered output sample has a binary64 envelope <= 1e-11 (torch's rule); Hann with H = W is refused.
+ *   groups  the frames go through a scratch of frames x W floats per row; the rows of a call run in groups whose scratch stays under a cap
+ *           (256 MiB by default; a row above the cap is a group of its own, a row above 2 GiB is refused).  Grouping changes no bit.
+ *           nc_audio_istft_workspace(device, set, &cap): set > 0 sets the cap in bytes, -1 restores the default, 0 keeps it; cap (nullable)
+ *           receives the value in force.
+ *   masks   nc_audio_spec_fill_*: per row the rectangle [k_lo, k_hi) x [t_lo, t_hi) of X [nbins][frames] is set to val exp(i val) =
+ *           (fl(val cos val), fl(val sin val)), evaluated in binary64: (0, 0) for val = 0.  An empty rectangle writes nothing; a row may be
+ *           named more than once.  One launch for all rows.  The index helpers restate the reference's interval test on a linspace:
+ *             nc_audio_mask_freq_bins:   bin_hz[k] = k (sample_rate / 2) / (nbins - 1) in binary64 with the reference's INTEGER
+ *               sample_rate / 2;  [k_lo, k_hi) = { k : fmin <= bin_hz[k] < fmax }, the float bounds widened
+ *             nc_audio_mask_time_frames: bin_t[t] = t duration / (frames - 1), compared the same way
+ *           (one bin or one frame: the only grid point is 0).  The reference's float32 linspace can differ from this exactly at a bin.
+ *           Deviation from the reference: it sends every UNMASKED bin through abs / angle / exp, which moves it by a few ulp; here
+ *           unmasked bins keep their bits.  fmin >= fmax or tmin >= tmax: NC_EINVAL (the reference throws).
+ *   MFCC    mfcc[c][t] = ONE chain over m ascending of fmaf(dct[c][m], L[m][t], acc) from acc = 0,  L = nc_logf(fl(mel[m][t] + log_offset)),
+ *           mel exactly what nc_audio_mel_spectrogram_* returns; a sum that is not finite gives L = NaN, and a NaN result is stored as
+ *           0x7fc00000.  nc_logf: the natural logarithm on the ln(1 + f) core of nc_log10f (csrc/nc_math.h; its measured bound against
+ *           binary64 is in tests/golden/spectral_bounds.json).  Output float [n_mfcc][frames] at out_off[b].
+ *           dct[c][m] = fl(cos(pi c (2m + 1) / (2 n_mels)) sqrt(2 / n_mels)), row 0 times 1 / sqrt 2, in binary64: the orthonormal DCT-II
+ *           (nc_audio_dct_matrix).  1 <= n_mfcc <= n_mels <= 512; log_offset a finite positive normal binary32.
+ *           Deviation from the reference: its DCTMatrix ends in select(0, 0) and so returns ONE row of n_mels values, with which
+ *           DSP.MFCC cannot produce n_mfcc coefficients; the evident intent (scale row 0) is built, tests/test_spectral_cpu.py
+ *           transcribes the member as written and asserts what it yields.
+ * All off[] / frames[] / length[] / k_*[] / t_*[] arrays are HOST arrays.
+ * NC_EINVAL, before anything is launched: a null pointer (length excepted); B outside [1, 32767]; a negative offset or length;
+ * frames[b] < 1; W, H or the window outside the forward transform's ranges; a NOLA failure; a rectangle outside [0, nbins] x
+ * [0, frames]; nbins outside [1, 1025]; a fill value that is not finite; the MFCC ranges above and those of the mel spectrogram.
+ *
+ * replaces: DSP.InverseSTFT                          AudioTools/AudioTensorDSP.cs:124-151 as _dev (DEVICE buffers, asynchronous on
+ *           `hip_stream`), plain (HOST buffers: upload, run, download) and _host (no device)
+ * replaces: DSP.MaskFrequencies                      AudioTools/AudioTensorDSP.cs:307-345 (nc_audio_mask_freq_bins + nc_audio_spec_fill_*)
+ * replaces: DSP.MaskTimesteps                        AudioTools/AudioTensorDSP.cs:356-394 (nc_audio_mask_time_frames + nc_audio_spec_fill_*)
+ * replaces: DSP.MFCC                                 AudioTools/AudioTensorDSP.cs:408-441 with DCTMatrix (:901-912) */
+NC_API int64_t nc_audio_istft_len(int64_t frames, int32_t W, int32_t H);
+NC_API nc_status nc_audio_idft_basis(int32_t W, int32_t window, float* T /* [W][W+2] */);
+NC_API nc_status nc_audio_istft_workspace(int device_index, int64_t set_bytes, int64_t* cap_bytes);
+NC_API nc_status nc_audio_istft_dev(int device_index, const float* spec_c64, int32_t B, const int64_t* spec_off, const int64_t* frames, int32_t W,
+                                    int32_t H, int32_t window, float* out, const int64_t* out_off, const int64_t* length, void* hip_stream);
+NC_API nc_status nc_audio_istft(int device_index, const float* spec_c64, int32_t B, const int64_t* spec_off, const int64_t* frames, int32_t W,
+                                int32_t H, int32_t window, float* out, const int64_t* out_off, const int64_t* length);
+NC_API nc_status nc_audio_istft_host(const float* spec_c64, int32_t B, const int64_t* spec_off, const int64_t* frames, int32_t W, int32_t H,
+                                     int32_t window, float* out, const int64_t* out_off, const int64_t* length);
+NC_API nc_status nc_audio_mask_freq_bins(int32_t sample_rate, int32_t nbins, float fmin_hz, float fmax_hz, int32_t* k_lo, int32_t* k_hi);
+NC_API nc_status nc_audio_mask_time_frames(float duration, int64_t frames, float tmin_s, float tmax_s, int64_t* t_lo, int64_t* t_hi);
+NC_API nc_status nc_audio_spec_fill_dev(int device_index, float* spec_c64, int32_t B, const int64_t* spec_off, const int64_t* frames,
+                                        int32_t nbins, const int32_t* k_lo, const int32_t* k_hi, const int64_t* t_lo, const int64_t* t_hi,
+                                        float val, void* hip_stream);
+NC_API nc_status nc_audio_spec_fill_host(float* spec_c64, int32_t B, const int64_t* spec_off, const int64_t* frames, int32_t nbins,
+                                         const int32_t* k_lo, const int32_t* k_hi, const int64_t* t_lo, const int64_t* t_hi, float val);
+NC_API nc_status nc_audio_dct_matrix(int32_t n_mfcc, int32_t n_mels, float* dct /* [n_mfcc][n_mels] */);
+NC_API nc_status nc_audio_mfcc_dev(int device_index, const float* pcm, int32_t B, const int64_t* off, const int64_t* n, int32_t sample_rate,
+                                   int32_t W, int32_t H, int32_t n_mels, float fmin, float fmax, int32_t n_mfcc, float log_offset, float* out,
+                                   const int64_t* out_off, void* hip_stream);
+NC_API nc_status nc_audio_mfcc_host(const float* pcm, int32_t B, const int64_t* off, const int64_t* n, int32_t sample_rate, int32_t W, int32_t H,
+                                    int32_t n_mels, float fmin, float fmax, int32_t n_mfcc, float log_offset, float* out, const int64_t* out_off);
+
 /* ------------------------------------------------------------------------------------ multi-GPU groups
  * The reference has no multi-device code; its callers batch clips (Examples/Program.cs:228-322, Models/Dia.cs:973-1002).  The path
  * shards over clips with no data-path exchange (every operator is per sample), so a group = one codec replica per GPU + ONE
@@ -1340,6 +1417,8 @@ NC_API nc_status nc_op_concat_copy(int device_index, int32_t elt, const void* a,
                                    const int64_t* desc, int64_t n_desc);
 /* nc_log10f (csrc/nc_math.h, the canonical log10 of the quality metrics) on n positive normal binary32 values, evaluated on the host */
 NC_API nc_status nc_op_log10f(const float* x, int64_t n, float* y);
+/* nc_logf (csrc/nc_math.h, the canonical natural logarithm of the MFCC) on n positive normal binary32 values, evaluated on the host */
+NC_API nc_status nc_op_logf(const float* x, int64_t n, float* y);
 /* weight-norm fold w = v/(||v||+1e-7)*g over dim-0 slices (host-side, what load_weights does) */
 NC_API nc_status nc_op_fold_weight_norm(const float* v, const float* g, int64_t d0, int64_t inner, float* w);
 /* The HBM-bound SNAC kernels, one at a time (host pointers in and out, like nc_op_conv1d).

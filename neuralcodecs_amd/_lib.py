@@ -322,6 +322,21 @@ SYMBOLS = [
     ("nc_audio_resample_sinc_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P, _P]),
     ("nc_audio_resample_sinc", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P]),
     ("nc_audio_resample_sinc_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(NcResampleCfg), _P, _P]),
+    ("nc_audio_istft_len", C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ("nc_audio_idft_basis", C.c_int, [C.c_int32, C.c_int32, _P]),
+    ("nc_audio_istft_workspace", C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nc_audio_istft_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("nc_audio_istft", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("nc_audio_istft_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("nc_audio_mask_freq_bins", C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nc_audio_mask_time_frames", C.c_int, [C.c_float, C.c_int64, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nc_audio_spec_fill_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_float, _P]),
+    ("nc_audio_spec_fill_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_float]),
+    ("nc_audio_dct_matrix", C.c_int, [C.c_int32, C.c_int32, _P]),
+    ("nc_audio_mfcc_dev", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                    C.c_float, _P, _P, _P]),
+    ("nc_audio_mfcc_host", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, _P,
+                                     _P]),
     ("nc_group_unique_id", C.c_int, [_P]),
     ("nc_group_create_rank", C.c_int, [C.c_int32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("nc_group_create_local", C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P)]),
@@ -357,6 +372,7 @@ SYMBOLS = [
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nc_op_concat_copy", C.c_int, [C.c_int, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64]),
     ("nc_op_log10f", C.c_int, [_P, C.c_int64, _P]),
+    ("nc_op_logf", C.c_int, [_P, C.c_int64, _P]),
     ("nc_op_fold_weight_norm", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
     ("nc_op_dwconv1d", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("nc_op_layer_norm", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P]),

@@ -112,9 +112,10 @@ NC_HD float nc_sigmoidf(float x) { return 1.0f / (1.0f + nc_expf(-x)); }
 // [sqrt(1/2), sqrt(2)), f = m - 1 (exact), s = f / (2 + f), z = s^2: ln m = f - f^2/2 + s (f^2/2 + z G(z)); then ln m / ln 10 and
 // k log10(2), both constants as a binary32 pair.  Zero, subnormals, negatives, inf and NaN are outside the domain (callers clamp first).
 // Measured against binary64 per decade of x: tests/golden/quality_bounds.json.
-NC_HD float nc_log10f(float x) {
+// the shared core: ln m and the exponent k of x = 2^k m
+NC_HD float nc_ln_mantissa(float x, int32_t& k) {
     const uint32_t ix = __builtin_bit_cast(uint32_t, x) - 0x3f3504f3u;
-    const int32_t k = (int32_t)ix >> 23;
+    k = (int32_t)ix >> 23;
     const float m = __builtin_bit_cast(float, (ix & 0x007fffffu) + 0x3f3504f3u);
     const float f = m - 1.0f;
     const float s = f / (2.0f + f);
@@ -124,11 +125,24 @@ NC_HD float nc_log10f(float x) {
     g = nc_fma(g, z, 0x1.9999f0p-2f);
     g = nc_fma(g, z, 0x1.555556p-1f);
     const float h = 0.5f * f * f;
-    const float ln = f - (h - s * nc_fma(z, g, h));
+    return f - (h - s * nc_fma(z, g, h));
+}
+NC_HD float nc_log10f(float x) {
+    int32_t k;
+    const float ln = nc_ln_mantissa(x, k);
     float r = nc_fma(ln, 0x1.bcb7b2p-2f, ln * -0x1.5b235ep-27f);
     const float kf = (float)k;
     r = nc_fma(kf, -0x1.ec10c0p-27f, r);
     return nc_fma(kf, 0x1.344136p-2f, r);
+}
+// The natural logarithm of a positive normal binary32 on the same core (the MFCC: AudioTensorDSP.cs:428 log): ln m + k ln 2 with ln 2 as
+// the binary32 pair 0x1.62e3p-1 + 0x1.2fefa2p-17, whose high part has 16 significant bits so that k times it is exact.  The domain is
+// nc_log10f's.  Measured against binary64 per decade of x: tests/golden/spectral_bounds.json.
+NC_HD float nc_logf(float x) {
+    int32_t k;
+    const float ln = nc_ln_mantissa(x, k);
+    const float kf = (float)k;
+    return nc_fma(kf, 0x1.62e300p-1f, nc_fma(kf, 0x1.2fefa2p-17f, ln));
 }
 
 #if defined(__HIPCC__)

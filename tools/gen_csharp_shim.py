@@ -15,6 +15,7 @@ Checked, not generated (hand-written against those stubs and against the referen
   bindings/csharp/Quality.Native.cs        QualityNative / LoudnessNative: static helpers over the round-trip quality, loudness
   bindings/csharp/Loudness.Native.cs       and resampling exports, held to the header's argument counts by check_templates as well.
   bindings/csharp/Resample.Native.cs       ResampleNative: the same for the band-limited resampler.
+  bindings/csharp/Spectral.Native.cs       SpectralNative: the same for the inverse STFT, the spectral masks and the MFCC.
                                     (Config/*Config.cs, Models/*.cs, NeuralCodecs.cs, Core/Exceptions) and holds the classes to them.
 dotnet is not available in the build image, so the files are cross-checked, not compiled.
 """
@@ -223,7 +224,7 @@ def gen_native(enums, structs, funcs, defines):
 # ---- hand-written model classes (bindings/csharp/*.Native.cs): checked here and in tests/test_csharp_shim_cpu.py -------------------------
 MODEL_FILES = ("DAC.Native.cs", "SNAC.Native.cs", "Encodec.Native.cs", "NeuralCodecs.Native.cs")
 # hand-written static helpers over the audio-tool exports: held to the header's argument counts like the model classes
-TOOL_FILES = ("Quality.Native.cs", "Loudness.Native.cs", "Resample.Native.cs")
+TOOL_FILES = ("Quality.Native.cs", "Loudness.Native.cs", "Resample.Native.cs", "Spectral.Native.cs")
 
 
 def model_sources():
